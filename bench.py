@@ -2,7 +2,7 @@
 """Headline benchmark: bootstrap replicates / second, 6-LV satisfaction model, N = 10,000 obs x 60 MVs
 (BASELINE.json configs[2]: Mode A, Scheme.PATH, scaled, 5,000 replicates per GPU -- weak scaling).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch: every rank resamples + solves its shard of the replicate
@@ -11,7 +11,13 @@ libplspm_hip.so itself: plspm_group_bootstrap) merges the B x 156 result rows --
 inside the timed region.  Rank 0 prints one JSON line.  No torch: under `python -m torch.distributed.run` the launcher
 only spawns the ranks (RANK / LOCAL_RANK / WORLD_SIZE); without a launcher `--gpus N` drives N GPUs from this process.
 
-Extra objects on the line:
+A plain run sets up, brings the device to its working clocks (the spin-up below), runs the W warm-up and the K timed steps
+and prints the line: metric, value, unit, ms_per_step, dtype, config.  --dump-outputs DIR writes the records of the last
+timed step as a caller receives them (rows / status / iterations, float64 .npy; inputs fixed by the arguments).  Everything
+else -- the extra objects below, the `cold` figure, kernels_ms_per_step and the checks of the timed records against the
+committed oracle row -- runs with --full only.
+
+Extra objects on a --full line:
   roofline      dominant kernel, duration measured with HIP events on the library's own stream during the timed steps.  Default path:
                 gram_i8p_kernel<S, MTW, 64> (round 4: S digit planes -- 6 on this data, `digit_planes` -- four waves per workgroup, each
                 MTW count tiles x 32 pairs x S planes of 16x16x64 int8 MFMA accumulators, count fragments straight from global memory) --
@@ -58,7 +64,23 @@ def synth_inputs():
 
 
 SPINUP_STEPS = 200      # untimed launches of the same step before the W warm-up steps (device clocks / power state; ~0.13 s)
-PROF_EVERY = 4          # a HIP-event pair around the dominant kernel of every 4th timed step (every step when fewer than 8 are timed)
+PROF_EVERY = 4          # --full: a HIP-event pair around the dominant kernel of every 4th timed step (every step when fewer than 8 are timed)
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy payload in all
+
+
+def dump_outputs(dirname, rows, status, iters):
+    """The records of the timed path's last step as its caller receives them (plspm_bootstrap_device, then the host copy): rows
+    [B, 156], status [B], iterations [B], all float64.  A batch beyond DUMP_BYTES keeps a fixed seeded sample of its replicates,
+    in replicate-id order; row_index.npy names them."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {"rows": rows, "status": status, "iterations": iters}
+    per_replicate = 8 * (rows.shape[1] + 2)
+    if per_replicate * len(rows) > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(len(rows), DUMP_BYTES // (per_replicate + 8), replace=False))
+        out = {name: a[keep] for name, a in out.items()}
+        out["row_index"] = keep
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_worker(args):
@@ -254,6 +276,9 @@ def main():
                                                                                "(group option gather_root: ncclSend / ncclRecv, 1 / N of the bytes; only rank 0 checks the merged records)")
     ap.add_argument("--no-transport-calibration", action="store_true", help="keep RCCL as created (skip the untimed comparison with channel-capped RCCL / the copy-engine exchange)")
     ap.add_argument("--gram-path", type=int, default=0, choices=[0, 1, 2], help="0 library default (int8 digit planes), 1 fp64 MFMA Gram, 2 int8 digit planes")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the records of the last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: cold figure, roofline, per-kernel times, checks against the oracle row, "
+                                                         "the other routes / precisions / sizes, API-inclusive and CPU baselines (the --no-* options trim it)")
     args = ap.parse_args()
 
     from plspm import _native, parallel
@@ -337,17 +362,18 @@ def main():
             live["group"].barrier()                            # every rank of the job (all-reduce of one word over RCCL)
 
     # cold figure: the W warm-up steps and K timed steps straight after the upload, BEFORE the spin-up below -- what the driver's
-    # --warmup alone buys (reported beside `value`; every rank makes the same calls)
-    for _ in range(args.warmup):
-        step()
-    fence()
-    cold_t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
-    cold_elapsed = time.perf_counter() - cold_t0
-    if group is not None:
-        cold_elapsed = group.max(cold_elapsed)
+    # --warmup alone buys (reported beside `value` by --full; every rank makes the same calls)
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        fence()
+        cold_t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        cold_elapsed = time.perf_counter() - cold_t0
+        if group is not None:
+            cold_elapsed = group.max(cold_elapsed)
     # spin-up: steps straight after an idle period run 10-16 % slower than steps in a stream (`cold` on the line against `value`: 0.55-0.59
     # against 0.48-0.51 ms per step in the round-3 / round-4 driver runs: clocks / power state), and W is the driver's choice -- so the device
     # is brought to its working state with SPINUP_STEPS of the same launches before the W warm-up steps; nothing of it is reused by the
@@ -433,7 +459,7 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    profiled = group is None                                   # single stream: the HIP events of the timed region see each kernel alone
+    profiled = args.full and group is None                     # single stream: the HIP events of the timed region see each kernel alone
     if profiled:
         model.profile(True)
         model.profile_reset()
@@ -453,6 +479,12 @@ def main():
     if profiled:
         model.profile(False)
         gram_timed = model.profile_read("gram")
+    holds_records = not (group is not None and args.gather == "root" and rank != 0)      # (--gather root: the merged records exist on rank 0 only)
+    timed_records = None                                       # (rows, status, iters) of the LAST timed step, before anything else runs
+    if args.dump_outputs and rank == 0 and holds_records:
+        timed_records = model.fetch(0, B_total) if group is None else group.rows()
+        dump_outputs(args.dump_outputs, *timed_records)
+    if profiled:
         # the other kernels of a step (kernels_ms_per_step): ten more steps with every kernel bracketed, outside the timed region
         model.profile(True)
         model.profile_reset()
@@ -463,28 +495,29 @@ def main():
     if group is not None:
         elapsed = group.max(elapsed)                           # max over ranks
 
-    # what was timed is correct: every replicate of the last step converged, the gathered records are complete and in order
-    last_offset = (state["k"] - 1) * B_total
-    holds_records = not (group is not None and args.gather == "root" and rank != 0)      # (--gather root: the merged records exist on rank 0 only)
-    if group is not None and holds_records:
-        rows_l, status_l, iters_l = group.rows()
-    elif group is None:
-        rows_l, status_l, iters_l = model.fetch(0, B_total)
-    probe = B_total - 3                                        # a row owned by the last rank
-    one, _, _ = model.bootstrap(1, seed=1, rep_offset=last_offset + probe)
-    if holds_records:
-        assert rows_l.shape == (B_total, width) and np.all(status_l == 0), "a replicate of the timed batch failed"
-        assert np.array_equal(rows_l[probe], one[0]), "sharded stream differs from the single-GPU stream"
-    # ... and equals the reference arithmetic: replicate 0 of the seeded stream against the committed oracle row
-    # (tests/golden/bench_guard.npz, made by tests/golden/make_bench_guard.py with the oracle)
-    rows, status, iters = model.bootstrap(8, seed=1, rep_offset=0)
-    assert np.all(status == 0), status
-    guard = np.load(os.path.join(ROOT, "tests", "golden", "bench_guard.npz"))
-    idx0 = _native.bootstrap_indices(1, 0, N_OBS)
-    assert int(idx0.astype(np.int64).sum()) == int(guard["idx_sum"]) and np.array_equal(idx0[:16], guard["idx_head"]), "resampling stream changed"
-    assert int(guard["iterations"]) == iters[0] and np.allclose(rows[0], guard["row"], rtol=1e-8, atol=1e-11), "timed path disagrees with the oracle"
+    iters_l = timed_records[2] if timed_records is not None else None
+    if args.full:
+        # what was timed is correct: every replicate of the last step converged, the gathered records are complete and in order
+        last_offset = (state["k"] - 1) * B_total
+        if group is not None and holds_records:
+            rows_l, status_l, iters_l = group.rows()
+        elif group is None:
+            rows_l, status_l, iters_l = model.fetch(0, B_total)
+        probe = B_total - 3                                    # a row owned by the last rank
+        one, _, _ = model.bootstrap(1, seed=1, rep_offset=last_offset + probe)
+        if holds_records:
+            assert rows_l.shape == (B_total, width) and np.all(status_l == 0), "a replicate of the timed batch failed"
+            assert np.array_equal(rows_l[probe], one[0]), "sharded stream differs from the single-GPU stream"
+        # ... and equals the reference arithmetic: replicate 0 of the seeded stream against the committed oracle row
+        # (tests/golden/bench_guard.npz, made by tests/golden/make_bench_guard.py with the oracle)
+        rows, status, iters = model.bootstrap(8, seed=1, rep_offset=0)
+        assert np.all(status == 0), status
+        guard = np.load(os.path.join(ROOT, "tests", "golden", "bench_guard.npz"))
+        idx0 = _native.bootstrap_indices(1, 0, N_OBS)
+        assert int(idx0.astype(np.int64).sum()) == int(guard["idx_sum"]) and np.array_equal(idx0[:16], guard["idx_head"]), "resampling stream changed"
+        assert int(guard["iterations"]) == iters[0] and np.allclose(rows[0], guard["row"], rtol=1e-8, atol=1e-11), "timed path disagrees with the oracle"
 
-    if not profiled:
+    if args.full and not profiled:
         # N > 1: the kernels of the timed region overlap the previous step's collective, so the dominant kernel is timed on a
         # calibration pass of the same launches on the handle's stream alone (same B per GPU, same data)
         model.sync()
@@ -496,7 +529,7 @@ def main():
         model.profile(False)
 
     single_call = None
-    if group is not None:
+    if args.full and group is not None:
         # ONE call of the whole job (configs[3] as a user issues it: Plspm(bootstrap_iterations = N x 5,000, devices = ...)): enqueue -> every rank's
         # records gathered on every rank, nothing of a neighbouring call to hide under.  With one sub-batch the whole gather is exposed; with the
         # automatic sub-batches (plspm_group_bootstrap, round 5) only the last, smallest one.  Median of 7 calls each, max over ranks.
@@ -519,7 +552,7 @@ def main():
         fence()
 
     pcie = None
-    if world == 1 and group is None:
+    if args.full and world == 1 and group is None:
         # the same batch through the host-buffer entry point (records copied back over PCIe every step); never `value`
         host = (np.empty((B_total, width)), np.empty(B_total, dtype=np.int32), np.empty(B_total, dtype=np.int32))     # caller-owned, re-used
         for _ in range(3):
@@ -529,7 +562,9 @@ def main():
             model.bootstrap(B_total, seed=1, out=host)
         pcie = B_total * 10 / (time.perf_counter() - t1)
 
-    if rank == 0:
+    used_path, slices = timed_launch["last_gram_path"], timed_launch["last_i8_slices"]
+    other = planes = round3 = None
+    if rank == 0 and args.full:
         gram_ms, gram_n = gram_timed if profiled else model.profile_read("gram")
         res_ms, res_n = model.profile_read("resample")
         sol_ms, sol_n = model.profile_read("solver")
@@ -673,6 +708,7 @@ def main():
             round3 = {"kernel": k3,
                       "gram_avg_launch_ms": round(g3_ms / max(g3_n, 1), 4), "ms_per_step": round(dt3 * 1e3, 4), "records_bit_identical": same,
                       "note": "20 steps with set_option('i8_priv', 0) behind 100 spin-up steps, every Gram launch between HIP events"}
+    if rank == 0:
         parallelism = ("one process, one GPU, no collective" if group is None else
                        "replicate-sharded x%d (%s), ONE ncclAllGather per step issued by libplspm_hip.so on a gather stream "
                        "(overlaps the next step's kernels; records double-buffered)" % (world, "one process per GPU" if launched else "one process, %d GPUs" % world))
@@ -689,22 +725,24 @@ def main():
                            "below a quarter of the a-priori rounding bound of an fp64 accumulation of the same terms -- `digit_planes`).  Measured on this "
                            "data against 80-bit sums (`digit_planes.moment_error_vs_80bit`): seven planes sit below the fp64 MFMA route's error, the "
                            "automatic %d planes within a small multiple of it -- all nine orders below the 1e-6 the records are held to; the seven-plane "
-                           "rate is on the line beside `value`" % (slices, slices)) if used_path == 2 else "fp64 throughout",
+                           "rate is on the --full line beside `value`" % (slices, slices)) if used_path == 2 else "fp64 throughout",
             "config": {"workload": "synthetic 10,000 obs x 60 MVs x 6 LVs, Mode A, Scheme.PATH, scaled, %d bootstrap replicates per GPU "
                                    "(BASELINE.json configs[2]; %d GPUs x %d = configs[3] at 8); on-device Philox resampling, a fresh replicate-id "
                                    "range every step; X resident in HBM" % (args.reps_per_gpu, world, args.reps_per_gpu),
-                       "replicates_per_step": B_total, "iterations_per_replicate": [int(iters_l.min()), int(iters_l.max())],
+                       "replicates_per_step": B_total,
+                       "iterations_per_replicate": [int(iters_l.min()), int(iters_l.max())] if iters_l is not None else None,     # (records fetched: --full / --dump-outputs)
                        "parallelism": parallelism, "transport": transport, "ranks_seen_by_rccl": ranks_seen if transport == "rccl" else 0,
                        "replicate_ranges": [[a, a + n] for a, n in shards], "solver_kernel": {1: "solver_kernel", 2: "solver_rows_kernel", 3: "solver_wave_kernel<8>", 4: "solver_rows_split_kernel", 5: "solver_quad_kernel<16>", 6: "solver_wave16_kernel<16>", 7: "solver_wave16_kernel<8>", 8: "solver_wave16_kernel<32>"}.get(timed_launch["last_solver"], "?"),
                        "gram_tile_plan_cus": plan_cus, "transport_calibration": transport_cal,
                        "comm_create_s": comm_create_s, "upload_s_per_device": upload_s, "single_call_latency_ms": single_call},
-            "roofline": roofline,
             "spinup": "%d untimed steps (%.2f s) of the same launches before the %d warm-up steps: brings the device to its working clocks" % (spin_steps, spin_s, args.warmup),
-            "cold": {"value": round(B_total * args.steps / cold_elapsed, 1), "unit": "replicates/s", "ms_per_step": round(cold_elapsed / args.steps * 1e3, 4),
-                     "note": "the same %d timed steps behind %d warm-up steps only, measured before the spin-up (device coming out of idle)" % (args.steps, args.warmup)},
-            "kernels_ms_per_step": {"resample": round(res_ms / max(res_n, 1), 4), "gram": round(gram_avg_ms, 4),
-                                    "solver": round(sol_ms / max(sol_n, 1), 4)},
         }
+        if args.full:
+            line["roofline"] = roofline
+            line["cold"] = {"value": round(B_total * args.steps / cold_elapsed, 1), "unit": "replicates/s", "ms_per_step": round(cold_elapsed / args.steps * 1e3, 4),
+                            "note": "the same %d timed steps behind %d warm-up steps only, measured before the spin-up (device coming out of idle)" % (args.steps, args.warmup)}
+            line["kernels_ms_per_step"] = {"resample": round(res_ms / max(res_n, 1), 4), "gram": round(gram_avg_ms, 4),
+                                           "solver": round(sol_ms / max(sol_n, 1), 4)}
         if planes is not None:
             line["digit_planes"] = planes
             # the rate that is no worse than fp64 BY CONSTRUCTION (seven planes: correctly rounded sums; what Plspm(..., precision="strict") runs and
@@ -722,11 +760,11 @@ def main():
                                                                            model.get_option("boot_align") or model.get_option("boot_round_units")),
                                       "note": "plspm_bootstrap(): the B x 158 records copied to the caller's (pageable, re-used) host buffers through pinned staging every step; "
                                               "round 5: the call runs as sub-batches, the download + unpacking of sub-batch k beside the kernels of k + 1"}
-        if world == 1 and group is None and not args.no_api:
+        if args.full and world == 1 and group is None and not args.no_api:
             line["api_inclusive"] = api_inclusive(X, args.reps_per_gpu)
             line["api_inclusive"]["frac_of_value"] = round(line["api_inclusive"]["value"] / line["value"], 3)
             line["api_inclusive"]["frac_of_cold_value"] = round(line["api_inclusive"]["value"] / line["cold"]["value"], 3)      # (an API call starts on an idle device, as `cold` does)
-        if world == 1 and group is None and not args.no_next_rows:
+        if args.full and world == 1 and group is None and not args.no_next_rows:
             # SURVEY 8(f) "next" rows beside the headline, measured by this run (child processes: their handles, their clocks): the categorical
             # (Scale.ORD, five-point) counterpart of the headline workload at 1,000 and 5,000 replicates per step -- tools/categorical_bench.py
             import subprocess
@@ -755,7 +793,7 @@ def main():
             line["next_rows"] = {"nonmetric_num_bootstrap": num, "categorical_bootstrap": cat, "metric_models_next_to_the_headline": sizes, "hoc_two_stage_bootstrap": hoc,
                                  "note": "not part of `value`: ORD / NOM optimal scaling on 300 indicator columns (10k x 60 five-point items x 6 LVs), one wave per problem, "
                                          "count matrices written by the int8 product as uint16, stop rule as an int8 matrix product; DESIGN 5c"}
-        if world == 1 and group is None and not args.no_single_fit:
+        if args.full and world == 1 and group is None and not args.no_single_fit:
             # SURVEY 8(d) "plus single-fit latency for C2 and C5": BASELINE.json configs[1] and configs[4] through plspm_upload / plspm_fit, in a child
             # process (tools/fit_bench.py: its own handle and 1.6 GB matrix; HIP-event kernel times, walls with and without upload / scores download,
             # A_fit / F_fit rooflines)
@@ -768,7 +806,7 @@ def main():
                                               "upload_ms = plspm_upload of the fp64 matrix from pageable host memory (PCIe); never part of `value`"}
             except Exception as e:                                        # noqa: BLE001 -- an extra of the line, never its failure
                 line["single_fit"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
             # the real reference cannot travel to this box: its rate measured in the build container, and the factor between the oracle and
             # the reference measured there back to back (oracle/time_calibration.py -> profiles/r05_cpu_calibration.json), convert this

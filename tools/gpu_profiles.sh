@@ -8,9 +8,9 @@ O=$R/gpurun_out/profiles_$TAG
 rm -rf $O; mkdir -p $O
 cd $R
 bash tools/gpu_profiles_headline.sh $TAG      # bench line, kernel trace, HBM counters, summary (profiles/<tag>_bench_n1.json, _rocprof_summary.*, _gram_i8_traffic.json)
-timeout 300 python bench.py --group --no-cpu-baseline --no-api --no-next-rows --no-single-fit 2>/dev/null | tail -1 > $O/bench_n1_group_rccl.json
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $O/bench_n1_launcher_rccl.json
-PLSPM_BENCH_SHARED_DEVICE=1 timeout 300 python bench.py --gpus 2 --no-cpu-baseline --no-api --no-next-rows --no-single-fit 2>/dev/null | tail -1 > $O/bench_seam_2ranks_one_device.json
+timeout 300 python bench.py --full --group --no-cpu-baseline --no-api --no-next-rows --no-single-fit 2>/dev/null | tail -1 > $O/bench_n1_group_rccl.json
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --full --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $O/bench_n1_launcher_rccl.json
+PLSPM_BENCH_SHARED_DEVICE=1 timeout 300 python bench.py --gpus 2 --full --no-cpu-baseline --no-api --no-next-rows --no-single-fit 2>/dev/null | tail -1 > $O/bench_seam_2ranks_one_device.json
 # round 5: the persistent Gram against the tiled launch (with the experiments build: the same launches without epilogue stores), what the group path
 # costs a one-rank step, the host-buffer entry point under the sub-batch options
 [ -f plspm-python_amd/csrc/build/exp_i8/libplspm_hip_exp.so ] && (for a in "5000" "2500" "5000 7"; do PLSPM_HIP_LIB=$R/plspm-python_amd/csrc/build/exp_i8/libplspm_hip_exp.so timeout 300 python tools/persist_ab.py $a; done) 2>/dev/null | grep "^{" > $O/persist_ab.jsonl
@@ -41,7 +41,7 @@ timeout 120 python tools/experiments/cat_bound_probe.py > $O/categorical_bound_p
 import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps({'option': '$o', 'kernel_ms': d['kernel_ms'], 'gram_kernel': d['roofline']['gram_kernel'], 'iterations': d['iterations']}))"; done) > $O/c5_ring_ab.jsonl
 timeout 300 python tools/api_phase_times.py 2>&1 | grep "^{" > $O/api_phase_times.jsonl
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_F64 -d $O/prof_pmc1 -o pmc1 -- python $R/bench.py --no-cpu-baseline --no-api --no-next-rows --no-single-fit --steps 3 --warmup 1 > $O/prof_pmc1.log 2>&1
+timeout 600 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_F64 -d $O/prof_pmc1 -o pmc1 -- python $R/bench.py --full --no-cpu-baseline --no-api --no-next-rows --no-single-fit --steps 3 --warmup 1 > $O/prof_pmc1.log 2>&1
 timeout 600 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_F64 -d $O/prof_c5_pmc1 -o pmc1 -- python $R/tools/fit_bench.py c5 > $O/prof_c5_pmc1.log 2>&1
 timeout 600 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VALU SQ_INSTS_VALU -d $O/prof_c5_pmc2 -o pmc2 -- python $R/tools/fit_bench.py c5 > $O/prof_c5_pmc2.log 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE -d $O/prof_c5_fetch -o fetch -- python $R/tools/fit_bench.py c5 > $O/prof_c5_fetch.log 2>&1

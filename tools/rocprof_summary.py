@@ -32,7 +32,7 @@ def main():
         pct = 100.0 * total / tot_all
         out["kernels"].append({"kernel": short(name), "calls": calls, "total_us": round(total, 3), "avg_us": round(avg, 3), "pct": round(pct, 2)})
         lines.append("| %s | %d | %.1f | %.2f | %.2f |" % (short(name), calls, total, avg, pct))
-    # the dominant kernel by phase of the bench command (bench.py: W + K cold steps, 200 spin-up steps, W warm-up steps, the K TIMED
+    # the dominant kernel by phase of the bench command (bench.py --full: W + K cold steps, 200 spin-up steps, W warm-up steps, the K TIMED
     # steps, then the profiled / validation launches): the timed-region average is the one the bench line's roofline.avg_launch_ms --
     # HIP events on every 10th timed step of its own run -- has to agree with; the log of the traced run (argv[5]) carries that line
     W, K, SPIN = 5, 50, 200
