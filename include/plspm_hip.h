@@ -354,6 +354,32 @@ int plspm_bootstrap_summary(plspm_model_t* m, const void* d_rows, int64_t B, int
                             int64_t* n_used);
 
 /*
+ * ---- Two-group permutation test (multi-group analysis) -------------------------------------------------------------------------
+ * Is an estimate different between two groups of the rows?  Permutation r (global id) splits the N uploaded rows into group a of n1 rows
+ * and group b of N - n1: row i carries the key  word (i & 3) of Philox4x32-10(counter = (i >> 2, 1, lo32(r), hi32(r)), key = (lo32(seed),
+ * hi32(seed)))  (the bootstrap's stream with counter word 1 = 1 instead of 0), and group a holds the n1 rows with the smallest (key, row)
+ * pairs in lexicographic order -- exactly n1 rows, a function of (seed, r, N, n1) only.  Both groups are estimated like bootstrap
+ * replicates (same record layout; each group's own n, treatment and `scaled` scalar from its moments), on the int8 Gram route with at
+ * least seven digit planes (correctly rounded moment sums whatever the group size), whatever "gram_path" / "i8_min_batch" say.
+ * Plain metric handles only (no non-metric scales, missing values or two-stage pair): PLSPM_E_ARG otherwise; PLSPM_E_LIMIT where the int8
+ * route is closed (N >= 2^24, digit planes above their budget).
+ *
+ * plspm_permutation_device: permutations [rep_offset, rep_offset + B), 1 <= B <= 2^29, 1 <= n1 < N.  Enqueues 2B problems: record 2p =
+ *   group a of permutation rep_offset + p, record 2p + 1 = its group b; they stay on the handle as its last records (plspm_bootstrap_fetch
+ *   reads them; 2B of them).  *d_out / *d_status / *d_iters as plspm_bootstrap_device.
+ *   member  NULL: the splits above, drawn on the device;  else [B*N] host bytes 0/1, row p = the membership of permutation p (group a = 1),
+ *           each with exactly n1 ones (test seam, like `idx` of plspm_bootstrap).
+ * plspm_permutation_counts: on the handle's last 2B records (B of the last plspm_permutation_device call), per result column j
+ *   exceed[j] = #{valid p : |d_pj| >= |observed_diff[j]|},  d_pj = record[2p][j] - record[2p + 1][j];  a NaN on either side counts as
+ *   "not >=".  Valid: both records of the permutation have status PLSPM_OK; *n_used = their number (may be NULL).
+ *   observed_diff [R] host (est_a - est_b on the observed split), exceed [R] host.
+ *   p-value of this project: p_j = (1 + exceed[j]) / (1 + n_used), NaN where observed_diff[j] is NaN.
+ */
+int plspm_permutation_device(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offset, int64_t n1, const uint8_t* member, void** d_out,
+                             void** d_status, void** d_iters);
+int plspm_permutation_counts(plspm_model_t* m, int64_t B, const double* observed_diff, int64_t* exceed, int64_t* n_used);
+
+/*
  * ---- Multi-GPU: replicate shards + ONE RCCL all-gather --------------------------------------------------------------------------
  * Reference: Bootstrap.__init__ forks `processes` workers, each running iterations / processes replicates, and merges their
  * frames through a Queue (plspm/bootstrap.py:89-111; `processes` kwarg plspm/plspm.py:35-37,60-61).  Here a GROUP of handles --

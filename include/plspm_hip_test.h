@@ -35,6 +35,10 @@ int plspm_bootstrap_moments(plspm_model_t* m, int64_t B, uint64_t seed, int64_t 
 /* The resample indices the on-device RNG uses for replicate `rep` (host-side mirror, for tests). */
 int plspm_bootstrap_indices(uint64_t seed, int64_t rep, int64_t N, int32_t* idx);
 
+/* The memberships the on-device splits of plspm_permutation_device use for permutation `perm` (host-side mirror, for tests): member [N]
+ * bytes, 1 = group a (the n1 rows with the smallest (key, row) pairs). */
+int plspm_permutation_members(uint64_t seed, int64_t perm, int64_t N, int64_t n1, uint8_t* member);
+
 /* Test seam, host arithmetic only (no device is touched): how the six-plane int8 Gram cuts `count_tiles` (16 replicates each) x
  * `pair_tiles` (32 pair columns each) into tile rows on `cus` CUs ("i8_rt" 0).  *tall rows of 20 count tiles and, with `mix` != 0, *shrt
  * rows of 16 in one launch; returns 1 when that launch is taken, 0 when the 256-replicate kernel is no slower, PLSPM_E_ARG on bad sizes. */

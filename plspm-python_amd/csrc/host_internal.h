@@ -79,9 +79,17 @@ static inline long i8_pairs(const plspm_model* m) { const long C = m->Pg + 1; re
 bool nm_counts8_possible(const plspm_model* m);
 int choose_gram_path(const plspm_model* m, int64_t B);      // 1 fp64 MFMA on (row,count) lists, 2 int8 digit planes
 int prepare_zs_stats(plspm_model* m);
-int prepare_zs(plspm_model* m);
+int prepare_zs(plspm_model* m, int floor = 0);      // floor: at least this many digit planes (0: the handle's own choice)
 int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const int32_t* d_idx, double* out, bool dense, bool* fallback, const void** counts = nullptr,
                 int* counts_MT = nullptr, unsigned short* out16 = nullptr, bool* wrote16 = nullptr);
 bool nm_wave_route_planned(const plspm_model* m);     // plspm_nonmetric.hip: Scale.NUM / RAW batches as one solver launch + verification (run_nonmetric_wave)
 int run_nonmetric_wave(plspm_model* m, long nb, const SolverOut& so, const void* cd8, int cd8_MT);
 bool nm_wave_step_planned(const plspm_model* m);      // plspm_nonmetric.hip: the categorical iteration of this handle runs one wave per problem (kernels_nmw.h)
+
+// ---- plspm_permute.hip (two-group permutation test)
+// One call's splits: permutation rep_offset + p has problem 2p = group a (n1 rows), 2p + 1 = the other N - n1 rows; `d_member` [B][N] bytes 0/1
+// (explicit memberships, tests) or null (on-device splits from the Philox keys, kernels_permute.h).
+struct PermSpec { uint64_t seed; int64_t rep_offset; int64_t n1; const uint8_t* d_member; };
+// run_gram_i8 on a permutation call (m->perm set): the 0/1 counts of problems [prob0, prob0 + nb) (prob0, nb even) into `cd`, layout of
+// resample_i8_kernel (MT count tiles, KB k-blocks)
+int launch_perm_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);

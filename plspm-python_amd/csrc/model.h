@@ -27,6 +27,9 @@ hipError_t plspm_stream_acquire(hipStream_t* s);
 void plspm_stream_release(hipStream_t s);
 
 // Kernel timing (plspm_profile_*): event pairs are recycled through `pool`, so a profiled launch costs two hipEventRecord only.
+// Split spec of a two-group permutation call (plspm_permute.hip) while plspm_detail_bootstrap runs it.
+struct PermSpec;
+
 struct ProfSlot { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, pool; double total_ms = 0.0; int64_t launches = 0; };
 
 struct plspm_model {
@@ -123,9 +126,12 @@ struct plspm_model {
     size_t h_zstat_cap = 0;
     hipEvent_t ev_zstat = nullptr;
     int zs_S = 0, zs_KB = 0, zs_NT = 0, zs_npair = 0, zs_npg = 0;
+    int zs_floor = 0;           // the plane floor the current planes were cut under (prepare_zs: 0 = the handle's own choice, 7 = a permutation call)
     bool zs_ind = false;        // one plane per pair group, launched through the seven-plane main loop (gram_i8_kernel<.., IND>)
     double zs_ratio = 0.0;      // smallest sum|z| / max|z| over the pair columns (automatic plane count; 0: not evaluated)
     double* moments_out = nullptr; // plspm_bootstrap_moments: dense moment matrices go here and the solver is skipped
+    const PermSpec* perm = nullptr; // plspm_permutation_device: the batch's problems are the two groups of random splits (int8 route, no resampling)
+    Buf perm_thr, perm_member, perm_io;      // ... the splits' thresholds, explicit memberships, the exceedance counts' in / out block
     int last_gram_path = 0;       // 1 fp64 MFMA, 2 int8 digit planes: what the last bootstrap call used (plspm_model_get_info)
     int last_i8_dma = 0;          // 1 global_load_lds, 2 buffer_load ... lds: the LDS-DMA form of the last int8 Gram launch
     int last_i8_persist = 0;      // 1: ... as one persistent workgroup per CU (gram_i8pp_kernel)

@@ -36,4 +36,10 @@ __host__ __device__ __forceinline__ u32x4 resample_quad(uint64_t seed, uint64_t 
     return philox4x32_10(q, 0u, (uint32_t)rep, (uint32_t)(rep >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 __host__ __device__ __forceinline__ int32_t to_index(uint32_t u, uint32_t n) { return (int32_t)mulhi32(u, n); }
+// Sort key of row i (0 <= i < N) in permutation `perm` of the two-group test: word (i & 3) of Philox(counter = (i >> 2, 1, perm), key = seed).
+// Counter word 1 is 1 where the bootstrap's is 0, so the two streams never share a block.  Group a of the permutation = the n1 rows with the
+// smallest (key, row) pairs (kernels_permute.h, plspm_permutation_members).
+__host__ __device__ __forceinline__ u32x4 permute_quad(uint64_t seed, uint64_t perm, uint32_t q) {
+    return philox4x32_10(q, 1u, (uint32_t)perm, (uint32_t)(perm >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+}
 

@@ -54,7 +54,7 @@ int choose_gram_path(const plspm_model* m, int64_t B) {
 // anything bell-shaped reach several hundred.  Measured against 80-bit sums on the 10k x 60 benchmark data (tests/test_gpu_gram_i8.py,
 // error relative to sqrt(M_pp M_qq)): seven planes 1e-16 (correctly rounded), six planes 3e-15, the blocked fp64 MFMA accumulation
 // 1.6e-15 -- all nine orders below the 1e-6 the records are held to.
-static int choose_slices(plspm_model* m, const unsigned long long* h, long npair, int* S_out) {      // h: [max bits | fixed-point sums | OR of the scaled integers], on the host
+static int choose_slices(plspm_model* m, const unsigned long long* h, long npair, int* S_out, int floor) {      // h: [max bits | fixed-point sums | OR of the scaled integers], on the host
     double worst = 1e300;
     unsigned long long any = 0ull;
     for (long j = 0; j < npair; ++j) any |= h[2 * npair + j];
@@ -75,6 +75,7 @@ static int choose_slices(plspm_model* m, const unsigned long long* h, long npair
     //  argument as for six / seven with the dominant row taken out of the sum: sum - max >= 2^(56 - 8S) max.)
     int S = worst >= 257.0 ? 6 : (worst >= 2.0 ? 7 : 8);
     if (m->tune.i8_min_slices > S) S = m->tune.i8_min_slices;              // "i8_min_slices": the automatic choice, but never fewer (Plspm(precision="strict"): 7)
+    if (floor > S) S = floor;                                               // (prepare_zs's floor: the same rule for one kind of call)
     // planes that would be identically zero in the seven-plane decomposition carry nothing: dropping them changes no sum
     int zero_planes = 0;
     if (worst > 0.0) {
@@ -139,12 +140,20 @@ int prepare_zs_stats(plspm_model* m) {
     return 0;
 }
 
-int prepare_zs(plspm_model* m) {
-    if (m->zs_valid) return 0;
+// floor > 0: never fewer than `floor` planes, for the calls that ask for it (the two-group permutation test: 7, plspm_permute.hip) -- the automatic
+// rule above assumes multiplicities that add up to N, a group of n1 << N rows does not.  Planes of the current upload built under another floor
+// are cut again from the column statistics already at hand (no second pass over the data, no host wait): such calls and the bootstrap's own
+// automatic choice can alternate on one handle.
+int prepare_zs(plspm_model* m, int floor) {
+    if (m->zs_valid && m->zs_floor == floor) return 0;
+    if (m->zs_valid) {
+        if (m->zs_stats_S == m->tune.i8_slices) m->zs_stats_ready = true;      // (pair tables, column maxima and the pinned statistics of this upload are still in place)
+        m->zs_valid = false;
+    }
     int rc;
     if (m->zs_stats_ready && m->zs_stats_S != m->tune.i8_slices) m->zs_stats_ready = false;      // the option changed in between
     if ((rc = prepare_zs_stats(m))) return rc;
-    int S = m->tune.i8_slices;
+    int S = m->tune.i8_slices ? std::max(m->tune.i8_slices, floor) : 0;
     const long npair = i8_pairs(m);
     const int npg = (int)((npair + 31) / 32) * 2;             // pair groups of 16, padded to whole workgroup tiles (two groups)
     const int KB = i8_kblocks(m->N);
@@ -153,7 +162,7 @@ int prepare_zs(plspm_model* m) {
     ProfScope ps(m, PLSPM_K_PACK);
     if (S == 0) {
         HIPCHK(m, hipEventSynchronize(m->ev_zstat));          // (long done when a fit ran behind plspm_bootstrap_prepare)
-        if ((rc = choose_slices(m, (const unsigned long long*)m->h_zstat, npair, &S))) return rc;
+        if ((rc = choose_slices(m, (const unsigned long long*)m->h_zstat, npair, &S, floor))) return rc;
     }
     hipLaunchKernelGGL(zs_scale_kernel, dim3((unsigned)((npair + 255) / 256)), dim3(256), 0, m->stream, d_max, (int)npair, S, d_k, (double*)m->pair_scale.p);
     // one plane (0/1 data): the product runs through the seven-plane main loop with the planes of a wave standing for seven consecutive
@@ -168,7 +177,7 @@ int prepare_zs(plspm_model* m) {
 #undef ZSB
     HIPCHK(m, hipGetLastError());
     m->zs_S = S; m->zs_KB = KB; m->zs_NT = NT; m->zs_npair = (int)npair; m->zs_npg = npg_built; m->zs_ind = ind;
-    m->zs_valid = true; m->zs_stats_ready = false;
+    m->zs_valid = true; m->zs_stats_ready = false; m->zs_floor = floor;
     return 0;
 }
 
@@ -327,7 +336,7 @@ int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const i
     plspm_model::Buf& cd = slot ? m->cd1 : m->cd;
     const size_t cd_bytes = (size_t)MT * 16 * ((size_t)KB + I8_SLACK_KB) * 64;
     if (cd_bytes > cd.cap) { if (m->aux) HIPCHK(m, hipStreamSynchronize(m->aux)); if ((rc = ensure(m, cd, cd_bytes))) return rc; m->cdfree_set[slot] = false; }
-    if (!d_idx && m->aux) {
+    if (!d_idx && !m->perm && m->aux) {
         // Philox draws: on the low-priority stream, as soon as the Gram that last read this buffer is done -- i.e. beside the Gram and the
         // solver of the PREVIOUS call when the host runs ahead; this call's Gram waits for the counts by event
         if (m->cdfree_set[slot]) HIPCHK(m, hipStreamWaitEvent(m->aux, m->ev_cdfree[slot], 0));
@@ -343,6 +352,8 @@ int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const i
         // explicit index lists (test / parity seam) arrive on the main stream: drawn there, and the host looks at the flag
         if (m->aux && m->cdfree_set[slot]) HIPCHK(m, hipStreamWaitEvent(m->stream, m->ev_cdfree[slot], 0));
         ProfScope ps(m, PLSPM_K_RESAMPLE);
+        if (m->perm) { if ((rc = launch_perm_counts(m, nb, rep0, MT, KB, cd.p))) return rc; }      // (two-group permutation test: 0/1 counts of random splits, plspm_permute.hip)
+        else
         if (hist_nib) hipLaunchKernelGGL(resample_i8_nib_kernel, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->stream, (int)m->N, KB, MT, seed, rep0, (uint4*)cd.p, (int*)m->err.p, nib_slow);
         else
         hipLaunchKernelGGL(resample_k, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->stream, (int)m->N, KB, MT, m->tune.i8_shape, d_idx, seed, rep0, (uint4*)cd.p, (int*)m->err.p);

@@ -26,7 +26,8 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_group_shard", "plspm_group_bootstrap", "plspm_group_sync", "plspm_group_records", "plspm_group_summary", "plspm_group_rows", "plspm_group_adopt", "plspm_bootstrap_prepare",
            "plspm_group_barrier", "plspm_group_max", "plspm_group_enqueue_times", "plspm_release_cached_memory",
            "plspm_op_inner_weights", "plspm_op_outer_weights", "plspm_op_outer_weights_nonmetric", "plspm_gram_tile_plan",
-           "plspm_comm_create_ex", "plspm_comm_split", "plspm_comm_transport", "plspm_comm_max_channels", "plspm_group_set_option", "plspm_group_plan", "plspm_chunk_plan"]
+           "plspm_comm_create_ex", "plspm_comm_split", "plspm_comm_transport", "plspm_comm_max_channels", "plspm_group_set_option", "plspm_group_plan", "plspm_chunk_plan",
+           "plspm_permutation_device", "plspm_permutation_counts", "plspm_permutation_members"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -99,6 +100,9 @@ def load():
     lib.plspm_stream.restype = vp
     lib.plspm_stream.argtypes = [vp]
     lib.plspm_bootstrap_indices.argtypes = [u64, i64, i64, vp]
+    lib.plspm_permutation_members.argtypes = [u64, i64, i64, i64, vp]
+    lib.plspm_permutation_device.argtypes = [vp, i64, u64, i64, i64, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.plspm_permutation_counts.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_profile_enable.argtypes = [vp, i32]
     lib.plspm_profile_read.argtypes = [vp, i32, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
     lib.plspm_profile_reset.argtypes = [vp]
@@ -172,6 +176,15 @@ def bootstrap_indices(seed, rep, n):
     if rc:
         raise NativeBackendError("plspm_bootstrap_indices failed (%d)" % rc)
     return idx
+
+
+def permutation_members(seed, perm, n, n1):
+    """Host mirror of the on-device splits of the two-group permutation test: [n] bools, True = group a of permutation ``perm``."""
+    member = np.empty(n, dtype=np.uint8)
+    rc = load().plspm_permutation_members(seed, perm, n, n1, _ptr(member))
+    if rc:
+        raise NativeBackendError("plspm_permutation_members failed (%d)" % rc)
+    return member.astype(bool)
 
 
 def i8_tile_plan(count_tiles, pair_tiles, cus=256, mix=True):
@@ -349,6 +362,31 @@ class NativeModel:
                     "plspm_bootstrap_device")
         self.last_B = B
         return d_out.value, d_st.value, d_it.value
+
+    def permutation(self, B, n1, seed=0, rep_offset=0, member=None):
+        """Enqueue B permutations of the two-group test (plspm_permutation_device): 2B records stay on the handle, record 2p = group a
+        (n1 rows) of permutation rep_offset + p, 2p + 1 = its group b.  ``member`` [B, N] bools: explicit memberships instead of the
+        on-device splits (tests)."""
+        if member is not None:
+            member = np.ascontiguousarray(member, dtype=np.uint8)
+            if member.shape != (B, self.N):
+                raise ValueError("member must have shape (B, N)")
+        d_out, d_st, d_it = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.plspm_permutation_device(self._h, B, seed, rep_offset, n1, _ptr(member), ctypes.byref(d_out), ctypes.byref(d_st),
+                                                       ctypes.byref(d_it)), "plspm_permutation_device")
+        self.last_B = 2 * B
+        return d_out.value, d_st.value, d_it.value
+
+    def permutation_counts(self, B, observed_diff):
+        """Exceedance counts of the last ``permutation`` call (plspm_permutation_counts): ([R] int64 #{valid p : |d_p| >= |observed_diff|},
+        number of valid permutations)."""
+        observed_diff = np.ascontiguousarray(observed_diff, dtype=np.float64)
+        if observed_diff.shape != (self.row_width,):
+            raise ValueError("observed_diff must have row_width entries")
+        exceed = np.empty(self.row_width, dtype=np.int64)
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_permutation_counts(self._h, B, _ptr(observed_diff), _ptr(exceed), ctypes.byref(used)), "plspm_permutation_counts")
+        return exceed, used.value
 
     def summary(self, B, original, d_rows=None, stride=0):
         """Device-side _create_summary of the last bootstrap on this handle (or of the device records at ``d_rows``).
