@@ -29,6 +29,7 @@
 #include "solver_wave.h"
 #include "solver_quad.h"
 #include "solver_wave16.h"
+#include "solver_route.h"
 
 using namespace plspm;
 
@@ -36,6 +37,21 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 __host__ __device__ __forceinline__ long lmin(long a, long b) { return a < b ? a : b; }
 
 #include "model.h"
+
+inline RouteShape route_shape(const plspm_model* m) { return {m->P, m->L, m->kmax, m->n_chol, m->n_eff, (int)m->pred_idx.size(), m->boff.data()}; }
+// Dynamic LDS beyond the 64 KiB default needs an explicit opt-in per kernel.
+inline int allow_lds(plspm_model* m, const void* fn, size_t bytes) {
+    if (bytes > kMaxLds) return fail(m, PLSPM_E_LIMIT, "kernel needs more than 160 KiB of LDS");
+    if (bytes > 48 * 1024) {
+        // (a kernel with static LDS of its own can be refused below 160 KiB of dynamic LDS: the same limit, the same code -- found by the many-LV fuzz, a 34-LV / 179-MV model)
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(m, PLSPM_E_LIMIT, "kernel needs " + std::to_string(bytes) + " bytes of dynamic LDS beside its static share: more than the device grants (" + hipGetErrorString(e) + ")");
+        }
+    }
+    return 0;
+}
 
 // where a solver launch writes: per-problem strides; null base pointers are skipped
 struct SolverOut {
@@ -53,15 +69,14 @@ static constexpr size_t kPinHalf = (size_t)8 << 20;       // two halves of the h
 int pin_ready(plspm_model* m);
 
 // ---- plspm_fit.hip
-size_t desc_lds_bytes(int P, int L, int ne, int nedge);
 // moment matrix of ALL uploaded rows -> m->gram (dense fp64 MFMA Gram over row chunks + fixed-order reduce)
 int dense_moments(plspm_model* m);
 // fp64 MFMA Gram of `nproblems` replicates over their (row,count) lists -> tile-packed matrices at `out`
 int launch_gram_lists(plspm_model* m, long nproblems, const int2* ent, const int* nent, long ent_stride, double* out);
 int run_impute(plspm_model* m, long nproblems, const double* Min, const double** Mp, long* mp_stride);
 int launch_solver(plspm_model* m, long nproblems, const double* Mp, long mp_stride, const SolverOut& so, int threads);
-// the metric solver of a bootstrap batch: wave / rows solver on dense matrices (`dense`: the int8 Gram wrote that layout) or the LDS solver
-int launch_batch_solver(plspm_model* m, long nb, bool dense, const SolverOut& so);
+// the metric solver of a bootstrap batch: `route` as metric_batch_route chose it when the int8 Gram wrote dense matrices, else ROUTE_LDS
+int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const SolverOut& so);
 // Scale.NUM / RAW non-metric bootstrap batches as ONE solver launch (round 6; solver_wave16.h NM): does this model have such a kernel, and the launch itself
 // (dense moment matrices at m->gram; maps / steps as kernels_solver.h solver_nmwave_kernel takes them; force + live: the replay of `nb` listed replicates)
 bool nm_wave_solver_covers(const plspm_model* m);

@@ -140,7 +140,7 @@ struct plspm_model {
     bool mix_valid = false, mix_wide = false; long mix_key[4] = {0, 0, 0, 0}; int mix_tall = 0, mix_short = 0;      // plspm_gram_i8.hip i8_mix_plan: the last tile-row cut
     int last_i8_mt = 0;           // count tiles (padded) of the last int8 Gram launch: 16 x this many replicate slots went through the matrix pipe
     int last_i8_short = 0;        // ... and, with 20, how many of its tile rows were short ones (16 count tiles: plspm_gram_i8.hip i8_mix_plan)
-    int last_solver = 0;          // 1 LDS solver (solver_kernel), 2 rows solver (solver_rows_kernel), 3 wave solver (solver_wave_kernel), 4 split rows solver (solver_rows_split_kernel), 5 quad solver (solver_quad_kernel), 6 wave solver for 9 .. 16 LVs (solver_wave16_kernel<16>), 7 its LMAX = 8 form (solver_wave16_kernel<8>: models of at most 8 LVs since round 5), 8 its LMAX = 32 form (17 .. 32 LVs, all Mode A): the last metric bootstrap's
+    int last_solver = 0;          // the SolverRoute (solver_route.h) of the last metric or Scale.NUM / RAW bootstrap batch
     // grow-only pinned host staging for uploads / row downloads (two halves: copy-in of chunk k+1 overlaps the DMA of chunk k)
     void* h_pin = nullptr;
     size_t h_pin_cap = 0;
@@ -215,21 +215,6 @@ inline int ensure(plspm_model* m, plspm_model::Buf& b, size_t bytes) {
     b.p = nullptr; b.cap = 0;
     HIPCHK(m, plspm_dmalloc(&b.p, bytes));
     b.cap = bytes;
-    return 0;
-}
-
-static constexpr size_t kMaxLds = 160 * 1024;
-// Dynamic LDS beyond the 64 KiB default needs an explicit opt-in per kernel.
-inline int allow_lds(plspm_model* m, const void* fn, size_t bytes) {
-    if (bytes > kMaxLds) return fail(m, PLSPM_E_LIMIT, "kernel needs more than 160 KiB of LDS");
-    if (bytes > 48 * 1024) {
-        // (a kernel with static LDS of its own can be refused below 160 KiB of dynamic LDS: the same limit, the same code -- found by the many-LV fuzz, a 34-LV / 179-MV model)
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(m, PLSPM_E_LIMIT, "kernel needs " + std::to_string(bytes) + " bytes of dynamic LDS beside its static share: more than the device grants (" + hipGetErrorString(e) + ")");
-        }
-    }
     return 0;
 }
 

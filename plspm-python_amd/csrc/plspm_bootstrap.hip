@@ -37,16 +37,9 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     const long dcnt_stride = ((N + 15) & ~15L);
     const int gpath = gpath_plan;
     m->last_gram_path = gpath;
-    // one wave per problem on dense moment matrices (solver_rows_kernel): metric models of at most 64 MVs behind the int8 Gram
-    // rows solver: one wave per problem, its small workspace + descriptors in LDS -- eight problems per CU at the headline size
-    // (at least four problems per CU; wide inner models, L >~ 20, take the LDS solver, which can move its workspace to global scratch)
-    const size_t rows_lds = desc_lds_bytes(m->P, m->L, m->n_eff, (int)m->pred_idx.size()) + (size_t)workspace_small_doubles(m->P, m->L, m->kmax, m->n_chol) * sizeof(double);
-    // (round 4: 64 < P <= 128 in the split form -- two threads per MV on either side of a block boundary, four waves and ~30 KB of LDS per problem)
-    // (round 5: the quad solver -- solver_quad.h, Mode-A models of 65 .. 128 MVs and at most 16 LVs -- has a workspace of its own, ~52 KB whatever the inner model)
-    const bool quad_width = m->tune.solver_quad != 0 && quad_solver_covers<16>(m->P, m->L, m->n_chol, m->kmax, m->boff.data());
-    const bool w16_width = m->tune.solver_wave != 0 && (wave16_solver_covers<16>(m->P, m->L, m->n_chol, m->kmax) || (m->n_chol == 0 && wave16_solver_covers<32>(m->P, m->L, 0, m->kmax)));      // (solver_wave16.h: 9 .. 16 LVs, its own ~16 KB workspace)
-    const bool rows_width = m->P <= 64 ? (rows_lds <= kMaxLds / 4 || w16_width) : (quad_width || (m->P <= 128 && rows_split_block(m->boff.data(), m->L, 64) > 0 && rows_lds + 4 * 16 * 66 * sizeof(double) <= kMaxLds / 2));
-    const bool rows_solver = gpath == 2 && m->tune.solver_rows != 0 && rows_width && !m->n_ind && !m->nonmetric && !m->moments_out;
+    // metric models on the int8 Gram: a solver on dense moment matrices (solver_route.h) unless the model is outside every dense solver's class
+    const SolverRoute route = metric_batch_route(route_shape(m), m->tune.solver_wave, m->tune.solver_quad, m->tune.solver_rows);
+    const bool rows_solver = gpath == 2 && route != ROUTE_LDS && !m->n_ind && !m->nonmetric && !m->moments_out;
     // round 6: Scale.NUM / RAW batches on the int8 route as one solver launch on dense moment matrices + a verification pass (plspm_nonmetric.hip
     // run_nonmetric_wave) -- needs the int8 counts the Gram consumed (explicit index lists of at most 65,535 rows keep the per-iteration launches and their
     // uint16 histograms; so does a chunk whose explicit indices made the int8 Gram fall back to the fp64 one)
@@ -169,7 +162,7 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
                                     nm_threads, true, cd8, cd8_MT, wrote16))) return rc;
             continue;
         }
-        if ((rc = launch_batch_solver(m, nb, rows_solver && !f64_gram, so))) return rc;
+        if ((rc = launch_batch_solver(m, nb, (rows_solver && !f64_gram) ? route : ROUTE_LDS, so))) return rc;
     }
     HIPCHK(m, hipGetLastError());
     if (rows_out == (double*)m->rows.p) m->rows_B = B;

@@ -59,11 +59,6 @@ static int launch_gram(plspm_model* m, long nproblems, int nchunks, const int2* 
     return 0;
 }
 
-size_t desc_lds_bytes(int P, int L, int ne, int nedge) {
-    const size_t T = ((size_t)P + 1 + 31) / 32 * 2, ntile = T * (T + 1) / 2;
-    return (size_t)P * 8 + (3 * (size_t)(L + 1) + P + 2 * (size_t)L + 2 * (size_t)ne + 2 * (size_t)nedge + (ntile + 1) / 2 + 4) * 4 + (((size_t)L * L + 15) & ~(size_t)15) + 16;
-}
-
 // Missing-data models: collapse the aug Gram(s) at `Min` into mean-imputed P-column moments; returns the matrix the solver reads.
 int run_impute(plspm_model* m, long nproblems, const double* Min, const double** Mp, long* mp_stride) {
     *Mp = Min; *mp_stride = packed_size(m->T);
@@ -153,126 +148,86 @@ int run_hoc_moments(plspm_model* m, plspm_model* m2, long nb) {
 }
 
 bool nm_wave_solver_covers(const plspm_model* m) {
-    if (!m->nonmetric || m->categorical || m->n_ind || m->nmx_K > 0 || m->stage1 || m->stage2 || m->P > 64) return false;
-    if (m->L <= 8) return m->P >= 1 && (wave16_ws_doubles<8>(m->L, m->kmax, m->n_chol) + 64) * sizeof(double) <= 20 * 1024 && m->n_chol / 2 <= 16 * 66;
-    if (m->L <= 16) return wave16_solver_covers<16>(m->P, m->L, m->n_chol, m->kmax);
-    return m->n_chol == 0 && wave16_solver_covers<32>(m->P, m->L, 0, m->kmax);      // 17 .. 32 LVs: all Mode A, as the metric <32> form
+    if (!m->nonmetric || m->categorical || m->n_ind || m->nmx_K > 0 || m->stage1 || m->stage2) return false;
+    return nm_wave_route(route_shape(m)) != ROUTE_NONE;
 }
 
-int launch_nm_wave_solver(plspm_model* m, long nb, const SolverOut& so, double* maps, long maps_stride, int* steps, const int* force, const int* live) {
-    int rc;
-    const double* gram_buf = (const double*)m->gram.p;
-    ProfScope ps(m, PLSPM_K_SOLVER);
-    if (m->L <= 8) {
-        const size_t lds = (size_t)(wave16_ws_doubles<8>(m->L, m->kmax, m->n_chol) + 64) * sizeof(double);
-        auto k = m->n_chol > 0 ? solver_nmwave_kernel<8, true> : solver_nmwave_kernel<8, false>;
-        if ((rc = allow_lds(m, (const void*)k, lds))) return rc;
-        hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(64), lds, m->stream, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so, maps, maps_stride, steps, force, live, std::ldexp(1.0, m->tune.nm_bound_shift));
-        m->last_solver = 9;
-    } else if (m->L <= 16) {
-        const size_t lds = (size_t)(wave16_ws_doubles<16>(m->L, m->kmax, m->n_chol) + 64) * sizeof(double);
-        auto k = m->n_chol > 0 ? solver_nmwave_kernel<16, true> : solver_nmwave_kernel<16, false>;
-        if ((rc = allow_lds(m, (const void*)k, lds))) return rc;
-        hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(64), lds, m->stream, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so, maps, maps_stride, steps, force, live, std::ldexp(1.0, m->tune.nm_bound_shift));
-        m->last_solver = 10;
-    } else {
-        const size_t lds = (size_t)(wave16_ws_doubles<32>(m->L, m->kmax, 0) + 64) * sizeof(double);
-        auto k = solver_nmwave_kernel<32, false>;
-        if ((rc = allow_lds(m, (const void*)k, lds))) return rc;
-        hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(64), lds, m->stream, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so, maps, maps_stride, steps, force, live, std::ldexp(1.0, m->tune.nm_bound_shift));
-        m->last_solver = 11;
-    }
+template <int LMAX>
+static int launch_nm_wave(plspm_model* m, long nb, const SolverOut& so, double* maps, long maps_stride, int* steps, const int* force, const int* live) {
+    const size_t lds = (size_t)(wave16_ws_doubles<LMAX>(m->L, m->kmax, m->n_chol) + 64) * sizeof(double);
+    auto k = (LMAX < 32 && m->n_chol > 0) ? solver_nmwave_kernel<LMAX, LMAX < 32> : solver_nmwave_kernel<LMAX, false>;      // (17 .. 32 LVs: all Mode A)
+    if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(64), lds, m->stream, make_desc(m), (const double*)m->gram.p, (long)cov_doubles(m->Pg), so, maps, maps_stride, steps, force, live, std::ldexp(1.0, m->tune.nm_bound_shift));
     return 0;
 }
 
-int launch_batch_solver(plspm_model* m, long nb, bool dense, const SolverOut& so_in) {
+int launch_nm_wave_solver(plspm_model* m, long nb, const SolverOut& so, double* maps, long maps_stride, int* steps, const int* force, const int* live) {
+    const SolverRoute route = nm_wave_route(route_shape(m));      // (callers asked nm_wave_solver_covers)
+    ProfScope ps(m, PLSPM_K_SOLVER);
+    const int rc = route == ROUTE_NM_WAVE_8 ? launch_nm_wave<8>(m, nb, so, maps, maps_stride, steps, force, live)
+                 : route == ROUTE_NM_WAVE_16 ? launch_nm_wave<16>(m, nb, so, maps, maps_stride, steps, force, live)
+                 : route == ROUTE_NM_WAVE_32 ? launch_nm_wave<32>(m, nb, so, maps, maps_stride, steps, force, live) : fail(m, PLSPM_E_STATE, "no wave solver covers this model");
+    if (!rc) m->last_solver = route;
+    return rc;
+}
+
+// A dense solver launch that signals the caller's event (plspm_group.cpp: the `computed` event its collective waits for, parked in m->stop_event; a separate
+// hipEventRecord is one more packet the queue drains the device for, ~5 us of every step).  The rows / LDS solvers leave the event to their caller.
+template <class K>
+static int launch_signalling(plspm_model* m, K kernel, long nb, int threads, size_t lds, const SolverOut& so) {
+    if (int rc = allow_lds(m, (const void*)kernel, lds)) return rc;
+    ProfScope ps(m, PLSPM_K_SOLVER);
+    hipEvent_t stop = m->stop_event;
+    m->stop_event = nullptr;
+    hipExtLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(threads), lds, m->stream, nullptr, stop, 0, make_desc(m), (const double*)m->gram.p, (long)cov_doubles(m->Pg), so);
+    return 0;
+}
+
+int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const SolverOut& so_in) {
     SolverOut so = so_in;
-    int rc;
+    int rc = 0;
     const double* gram_buf = (const double*)m->gram.p;
+    const bool modeb = m->n_chol > 0;
 #ifdef PLSPM_DEBUG_MARKS      // phase clocks of one solver problem (make marks); never in the release library
     long long* d_marks = nullptr;
     HIPCHK(m, plspm_dmalloc((void**)&d_marks, 32 * sizeof(long long))); so.marks = d_marks;
 #endif
-    if (dense && (m->tune.solver_wave == 1 || m->tune.solver_wave == 2) && m->L <= 8 && wave_solver_covers<8>(m->P, m->L, m->n_chol) &&
-        wave16_ws_doubles<8>(m->L, m->kmax, m->n_chol) * sizeof(double) <= 20 * 1024) {
-        // round 5 (second half): models of at most 8 LVs -- the headline's class -- in the arrangement of solver_wave16.h at LMAX = 8: V in LDS, the product
-        // stream's second copy w V for the Q sums, a folded into E (0.095 -> 0.084 ms per 5,000 replicates; set_option("solver_wave", 3): the round-3 kernel);
-        // Mode-B blocks: the round-4 block inverses on this workspace, a second instantiation
-        const size_t lds = (size_t)wave16_ws_doubles<8>(m->L, m->kmax, m->n_chol) * sizeof(double);
-        auto k8 = m->n_chol > 0 ? solver_wave16_kernel<8, true> : solver_wave16_kernel<8, false>;
-        if ((rc = allow_lds(m, (const void*)k8, lds))) return rc;
-        ProfScope ps(m, PLSPM_K_SOLVER);
-        hipEvent_t stop = m->stop_event;
-        m->stop_event = nullptr;
-        hipExtLaunchKernelGGL(k8, dim3((unsigned)nb), dim3(64), lds, m->stream, nullptr, stop, 0, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so);
-        m->last_solver = 7;
-    } else if (dense && m->tune.solver_wave != 0 && wave_solver_covers<8>(m->P, m->L, m->n_chol)) {
-        // one wave per problem with fixed lane roles (solver_wave.h): at most 64 MVs and 8 LVs; Mode-B blocks keep their inverses behind the workspace
-        const size_t lds = (size_t)wave_ws_doubles<8>(m->n_chol) * sizeof(double);
-        ProfScope ps(m, PLSPM_K_SOLVER);
-        // (a caller that wants an event behind this batch -- plspm_group.cpp: the `computed` event its collective waits for -- hands it over as the
-        //  launch's own completion signal: a separate hipEventRecord is one more packet the queue drains the device for, ~5 us of every step)
-        hipEvent_t stop = m->stop_event;
-        m->stop_event = nullptr;
-        if (m->n_chol > 0) hipExtLaunchKernelGGL((solver_wave_kernel<8, true>), dim3((unsigned)nb), dim3(64), lds, m->stream, nullptr, stop, 0, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so);
-        else hipExtLaunchKernelGGL((solver_wave_kernel<8, false>), dim3((unsigned)nb), dim3(64), lds, m->stream, nullptr, stop, 0, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so);
-        m->last_solver = 3;
-    } else if (dense && m->tune.solver_wave != 0 && wave16_solver_covers<16>(m->P, m->L, m->n_chol, m->kmax)) {
-        // the same for 9 .. 16 LVs (solver_wave16.h; round 5): four matrix entries per pair lane, V in LDS
-        const size_t lds = (size_t)wave16_ws_doubles<16>(m->L, m->kmax, m->n_chol) * sizeof(double);
-        auto k16 = m->n_chol > 0 ? solver_wave16_kernel<16, true> : solver_wave16_kernel<16, false>;
-        if ((rc = allow_lds(m, (const void*)k16, lds))) return rc;
-        ProfScope ps(m, PLSPM_K_SOLVER);
-        hipEvent_t stop = m->stop_event;
-        m->stop_event = nullptr;
-        hipExtLaunchKernelGGL(k16, dim3((unsigned)nb), dim3(64), lds, m->stream, nullptr, stop, 0, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so);
-        m->last_solver = 6;
-    } else if (dense && m->tune.solver_wave != 0 && m->n_chol == 0 && wave16_solver_covers<32>(m->P, m->L, m->n_chol, m->kmax)) {
-        // ... and for 17 .. 32 LVs: sixteen matrix entries per pair lane, three problems per CU (all Mode A)
-        const size_t lds = (size_t)wave16_ws_doubles<32>(m->L, m->kmax, 0) * sizeof(double);
-        if ((rc = allow_lds(m, (const void*)solver_wave16_kernel<32, false>, lds))) return rc;
-        ProfScope ps(m, PLSPM_K_SOLVER);
-        hipEvent_t stop = m->stop_event;
-        m->stop_event = nullptr;
-        hipExtLaunchKernelGGL((solver_wave16_kernel<32, false>), dim3((unsigned)nb), dim3(64), lds, m->stream, nullptr, stop, 0, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so);
-        m->last_solver = 8;
-    } else if (dense) {
-        const size_t lds = desc_lds_bytes(m->P, m->L, m->n_eff, (int)m->pred_idx.size()) + (size_t)workspace_small_doubles(m->P, m->L, m->kmax, m->n_chol) * sizeof(double);
-        if (m->P > 64 && m->tune.solver_quad != 0 && quad_solver_covers<16>(m->P, m->L, m->n_chol, m->kmax, m->boff.data())) {
-            // four waves per problem with fixed lane roles (solver_quad.h; round 5): Mode-A models of 65 .. 128 MVs and at most 16 LVs
-            m->last_solver = 5;
-            const size_t ldsq = (size_t)quad_ws_doubles<16>(m->L, m->kmax) * sizeof(double);
-            if ((rc = allow_lds(m, (const void*)solver_quad_kernel<16>, ldsq))) return rc;
+    switch (route) {
+        case ROUTE_WAVE16_8:      // (round 5: V in LDS, the product stream's second copy w V for the Q sums, a folded into E; Mode-B blocks: a second instantiation)
+            rc = launch_signalling(m, modeb ? solver_wave16_kernel<8, true> : solver_wave16_kernel<8, false>, nb, 64, (size_t)wave16_ws_doubles<8>(m->L, m->kmax, m->n_chol) * sizeof(double), so); break;
+        case ROUTE_WAVE:          // (fixed lane roles, solver_wave.h; Mode-B blocks keep their inverses behind the workspace)
+            rc = launch_signalling(m, modeb ? solver_wave_kernel<8, true> : solver_wave_kernel<8, false>, nb, 64, (size_t)wave_ws_doubles<8>(m->n_chol) * sizeof(double), so); break;
+        case ROUTE_WAVE16_16:     // (four matrix entries per pair lane)
+            rc = launch_signalling(m, modeb ? solver_wave16_kernel<16, true> : solver_wave16_kernel<16, false>, nb, 64, (size_t)wave16_ws_doubles<16>(m->L, m->kmax, m->n_chol) * sizeof(double), so); break;
+        case ROUTE_WAVE16_32:     // (sixteen matrix entries per pair lane, three problems per CU)
+            rc = launch_signalling(m, solver_wave16_kernel<32, false>, nb, 64, (size_t)wave16_ws_doubles<32>(m->L, m->kmax, 0) * sizeof(double), so); break;
+        case ROUTE_QUAD:
+            rc = launch_signalling(m, solver_quad_kernel<16>, nb, 256, (size_t)quad_ws_doubles<16>(m->L, m->kmax) * sizeof(double), so); break;
+        case ROUTE_ROWS_SPLIT:    // (two threads per MV on either side of a block boundary, rows_split_block)
+        case ROUTE_ROWS: {
+            const bool split = route == ROUTE_ROWS_SPLIT;
+            const size_t lds = desc_lds_bytes(m->P, m->L, m->n_eff, (int)m->pred_idx.size()) + (workspace_small_doubles(m->P, m->L, m->kmax, m->n_chol) + (split ? PLSPM_ROWS_SPLIT_STAGE_DOUBLES : 0)) * sizeof(double);
+            auto k = split ? solver_rows_split_kernel : solver_rows_kernel;
+            if ((rc = allow_lds(m, (const void*)k, lds))) return rc;
             ProfScope ps(m, PLSPM_K_SOLVER);
-            hipEvent_t stop = m->stop_event;
-            m->stop_event = nullptr;
-            hipExtLaunchKernelGGL((solver_quad_kernel<16>), dim3((unsigned)nb), dim3(256), ldsq, m->stream, nullptr, stop, 0, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so);
-        } else if (m->P > 64) {                    // split form: two threads per MV (plspm_detail_bootstrap asked rows_split_block)
-            m->last_solver = 4;
-            const size_t lds4 = lds + PLSPM_ROWS_SPLIT_STAGE_DOUBLES * sizeof(double);
-            if ((rc = allow_lds(m, (const void*)solver_rows_split_kernel, lds4))) return rc;
+            hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(split ? 256 : 64), lds, m->stream, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so);
+        } break;
+        default: {                // ROUTE_LDS
+            const double* Mp; long mp_stride;
+            if ((rc = run_impute(m, nb, gram_buf, &Mp, &mp_stride))) return rc;
             ProfScope ps(m, PLSPM_K_SOLVER);
-            hipLaunchKernelGGL(solver_rows_split_kernel, dim3((unsigned)nb), dim3(256), lds4, m->stream, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so);
-        } else {
-            m->last_solver = 2;
-            if ((rc = allow_lds(m, (const void*)solver_rows_kernel, lds))) return rc;
-            ProfScope ps(m, PLSPM_K_SOLVER);
-            hipLaunchKernelGGL(solver_rows_kernel, dim3((unsigned)nb), dim3(64), lds, m->stream, make_desc(m), gram_buf, (long)cov_doubles(m->Pg), so);
-        }
-    } else {
-        const double* Mp; long mp_stride;
-        if ((rc = run_impute(m, nb, gram_buf, &Mp, &mp_stride))) return rc;
-        ProfScope ps(m, PLSPM_K_SOLVER);
-        m->last_solver = 1;
-        if ((rc = launch_solver(m, nb, Mp, mp_stride, so, m->tune.solver_threads))) return rc;
+            rc = launch_solver(m, nb, Mp, mp_stride, so, m->tune.solver_threads);
+        } break;
     }
+    if (rc) return rc;
+    m->last_solver = route;
     HIPCHK(m, hipGetLastError());
 #ifdef PLSPM_DEBUG_MARKS
     {
         long long h[32];
         HIPCHK(m, hipStreamSynchronize(m->stream));
         HIPCHK(m, hipMemcpy(h, d_marks, sizeof(h), hipMemcpyDeviceToHost));
-        if (m->last_solver == 3 || m->last_solver >= 5) {
+        if (route != ROUTE_LDS && route != ROUTE_ROWS && route != ROUTE_ROWS_SPLIT) {      // the wave / quad solvers' marks
             fprintf(stderr, "[plspm wave clocks] load %lld  treat %lld  init %lld  iterations %lld  finalize %lld  inner %lld  effects %lld  outputs %lld  total %lld\n",
                     h[1] - h[0], h[2] - h[1], h[3] - h[2], h[4] - h[3], h[5] - h[4], h[6] - h[5], h[7] - h[6], h[13] - h[7], h[13] - h[0]);
             fprintf(stderr, "[plspm wave last iterate] apply_cov %lld  a/G/E %lld  regress %lld  outer+conv %lld\n", h[9] - h[8], h[10] - h[9], h[11] - h[10], h[12] - h[11]);

@@ -16,6 +16,7 @@
 #include "../../plspm-python_amd/csrc/solver_wave.h"
 #include "../../plspm-python_amd/csrc/solver_quad.h"
 #include "../../plspm-python_amd/csrc/solver_wave16.h"
+#include "../../plspm-python_amd/csrc/solver_route.h"
 
 using namespace plspm;
 
@@ -584,6 +585,12 @@ int hostemu_nmx(int mode_op, int raw, int P, int L, int PA, int scheme, int max_
         else nmx_finish(ex, em.md, xd, ws, st, x, out);
     });
     return active;
+}
+
+// The solver route of a model shape (csrc/solver_route.h): nm_wave_route when nm != 0, else metric_batch_route under the three solver options.
+int hostemu_solver_route(int P, int L, int kmax, int n_chol, int n_eff, int nedge, const int* boff, int solver_wave, int solver_quad, int solver_rows, int nm) {
+    const RouteShape s{P, L, kmax, n_chol, n_eff, nedge, boff};
+    return nm ? nm_wave_route(s) : metric_batch_route(s, solver_wave, solver_quad, solver_rows);
 }
 
 long hostemu_packed_index(int T, int p, int q) { return packed_index(T, p, q); }
