@@ -380,6 +380,31 @@ int plspm_permutation_device(plspm_model_t* m, int64_t B, uint64_t seed, int64_t
 int plspm_permutation_counts(plspm_model_t* m, int64_t B, const double* observed_diff, int64_t* exceed, int64_t* n_used);
 
 /*
+ * ---- Two-group bootstrap (multi-group analysis) ---------------------------------------------------------------------------------
+ * Each group is bootstrapped on its own.  member [N] host bytes 0/1 (1 = group a) define the row lists rows_a, rows_b (ascending row order)
+ * of n_a, n_b >= 2 rows.  Resample r (global id) makes problem s = 2r: n_a draws, draw j = rows_a[to_index(word (j & 3) of
+ * Philox4x32-10(counter = (j >> 2, 2, lo32(s), hi32(s)), key = (lo32(seed), hi32(seed))), n_a)] (to_index(u, n) = (u * n) >> 32; counter word 1
+ * is 2 where the bootstrap's is 0 and the permutation's 1), and problem s = 2r + 1: n_b draws from rows_b, likewise.  Both problems are
+ * estimated like bootstrap replicates (each group's own n, treatment and `scaled` scalar from its moments) on the int8 Gram route with at least
+ * seven digit planes, whatever "gram_path" / "i8_min_batch" say; the floor belongs to this call (a later bootstrap keeps its own planes).
+ * Plain metric handles only: PLSPM_E_ARG otherwise; PLSPM_E_LIMIT where the int8 route is closed or a multiplicity exceeds 127.
+ *
+ * plspm_stratified_bootstrap_device: resamples [rep_offset, rep_offset + B), 1 <= B <= 2^29.  Enqueues 2B problems and waits for them: record 2p
+ *   = group a of resample rep_offset + p, 2p + 1 = its group b; they stay on the handle as its last records (plspm_bootstrap_fetch reads
+ *   them; plspm_bootstrap_summary on *d_out with stride 2 * row_stride summarises group a, on *d_out + row_stride group b).
+ *   draws  NULL: the Philox draws above;  else [B*N] host rows (test seam): row p holds resample p's draws, entries [0, n_a) rows of group a,
+ *          [n_a, N) rows of group b -- PLSPM_E_ARG when an entry is not a row of its group.
+ * plspm_stratified_pair_counts: on the handle's last 2B records (B of the last stratified call), per result column j
+ *   above[j] = #{(i, k) : u_a,i > u_b,k},  u_a = 2 center_a[j] - x over group a's records of status PLSPM_OK, u_b = 2 center_b[j] - x over
+ *   group b's (that fp64 expression; a NaN on either side never counts).  *used_a / *used_b: the OK records of each group (may be NULL).
+ *   center_a, center_b [R] host (the groups' bootstrap means for Henseler's PLS-MGA test), above [R] host.
+ */
+int plspm_stratified_bootstrap_device(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offset, const uint8_t* member, const int32_t* draws,
+                                      void** d_out, void** d_status, void** d_iters);
+int plspm_stratified_pair_counts(plspm_model_t* m, int64_t B, const double* center_a, const double* center_b, int64_t* above, int64_t* used_a,
+                                 int64_t* used_b);
+
+/*
  * ---- Multi-GPU: replicate shards + ONE RCCL all-gather --------------------------------------------------------------------------
  * Reference: Bootstrap.__init__ forks `processes` workers, each running iterations / processes replicates, and merges their
  * frames through a Queue (plspm/bootstrap.py:89-111; `processes` kwarg plspm/plspm.py:35-37,60-61).  Here a GROUP of handles --

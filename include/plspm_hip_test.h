@@ -39,6 +39,10 @@ int plspm_bootstrap_indices(uint64_t seed, int64_t rep, int64_t N, int32_t* idx)
  * bytes, 1 = group a (the n1 rows with the smallest (key, row) pairs). */
 int plspm_permutation_members(uint64_t seed, int64_t perm, int64_t N, int64_t n1, uint8_t* member);
 
+/* The draws plspm_stratified_bootstrap_device makes for resample `rep` (host-side mirror, for tests): rows [N], entries [0, n_a) the drawn rows
+ * of group a (member = 1), [n_a, N) those of group b -- the layout of its `draws`.  PLSPM_E_ARG when a group has fewer than two rows. */
+int plspm_stratified_draws(uint64_t seed, int64_t rep, int64_t N, const uint8_t* member, int32_t* rows);
+
 /* Test seam, host arithmetic only (no device is touched): how the six-plane int8 Gram cuts `count_tiles` (16 replicates each) x
  * `pair_tiles` (32 pair columns each) into tile rows on `cus` CUs ("i8_rt" 0).  *tall rows of 20 count tiles and, with `mix` != 0, *shrt
  * rows of 16 in one launch; returns 1 when that launch is taken, 0 when the 256-replicate kernel is no slower, PLSPM_E_ARG on bad sizes. */

@@ -108,3 +108,8 @@ struct PermSpec { uint64_t seed; int64_t rep_offset; int64_t n1; const uint8_t* 
 // run_gram_i8 on a permutation call (m->perm set): the 0/1 counts of problems [prob0, prob0 + nb) (prob0, nb even) into `cd`, layout of
 // resample_i8_kernel (MT count tiles, KB k-blocks)
 int launch_perm_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
+// One call's stratified resamples: resample rep_offset + p has problem 2p = n_a draws from group a's rows, 2p + 1 = n_b draws from group b's;
+// `d_rows` [N] = group a's rows then group b's, ascending; `d_draws` [B][N] explicit rows (tests) or null (Philox draws, kernels_strat.h).
+struct StratSpec { uint64_t seed; int64_t rep_offset; int64_t n_a; const int32_t* d_rows; const int32_t* d_draws; };
+// run_gram_i8 on a stratified call (m->strat set): the counts of problems [prob0, prob0 + nb) (prob0, nb even) into `cd`, same layout
+int launch_strat_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);

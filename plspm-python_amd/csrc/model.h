@@ -29,6 +29,8 @@ void plspm_stream_release(hipStream_t s);
 // Kernel timing (plspm_profile_*): event pairs are recycled through `pool`, so a profiled launch costs two hipEventRecord only.
 // Split spec of a two-group permutation call (plspm_permute.hip) while plspm_detail_bootstrap runs it.
 struct PermSpec;
+// Draw spec of a stratified bootstrap call of the two-group test (plspm_permute.hip) while plspm_detail_bootstrap runs it.
+struct StratSpec;
 
 struct ProfSlot { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, pool; double total_ms = 0.0; int64_t launches = 0; };
 
@@ -53,6 +55,7 @@ struct plspm_model {
     bool codes_valid = false;    // m->codes holds the category codes of the uploaded rows (nm_conv_codes_kernel)
     bool ind8_valid = false;     // m->ind8 holds their indicator bytes in MFMA fragment order (kernels_nmp.h)
     long last_nm_problems = 0;   // problems of the last run_nonmetric (plspm_nonmetric_criteria)
+    int last_strat_rows = 0;     // 1 / 2: the last stratified counts read the group's rows through L2 / from LDS (plspm_permute.hip)
     int last_i8_nibbles = 0;     // 1: the last int8 resample drew into 4-bit counters (data sets beyond one 16-bit window)
     int last_nm_direct16 = 0;    // 1: the last categorical bootstrap's count matrices were written by the int8 product itself (uint16, no scatter pass)
     int last_nm_mfma = 0;        // 1: the last non-metric bootstrap's stop-rule passes ran as int8 matrix products (kernels_nmp.h)
@@ -101,7 +104,7 @@ struct plspm_model {
     bool err_clean = false;       // the device error word is zero and no call since could have raised it (plspm_detail_bootstrap)
     // launch-geometry options (plspm_model_set_option); validated there, never read from the environment
     struct Tune { int wide_nw = 4, fit_chunks = 0, conv_pass = 0, conv_gy = 0, nm_threads = 0, solver_threads = 128, scores_tile = 0, gram_lds_kb = 0;
-                  int gram_path = 0, i8_slices = 0, i8_min_batch = 1, i8_waves = 8, i8_rt = 0, i8_short = -1, i8_cus = 0, upload_direct = 0, i8_dma = 0, i8_variant = -1, solver_rows = 1, solver_wave = 1, solver_quad = 1, nm_counts8 = 1, nm_fast_lds = 1, nm_k16 = 1, nm_codes = 1, i8_ind = 1, i8_shape = 16, resample_aux = 0, i8_sched = 0, i8_priv = 1, boot_chunks = 0, boot_ratio = 60, boot_align = 0, i8_persist = 0, i8_min_slices = 0, i8_nostore = 0, nm_wave = 1, nm_live = 1, nm_mfma = 1, nm_direct16 = 1, i8_nibbles = 1, nm_wave16 = 1, nm_verify_rows = 0, nm_bound_shift = 0, wide_ring = 4, nm_subset = 4, nm_cat_one = 1, nm_cpl = 0, nm_c10 = 1, nm_vlong = 1; } tune;
+                  int gram_path = 0, i8_slices = 0, i8_min_batch = 1, i8_waves = 8, i8_rt = 0, i8_short = -1, i8_cus = 0, upload_direct = 0, i8_dma = 0, i8_variant = -1, solver_rows = 1, solver_wave = 1, solver_quad = 1, nm_counts8 = 1, nm_fast_lds = 1, nm_k16 = 1, nm_codes = 1, i8_ind = 1, i8_shape = 16, resample_aux = 0, i8_sched = 0, i8_priv = 1, boot_chunks = 0, boot_ratio = 60, boot_align = 0, i8_persist = 0, i8_min_slices = 0, i8_nostore = 0, nm_wave = 1, nm_live = 1, nm_mfma = 1, nm_direct16 = 1, i8_nibbles = 1, nm_wave16 = 1, nm_verify_rows = 0, nm_bound_shift = 0, wide_ring = 4, nm_subset = 4, nm_cat_one = 1, nm_cpl = 0, nm_c10 = 1, nm_vlong = 1, strat_rows = 0; } tune;
     // int8 digit-plane Gram of bootstrap batches (kernels_gram_i8.h): per data set the digit planes `zs` of all pair products and the
     // pair tables (p, q, k, slot in the packed matrix | 2^-k); per call the dense int8 multiplicities `cd`
     Buf zs, cd, cd1, err2, pair_tab, pair_scale, zs_stat, codes, ind8, tab8, scl8, pp_ctl;      // pp_ctl: tile counters of the persistent Gram (kernels_gram_i8p.h GramI8PPCtl)
@@ -132,6 +135,9 @@ struct plspm_model {
     double* moments_out = nullptr; // plspm_bootstrap_moments: dense moment matrices go here and the solver is skipped
     const PermSpec* perm = nullptr; // plspm_permutation_device: the batch's problems are the two groups of random splits (int8 route, no resampling)
     Buf perm_thr, perm_member, perm_io;      // ... the splits' thresholds, explicit memberships, the exceedance counts' in / out block
+    const StratSpec* strat = nullptr;        // plspm_stratified_bootstrap_device: the batch's problems are resamples drawn inside each group (int8 route)
+    Buf strat_rows, strat_draws, strat_io, strat_u;      // ... both groups' row lists, explicit draws, the pair counts' in / out block and u values
+    std::vector<uint8_t> strat_member;       // ... the memberships strat_rows was built from (uploaded again only when they change)
     int last_gram_path = 0;       // 1 fp64 MFMA, 2 int8 digit planes: what the last bootstrap call used (plspm_model_get_info)
     int last_i8_dma = 0;          // 1 global_load_lds, 2 buffer_load ... lds: the LDS-DMA form of the last int8 Gram launch
     int last_i8_persist = 0;      // 1: ... as one persistent workgroup per CU (gram_i8pp_kernel)

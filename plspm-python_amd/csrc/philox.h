@@ -43,3 +43,9 @@ __host__ __device__ __forceinline__ u32x4 permute_quad(uint64_t seed, uint64_t p
     return philox4x32_10(q, 1u, (uint32_t)perm, (uint32_t)(perm >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
+// Draw word of problem `s` of the stratified (within-group) bootstrap of the two-group test: word (j & 3) of Philox(counter = (j >> 2, 2, s),
+// key = seed) for draw j.  Counter word 1 is 2 (bootstrap 0, permutation 1): the three streams never share a block.  Resample r makes problem
+// s = 2r (group a, n_a draws from its rows) and s = 2r + 1 (group b) -- kernels_strat.h, plspm_stratified_draws.
+__host__ __device__ __forceinline__ u32x4 strat_quad(uint64_t seed, uint64_t s, uint32_t q) {
+    return philox4x32_10(q, 2u, (uint32_t)s, (uint32_t)(s >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+}

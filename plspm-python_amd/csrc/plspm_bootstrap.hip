@@ -29,7 +29,7 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     // counts the Gram consumed -- no second resample kernel, no (row,count) lists, no uint16 histograms (set_option "nm_counts8" 0: the
     // round-2 path, kept for A/B and for the cases below)
     // (a two-group permutation call, plspm_permute.hip, always takes the int8 route: its caller checked that the route is open)
-    const int gpath_plan = m->perm ? 2 : choose_gram_path(m, B);
+    const int gpath_plan = (m->perm || m->strat) ? 2 : choose_gram_path(m, B);
     // (explicit index lists of at most 65,535 rows keep the round-3 arrangement -- uint16 histograms beside the lists they need anyway; beyond
     //  one window the int8 counts are the only dense multiplicities there are)
     const bool counts8_plan = gpath_plan == 2 && (!d_idx || !lds_hist) && nm_counts8_possible(m);
@@ -61,7 +61,7 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     if (gpath == 2 && chunk < B) chunk = std::max<int64_t>(256, chunk & ~(int64_t)255);      // whole 256-replicate tiles per pass
     int rc;
     if (gpath == 2) {
-        if ((rc = prepare_zs(m, m->perm ? 7 : 0))) return rc;      // (a permutation call: seven planes at least, plspm_permute.hip)
+        if ((rc = prepare_zs(m, (m->perm || m->strat) ? 7 : 0))) return rc;      // (a permutation / stratified call: seven planes at least, plspm_permute.hip)
     }
     if (need_lists) {
         if ((rc = ensure(m, m->ent, (size_t)chunk * ent_stride * sizeof(int2)))) return rc;
@@ -85,7 +85,7 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     // indices or runs the persistent Gram (data sets of fewer than 128 rows cannot exceed a multiplicity of 127; they are kept on the clearing
     // side because their launches take the short-N forms that share the word with the index check): a Philox call on the tiled launch neither raises nor needs to clear it (the 4-byte memset is a
     // kernel of its own on the stream: ~8 us with its gaps, 1.5 % of a 5,000-replicate step)
-    const bool may_raise = d_idx != nullptr || m->tune.i8_sched != 0 || N < 128;
+    const bool may_raise = d_idx != nullptr || m->strat != nullptr || m->tune.i8_sched != 0 || N < 128;
     if (!m->err_clean || may_raise) HIPCHK(m, hipMemsetAsync(m->err.p, 0, sizeof(int), m->stream));
     m->err_clean = !may_raise;
     double* const gram_buf = (double*)m->gram.p;

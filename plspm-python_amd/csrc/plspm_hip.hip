@@ -298,7 +298,7 @@ void plspm_model_destroy(plspm_model_t* m) {
                     m->ent.p, m->nent.p, m->gram.p, m->gram_partial.p, m->rows.p, m->status.p, m->iters.p, m->gS.p, m->gsmall.p,
                     m->fitout.p, m->idx.p, m->err.p, m->ghist.p, m->nmstate.p, m->nmpartial.p, m->nmactive.p, m->nmlist.p, m->gK16.p, m->sum_buf.p, m->cols.p,
                     m->nmw_maps.p, m->nmw_ints.p, m->nmw_vsum.p, m->zs.p, m->cd.p, m->cd1.p, m->codes.p, m->ind8.p, m->tab8.p, m->scl8.p, m->err2.p, m->pp_ctl.p, m->sk_partial.p, m->sk_flags.p, m->pair_tab.p, m->pair_scale.p, m->zs_stat.p,
-                    m->perm_thr.p, m->perm_member.p, m->perm_io.p};
+                    m->perm_thr.p, m->perm_member.p, m->perm_io.p, m->strat_rows.p, m->strat_draws.p, m->strat_io.p, m->strat_u.p};
     for (void* p : ptrs) if (p) plspm_dfree(p);
     for (void* p : m->blobs) if (p) plspm_dfree(p);
     if (m->h_stage) plspm_hfree(m->h_stage);
@@ -458,6 +458,7 @@ int plspm_model_set_option(plspm_model_t* m, const char* key, int32_t value) {
     else if (k == "nm_mfma") { if (value < 0 || value > 1) return bad(); m->tune.nm_mfma = value; }
     else if (k == "nm_direct16") { if (value < 0 || value > 1) return bad(); m->tune.nm_direct16 = value; }
     else if (k == "i8_nibbles") { if (value < 0 || value > 2) return bad(); m->tune.i8_nibbles = value; }
+    else if (k == "strat_rows") { if (value < 0 || value > 2) return bad(); m->tune.strat_rows = value; }
     else if (k == "nm_wave") { if (value < 0 || value > 1) return bad(); m->tune.nm_wave = value; }
     else if (k == "i8_ind") { if (value < 0 || value > 1) return bad(); if (value != m->tune.i8_ind) m->zs_valid = false; m->tune.i8_ind = value; }
     else if (k == "upload_direct") { if (value < 0 || value > 1) return bad(); m->tune.upload_direct = value; }
@@ -524,6 +525,8 @@ int plspm_model_get_option(const plspm_model_t* m, const char* key, int32_t* val
     else if (k == "nm_direct16") *value = m->tune.nm_direct16;
     else if (k == "last_nm_direct16") *value = m->last_nm_direct16;
     else if (k == "i8_nibbles") *value = m->tune.i8_nibbles;
+    else if (k == "strat_rows") *value = m->tune.strat_rows;
+    else if (k == "last_strat_rows") *value = m->last_strat_rows;
     else if (k == "last_i8_nibbles") *value = m->last_i8_nibbles;
     else if (k == "i8_ind") *value = m->tune.i8_ind;
     else if (k == "i8_rt") *value = m->tune.i8_rt;

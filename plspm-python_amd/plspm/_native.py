@@ -27,7 +27,8 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_group_barrier", "plspm_group_max", "plspm_group_enqueue_times", "plspm_release_cached_memory",
            "plspm_op_inner_weights", "plspm_op_outer_weights", "plspm_op_outer_weights_nonmetric", "plspm_gram_tile_plan",
            "plspm_comm_create_ex", "plspm_comm_split", "plspm_comm_transport", "plspm_comm_max_channels", "plspm_group_set_option", "plspm_group_plan", "plspm_chunk_plan",
-           "plspm_permutation_device", "plspm_permutation_counts", "plspm_permutation_members"]
+           "plspm_permutation_device", "plspm_permutation_counts", "plspm_permutation_members",
+           "plspm_stratified_bootstrap_device", "plspm_stratified_pair_counts", "plspm_stratified_draws"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -103,6 +104,9 @@ def load():
     lib.plspm_permutation_members.argtypes = [u64, i64, i64, i64, vp]
     lib.plspm_permutation_device.argtypes = [vp, i64, u64, i64, i64, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     lib.plspm_permutation_counts.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
+    lib.plspm_stratified_draws.argtypes = [u64, i64, i64, vp, vp]
+    lib.plspm_stratified_bootstrap_device.argtypes = [vp, i64, u64, i64, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.plspm_stratified_pair_counts.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.plspm_profile_enable.argtypes = [vp, i32]
     lib.plspm_profile_read.argtypes = [vp, i32, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
     lib.plspm_profile_reset.argtypes = [vp]
@@ -185,6 +189,17 @@ def permutation_members(seed, perm, n, n1):
     if rc:
         raise NativeBackendError("plspm_permutation_members failed (%d)" % rc)
     return member.astype(bool)
+
+
+def stratified_draws(seed, rep, member):
+    """Host mirror of the on-device draws of the two-group bootstrap for resample ``rep``: [n] int32, entries [0, n_a) the drawn rows of
+    group a (``member`` True), [n_a, n) those of group b."""
+    member = np.ascontiguousarray(member, dtype=np.uint8)
+    rows = np.empty(member.shape[0], dtype=np.int32)
+    rc = load().plspm_stratified_draws(seed, rep, member.shape[0], _ptr(member), _ptr(rows))
+    if rc:
+        raise NativeBackendError("plspm_stratified_draws failed (%d)" % rc)
+    return rows
 
 
 def i8_tile_plan(count_tiles, pair_tiles, cus=256, mix=True):
@@ -387,6 +402,36 @@ class NativeModel:
         used = ctypes.c_int64(0)
         self._check(self._lib.plspm_permutation_counts(self._h, B, _ptr(observed_diff), _ptr(exceed), ctypes.byref(used)), "plspm_permutation_counts")
         return exceed, used.value
+
+    def stratified_bootstrap(self, B, member, seed=0, rep_offset=0, draws=None):
+        """Enqueue B resamples of the two-group bootstrap (plspm_stratified_bootstrap_device): ``member`` [N] bools (True = group a); 2B
+        records stay on the handle, record 2p = group a of resample rep_offset + p, 2p + 1 = its group b.  ``draws`` [B, N] int32: explicit
+        draws in the layout of ``stratified_draws`` instead of the on-device ones (tests)."""
+        member = np.ascontiguousarray(member, dtype=np.uint8)
+        if member.shape != (self.N,):
+            raise ValueError("member must have N entries")
+        if draws is not None:
+            draws = np.ascontiguousarray(draws, dtype=np.int32)
+            if draws.shape != (B, self.N):
+                raise ValueError("draws must have shape (B, N)")
+        d_out, d_st, d_it = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.plspm_stratified_bootstrap_device(self._h, B, seed, rep_offset, _ptr(member), _ptr(draws), ctypes.byref(d_out),
+                                                                ctypes.byref(d_st), ctypes.byref(d_it)), "plspm_stratified_bootstrap_device")
+        self.last_B = 2 * B
+        return d_out.value, d_st.value, d_it.value
+
+    def stratified_pair_counts(self, B, center_a, center_b):
+        """Henseler's all-pairs counts on the last ``stratified_bootstrap`` call (plspm_stratified_pair_counts): ([R] int64 #{(i, k) :
+        2 center_a - x_a,i > 2 center_b - x_b,k}, OK records of group a, OK records of group b)."""
+        center_a = np.ascontiguousarray(center_a, dtype=np.float64)
+        center_b = np.ascontiguousarray(center_b, dtype=np.float64)
+        if center_a.shape != (self.row_width,) or center_b.shape != (self.row_width,):
+            raise ValueError("center_a / center_b must have row_width entries")
+        above = np.empty(self.row_width, dtype=np.int64)
+        used_a, used_b = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.plspm_stratified_pair_counts(self._h, B, _ptr(center_a), _ptr(center_b), _ptr(above), ctypes.byref(used_a),
+                                                           ctypes.byref(used_b)), "plspm_stratified_pair_counts")
+        return above, used_a.value, used_b.value
 
     def summary(self, B, original, d_rows=None, stride=0):
         """Device-side _create_summary of the last bootstrap on this handle (or of the device records at ``d_rows``).
