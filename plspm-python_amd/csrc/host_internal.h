@@ -30,6 +30,7 @@
 #include "solver_quad.h"
 #include "solver_wave16.h"
 #include "solver_route.h"
+#include "nm_route.h"
 
 using namespace plspm;
 
@@ -39,6 +40,31 @@ __host__ __device__ __forceinline__ long lmin(long a, long b) { return a < b ? a
 #include "model.h"
 
 inline RouteShape route_shape(const plspm_model* m) { return {m->P, m->L, m->kmax, m->n_chol, m->n_eff, (int)m->pred_idx.size(), m->boff.data()}; }
+// nm_route.h: the shape, the options and the plan of a non-metric call on this handle (an attached second stage streams its first stage's data)
+inline NmShape plan_shape(const plspm_model* m) {
+    const plspm_model* src = m->stage1 ? m->stage1 : m;
+    const std::vector<int>& blocks = m->stage1 ? m->lv_cols : m->boff;
+    NmShape s{};
+    s.P = m->P; s.P1 = src->P; s.Pm = m->Pm; s.L = m->L; s.kmax = m->kmax; s.n_chol = m->n_chol; s.n_eff = m->n_eff; s.nedge = (int)m->pred_idx.size();
+    s.cmax = m->cmax; s.kmv = m->kmv; s.max_iter = m->max_iter; s.N = src->N; s.nmx_K = m->nmx_K;
+    s.kb = 1;
+    for (int l = 0; l < m->L; ++l) s.kb = std::max(s.kb, blocks[l + 1] - blocks[l]);
+    s.nonmetric = m->nonmetric != 0; s.categorical = m->categorical != 0; s.cat_pure = m->cat_pure; s.src_cat_pure = src->categorical && src->cat_pure;
+    s.all_mode_a = std::all_of(m->mode.begin(), m->mode.end(), [](int mode) { return mode == PLSPM_MODE_A; });
+    s.attached = m->stage1 != nullptr; s.has_stage2 = m->stage2 != nullptr; s.has_ind = m->n_ind != 0;
+    s.codes_tables = m->stage1 ? (m->d_mv_base2 && m->d_lmv2_off) : (m->d_mv_base && m->d_lmv_off);
+    return s;
+}
+inline NmOptions nm_options(const plspm_model* m) {
+    const plspm_model::Tune& t = m->tune;
+    return {t.conv_pass, t.conv_gy, t.nm_k16, t.nm_wave, t.nm_codes, t.nm_mfma, t.nm_subset, t.nm_cat_one, t.nm_cpl, t.nm_c10, t.nm_fast_lds, t.nm_wave16, t.nm_direct16};
+}
+// lists: the call has (row,count) lists for these problems (the dense pass reads their uint16 histograms when the bootstrap built them)
+inline NmPlan plan_nonmetric(const plspm_model* m, long nproblems, bool counts8, bool lists, bool counts16_ready, bool finish) {
+    const plspm_model* src = m->stage1 ? m->stage1 : m;
+    return nm_plan(plan_shape(m), NmCall{nproblems, counts8, lists && src->dcnt_ready, counts16_ready, finish}, nm_options(m));
+}
+inline size_t nm_state_doubles_of(const plspm_model* m) { return (size_t)nm_state_doubles_of(plan_shape(m)); }
 // Dynamic LDS beyond the 64 KiB default needs an explicit opt-in per kernel.
 inline int allow_lds(plspm_model* m, const void* fn, size_t bytes) {
     if (bytes > kMaxLds) return fail(m, PLSPM_E_LIMIT, "kernel needs more than 160 KiB of LDS");
@@ -77,14 +103,13 @@ int run_impute(plspm_model* m, long nproblems, const double* Min, const double**
 int launch_solver(plspm_model* m, long nproblems, const double* Mp, long mp_stride, const SolverOut& so, int threads);
 // the metric solver of a bootstrap batch: `route` as metric_batch_route chose it when the int8 Gram wrote dense matrices, else ROUTE_LDS
 int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const SolverOut& so);
-// Scale.NUM / RAW non-metric bootstrap batches as ONE solver launch (round 6; solver_wave16.h NM): does this model have such a kernel, and the launch itself
+// Scale.NUM / RAW non-metric bootstrap batches as ONE solver launch (round 6; solver_wave16.h NM; nm_route.h num_one says whether the model has such a kernel)
 // (dense moment matrices at m->gram; maps / steps as kernels_solver.h solver_nmwave_kernel takes them; force + live: the replay of `nb` listed replicates)
-bool nm_wave_solver_covers(const plspm_model* m);
 int launch_nm_wave_solver(plspm_model* m, long nb, const SolverOut& so, double* maps, long maps_stride, int* steps, const int* force, const int* live);
-size_t nm_state_doubles_of(const plspm_model* m);
-size_t nm_dense_lds(const plspm_model* m, bool* whole, int* kb_out);
-int run_nonmetric(plspm_model* m, long nproblems, const double* Mp, long mp_stride, const SolverOut& so_in, const int2* ent, const int* nent, long ent_stride, int threads,
-                  bool finish = true, const void* cd8 = nullptr, int cd8_MT = 0, bool counts16_ready = false);
+// plspm_nonmetric.hip: the non-metric solve of pl.call.nproblems problems as `pl` (plan_nonmetric) routes it.  Mp: their packed scatter matrices (unless the
+// Gram wrote the uint16 counts); ent / nent: their (row,count) lists or null; cd8 / cd8_MT: the int8 row multiplicities the digit-plane Gram consumed or null
+int run_nonmetric(plspm_model* m, const NmPlan& pl, const double* Mp, long mp_stride, const SolverOut& so_in, const int2* ent, const int* nent, long ent_stride, int threads,
+                  const void* cd8 = nullptr, int cd8_MT = 0);
 // second-stage moments of a HOC pair by congruence with the first stage's score maps: m->gram (stage 1) -> m2->gram
 int run_hoc_moments(plspm_model* m, plspm_model* m2, long nb);
 
@@ -97,9 +122,8 @@ int prepare_zs_stats(plspm_model* m);
 int prepare_zs(plspm_model* m, int floor = 0);      // floor: at least this many digit planes (0: the handle's own choice)
 int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const int32_t* d_idx, double* out, bool dense, bool* fallback, const void** counts = nullptr,
                 int* counts_MT = nullptr, unsigned short* out16 = nullptr, bool* wrote16 = nullptr);
-bool nm_wave_route_planned(const plspm_model* m);     // plspm_nonmetric.hip: Scale.NUM / RAW batches as one solver launch + verification (run_nonmetric_wave)
-int run_nonmetric_wave(plspm_model* m, long nb, const SolverOut& so, const void* cd8, int cd8_MT);
-bool nm_wave_step_planned(const plspm_model* m);      // plspm_nonmetric.hip: the categorical iteration of this handle runs one wave per problem (kernels_nmw.h)
+// plspm_nonmetric.hip: a Scale.NUM / RAW batch as one solver launch + verification (pl.num_one)
+int run_nonmetric_wave(plspm_model* m, const NmPlan& pl, const SolverOut& so, const void* cd8, int cd8_MT);
 
 // ---- plspm_permute.hip (two-group permutation test)
 // One call's splits: permutation rep_offset + p has problem 2p = group a (n1 rows), 2p + 1 = the other N - n1 rows; `d_member` [B][N] bytes 0/1

@@ -24,19 +24,9 @@
 // iteration counts are equal (tests/test_gpu_categorical.py).
 #pragma once
 #include <type_traits>
+#include "nm_route.h"      // nmw::LMAX_MAX, CMAX_MAX, CPL8, lds_doubles: host arithmetic the route plan shares
 
 namespace nmw {
-
-constexpr int LMAX_MAX = 8, CMAX_MAX = 16, CPL8 = 8;      // LVs (the kernel is instantiated for LMAX = 2, 4, 6, 8), categories per MV (CMAX = 8; 16: ten-point items -- the reference's own
-                                                         // mobi / ECSI example data -- at one wave per SIMD), columns per lane
-
-// LDS of one problem (doubles): c | tq | mean | mzown (each QP = Q + 1 rounded up to 8), then the small arrays, then c_old (QP)
-__host__ __device__ inline long lds_doubles(int Q, int Pm, int L, int kmax) {
-    const long QP = (Q + 1 + 7) & ~7L;
-    const long step = 3L * L * L + 6L * L + 2L * Pm + (long)L * regression_scratch_doubles(kmax) + 8 + 16;
-    const long fin = workspace_small_doubles(Pm, L, kmax, 0) + Pm;           // the fused finish: MV-level workspace of finish_problem + one row of the MV moment matrix
-    return 4 * QP + (step > fin ? step : fin) + QP;             // (+ QP, round 6: the old score map beside the new one for the step's own bound)
-}
 
 // CPL consecutive uint16 counts of a row as packed dwords: 8 columns per lane (one 16-byte load; up to 511 aug columns) or -- round 6 -- 6 (one 12-byte load; up to 383
 // columns): the count streams are VALU-bound and 300 columns at 8 per lane leave 26 of the 64 lanes without work; at 6 per lane 51 lanes share it.

@@ -40,21 +40,22 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     // metric models on the int8 Gram: a solver on dense moment matrices (solver_route.h) unless the model is outside every dense solver's class
     const SolverRoute route = metric_batch_route(route_shape(m), m->tune.solver_wave, m->tune.solver_quad, m->tune.solver_rows);
     const bool rows_solver = gpath == 2 && route != ROUTE_LDS && !m->n_ind && !m->nonmetric && !m->moments_out;
+    // The non-metric route of the call as its batches will take it (nm_route.h): planned here with the int8 counts the call expects, and again per chunk with
+    // what the chunk has (a chunk whose explicit indices made the int8 Gram fall back to the fp64 one has none) -- the same function, so buffers and launches agree.
     // round 6: Scale.NUM / RAW batches on the int8 route as one solver launch on dense moment matrices + a verification pass (plspm_nonmetric.hip
     // run_nonmetric_wave) -- needs the int8 counts the Gram consumed (explicit index lists of at most 65,535 rows keep the per-iteration launches and their
-    // uint16 histograms; so does a chunk whose explicit indices made the int8 Gram fall back to the fp64 one)
-    const bool nm_wave = gpath == 2 && counts8_plan && !m->moments_out && nm_wave_route_planned(m);
+    // uint16 histograms)
+    const NmPlan nm = m->nonmetric ? plan_nonmetric(m, B, counts8_plan, false, false, true) : NmPlan{};
+    const bool nm_wave = gpath == 2 && !m->moments_out && nm.num_one;
     // the fp64 Gram walks (row,count) lists (explicit indices may fall back to it); so do the stop-rule passes of the non-metric solvers
     const bool need_lists = gpath == 1 || d_idx != nullptr || (m->nonmetric && !counts8_plan);
     const size_t kpad = (size_t)i8_kblocks(N) * 64;
     // (the global-scratch histogram serves the (row,count) lists only: the int8 route on Philox draws never builds them)
     const bool need_ghist = !lds_hist && need_lists;
-    const bool cat_one = gpath_plan == 2 && counts8_plan && !m->stage1 && m->tune.nm_cat_one != 0 && m->tune.nm_subset != 0 && m->tune.nm_mfma != 0 && nm_wave_step_planned(m);
+    const bool cat_one = nm.one_launch;
     const size_t per_rep = (need_lists ? (size_t)ent_stride * sizeof(int2) : 0) + (size_t)std::max<long>(psize, cov_doubles(m->Pg)) * sizeof(double) + (need_ghist ? (size_t)N * sizeof(unsigned) : 0) +
                            (want_dcnt ? (size_t)dcnt_stride * sizeof(unsigned short) : 0) + (gpath == 2 ? kpad : 0) +
-                           (nm_wave ? (size_t)(m->max_iter + 2) * (m->P + m->L + 1) * sizeof(double) + 4 * ((size_t)(2 * m->P + 2 * m->L + 1) + 8) * sizeof(double) : 0) +      // (score maps + verification tables)
-                           // (the categorical one-launch form, plspm_nonmetric.hip: a map per step and replicate, digit planes of eight (replicate, step) slots per replicate)
-                           (cat_one ? (size_t)(m->max_iter + 2) * (m->P + m->L + 1) * sizeof(double) + 8 * ((size_t)m->L * 2 * 7 * 2 * 64 + 64) : 0);
+                           ((nm_wave || cat_one) ? nm.verify_bytes_per_rep : 0);      // (the one-launch forms: score maps + verification tables)
     // (the one-launch categorical batch lasts as long as its slowest replicate -- the ones that never converge run max_iter + 1 steps in one wave --, so cutting a call
     //  into passes multiplies that tail: 16 GiB of the 288 for it instead of 2)
     int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(((cat_one ? 16ull : 2ull) << 30) / per_rep)));
@@ -91,7 +92,7 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     double* const gram_buf = (double*)m->gram.p;
     // round 5: all-indicator categorical models on the wave step -- the int8 product writes the uint16 count matrices the step streams itself (no fp64 slots, no
     // scatter pass: kernels_gram_i8.h IND epilogue, kernels_nonmetric.h nmg_kernel<4>); option "nm_direct16" 0: the packed fp64 matrices + nmg_kernel<3>
-    const bool want16 = gpath == 2 && m->nonmetric && !m->stage2 && !m->stage1 && !m->moments_out && m->tune.nm_direct16 != 0 && nm_wave_step_planned(m);
+    const bool want16 = gpath == 2 && m->nonmetric && !m->moments_out && nm.direct16;
     if (want16 && (rc = ensure(m, m->gK16, (size_t)chunk * (m->P + 1) * ((m->P + 1 + 7) & ~7) * sizeof(unsigned short) + 64))) return rc;
     hipEvent_t parked_stop = m->stop_event;
     m->stop_event = nullptr;
@@ -134,23 +135,24 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
         }
         SolverOut so{};
         so.row = rows_out + b0 * R; so.row_stride = R; so.status = (int*)m->status.p + b0; so.iters = (int*)m->iters.p + b0;
+        const bool lists = need_lists && !cd8;                         // (built above only when the int8 counts are not used)
+        const int2* ent_l = lists ? (const int2*)m->ent.p : nullptr;
+        const int* nent_l = lists ? (const int*)m->nent.p : nullptr;
         if (m->nonmetric && m->stage2) {
             // two-stage HOC estimation per replicate (solver_hoc.h): stage 1 to convergence (no report), stage-2 moments by congruence,
             // stage 2 on the second handle's descriptors with the convergence pass streaming THIS handle's data
             plspm_model* m2 = m->stage2;
             const long psize2 = packed_size(m2->Ts);
-            const int2* ent_l = (need_lists && !cd8) ? (const int2*)m->ent.p : nullptr;      // (built above only when the int8 counts are not used)
-            const int* nent_l = (need_lists && !cd8) ? (const int*)m->nent.p : nullptr;
             // (threads per problem: 128 unless the handle's "nm_threads" option says otherwise -- each stage reads its own handle's)
             const int t1 = m->tune.nm_threads > 0 ? m->tune.nm_threads : 128, t2 = m2->tune.nm_threads > 0 ? m2->tune.nm_threads : 128;
-            if ((rc = run_nonmetric(m, nb, (const double*)m->gram.p, psize, SolverOut{}, ent_l, nent_l, ent_stride, t1, false, cd8, cd8_MT))) return rc;
+            if ((rc = run_nonmetric(m, plan_nonmetric(m, nb, cd8 != nullptr, lists, false, false), (const double*)m->gram.p, psize, SolverOut{}, ent_l, nent_l, ent_stride, t1, cd8, cd8_MT))) return rc;
             if ((rc = run_hoc_moments(m, m2, nb))) return rc;
-            rc = run_nonmetric(m2, nb, (const double*)m2->gram.p, psize2, so, ent_l, nent_l, ent_stride, t2, true, cd8, cd8_MT);
+            rc = run_nonmetric(m2, plan_nonmetric(m2, nb, cd8 != nullptr, lists, false, true), (const double*)m2->gram.p, psize2, so, ent_l, nent_l, ent_stride, t2, cd8, cd8_MT);
             if (rc) return fail(m, rc, "second stage: " + m2->error);
             continue;
         }
         if (m->nonmetric && nm_wave && cd8 && !f64_gram) {
-            if ((rc = run_nonmetric_wave(m, nb, so, cd8, cd8_MT))) return rc;
+            if ((rc = run_nonmetric_wave(m, plan_nonmetric(m, nb, true, false, false, true), so, cd8, cd8_MT))) return rc;
             continue;
         }
         if (m->nonmetric) {
@@ -158,8 +160,7 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
             // threads per problem by model width (measured: 60 columns 0.60 / 0.64 / 0.81 ms with 64 / 128 / 256 threads; 300 indicator
             // columns 21.0 / 13.5 / 10.0 ms)
             const int nm_threads = m->tune.nm_threads > 0 ? m->tune.nm_threads : (m->P > 128 ? 256 : (m->P > 64 ? 128 : 64));
-            if ((rc = run_nonmetric(m, nb, (const double*)m->gram.p, psize, so, (need_lists && !cd8) ? (const int2*)m->ent.p : nullptr, (need_lists && !cd8) ? (const int*)m->nent.p : nullptr, ent_stride,
-                                    nm_threads, true, cd8, cd8_MT, wrote16))) return rc;
+            if ((rc = run_nonmetric(m, plan_nonmetric(m, nb, cd8 != nullptr, lists, wrote16, true), (const double*)m->gram.p, psize, so, ent_l, nent_l, ent_stride, nm_threads, cd8, cd8_MT))) return rc;
             continue;
         }
         if ((rc = launch_batch_solver(m, nb, (rows_solver && !f64_gram) ? route : ROUTE_LDS, so))) return rc;

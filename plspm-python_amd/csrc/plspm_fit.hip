@@ -147,11 +147,6 @@ int run_hoc_moments(plspm_model* m, plspm_model* m2, long nb) {
     return 0;
 }
 
-bool nm_wave_solver_covers(const plspm_model* m) {
-    if (!m->nonmetric || m->categorical || m->n_ind || m->nmx_K > 0 || m->stage1 || m->stage2) return false;
-    return nm_wave_route(route_shape(m)) != ROUTE_NONE;
-}
-
 template <int LMAX>
 static int launch_nm_wave(plspm_model* m, long nb, const SolverOut& so, double* maps, long maps_stride, int* steps, const int* force, const int* live) {
     const size_t lds = (size_t)(wave16_ws_doubles<LMAX>(m->L, m->kmax, m->n_chol) + 64) * sizeof(double);
@@ -162,7 +157,7 @@ static int launch_nm_wave(plspm_model* m, long nb, const SolverOut& so, double* 
 }
 
 int launch_nm_wave_solver(plspm_model* m, long nb, const SolverOut& so, double* maps, long maps_stride, int* steps, const int* force, const int* live) {
-    const SolverRoute route = nm_wave_route(route_shape(m));      // (callers asked nm_wave_solver_covers)
+    const SolverRoute route = nm_wave_route(route_shape(m));      // (callers asked the plan: nm_route.h num_one)
     ProfScope ps(m, PLSPM_K_SOLVER);
     const int rc = route == ROUTE_NM_WAVE_8 ? launch_nm_wave<8>(m, nb, so, maps, maps_stride, steps, force, live)
                  : route == ROUTE_NM_WAVE_16 ? launch_nm_wave<16>(m, nb, so, maps, maps_stride, steps, force, live)
@@ -274,7 +269,7 @@ int plspm_fit(plspm_model_t* m, const plspm_fit_result_t* out) {
     so.fit.lv_cov = d + o_lc; so.fit.indirect = d + o_ind; so.fit.score_w = d + o_sw; so.fit.score_c = d + o_sc;
     so.fit.cov = out->cov ? d + o_cov : nullptr; so.fit.mean = d + o_mean; so.fit.sign = d_sign;
     if (m->nonmetric) {
-        if ((rc = run_nonmetric(m, 1, (const double*)m->gram.p, psize, so, nullptr, nullptr, 0, 256))) return rc;
+        if ((rc = run_nonmetric(m, plan_nonmetric(m, 1, false, false, false, true), (const double*)m->gram.p, psize, so, nullptr, nullptr, 0, 256))) return rc;
     } else {
         const double* Mp; long mp_stride;
         if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;

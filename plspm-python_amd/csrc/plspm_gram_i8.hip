@@ -22,7 +22,7 @@ static int cu_count_of(plspm_model* m) {
 
 bool nm_counts8_possible(const plspm_model* m) {
     return m->nonmetric && m->tune.nm_counts8 != 0 && m->tune.resample_aux == 0 && !m->aux && m->tune.i8_shape == 16 && m->nmx_K == 0 &&
-           nm_dense_lds(m, nullptr, nullptr) != 0 && (!m->stage2 || nm_dense_lds(m->stage2, nullptr, nullptr) != 0);
+           nm_dense_lds(plan_shape(m), m->tune.conv_pass, nullptr) != 0 && (!m->stage2 || nm_dense_lds(plan_shape(m->stage2), m->stage2->tune.conv_pass, nullptr) != 0);
 }
 int choose_gram_path(const plspm_model* m, int64_t B) {
     if (m->tune.gram_path == 1) return 1;

@@ -17,6 +17,7 @@
 #include "../../plspm-python_amd/csrc/solver_quad.h"
 #include "../../plspm-python_amd/csrc/solver_wave16.h"
 #include "../../plspm-python_amd/csrc/solver_route.h"
+#include "../../plspm-python_amd/csrc/nm_route.h"
 
 using namespace plspm;
 
@@ -591,6 +592,22 @@ int hostemu_nmx(int mode_op, int raw, int P, int L, int PA, int scheme, int max_
 int hostemu_solver_route(int P, int L, int kmax, int n_chol, int n_eff, int nedge, const int* boff, int solver_wave, int solver_quad, int solver_rows, int nm) {
     const RouteShape s{P, L, kmax, n_chol, n_eff, nedge, boff};
     return nm ? nm_wave_route(s) : metric_batch_route(s, solver_wave, solver_quad, solver_rows);
+}
+
+// The route of a non-metric call (csrc/nm_route.h nm_plan).  shape: P, P1, Pm, L, kmax, n_chol, n_eff, nedge, cmax, kmv, kb, max_iter, N, nmx_K, then the flags nonmetric,
+// categorical, cat_pure, src_cat_pure, all_mode_a, attached, has_stage2, has_ind, codes_tables; call: nproblems, counts8, lists_dcnt, counts16_ready, finish; opts in the
+// order of NmOptions.  out: error, dense, dense_whole, use_codes, use_mfma, flag_from_list, k16, wave_step, bound_ok, sub_pass, one_launch, step LMAX, CMAX, CPL, num_one,
+// direct16, KS, tpc, nparts, nsub, cat_fast
+void hostemu_nm_plan(const long* sh, const long* call, const int* o, long* out) {
+    NmShape s{};
+    s.P = (int)sh[0]; s.P1 = (int)sh[1]; s.Pm = (int)sh[2]; s.L = (int)sh[3]; s.kmax = (int)sh[4]; s.n_chol = (int)sh[5]; s.n_eff = (int)sh[6]; s.nedge = (int)sh[7]; s.cmax = (int)sh[8];
+    s.kmv = (int)sh[9]; s.kb = (int)sh[10]; s.max_iter = (int)sh[11]; s.N = sh[12]; s.nmx_K = (int)sh[13];
+    s.nonmetric = sh[14]; s.categorical = sh[15]; s.cat_pure = sh[16]; s.src_cat_pure = sh[17]; s.all_mode_a = sh[18]; s.attached = sh[19]; s.has_stage2 = sh[20]; s.has_ind = sh[21];
+    s.codes_tables = sh[22];
+    const NmPlan p = nm_plan(s, NmCall{call[0], call[1] != 0, call[2] != 0, call[3] != 0, call[4] != 0}, NmOptions{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11], o[12]});
+    const long v[] = {p.error, p.dense, p.dense_whole, p.use_codes, p.use_mfma, p.flag_from_list, p.k16, p.wave_step, p.bound_ok, p.sub_pass, p.one_launch, p.step_lmax, p.step_cmax, p.step_cpl,
+                      p.num_one, p.direct16, p.KS, p.tpc, p.nparts, p.nsub, p.cat_fast};
+    for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
 }
 
 long hostemu_packed_index(int T, int p, int q) { return packed_index(T, p, q); }
