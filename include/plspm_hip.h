@@ -361,7 +361,7 @@ int plspm_bootstrap_summary(plspm_model_t* m, const void* d_rows, int64_t B, int
  * pairs in lexicographic order -- exactly n1 rows, a function of (seed, r, N, n1) only.  Both groups are estimated like bootstrap
  * replicates (same record layout; each group's own n, treatment and `scaled` scalar from its moments), on the int8 Gram route with at
  * least seven digit planes (correctly rounded moment sums whatever the group size), whatever "gram_path" / "i8_min_batch" say.
- * Plain metric handles only (no non-metric scales, missing values or two-stage pair): PLSPM_E_ARG otherwise; PLSPM_E_LIMIT where the int8
+ * Plain metric handles only (no non-metric scales, no missing values, not part of a two-stage pair): PLSPM_E_ARG otherwise; PLSPM_E_LIMIT where the int8
  * route is closed (N >= 2^24, digit planes above their budget).
  *
  * plspm_permutation_device: permutations [rep_offset, rep_offset + B), 1 <= B <= 2^29, 1 <= n1 < N.  Enqueues 2B problems: record 2p =
@@ -403,6 +403,51 @@ int plspm_stratified_bootstrap_device(plspm_model_t* m, int64_t B, uint64_t seed
                                       void** d_out, void** d_status, void** d_iters);
 int plspm_stratified_pair_counts(plspm_model_t* m, int64_t B, const double* center_a, const double* center_b, int64_t* above, int64_t* used_a,
                                  int64_t* used_b);
+
+/*
+ * ---- Out-of-sample prediction: repeated k-fold cross-validation (PLSpredict) ------------------------------------------------------
+ * How well does the model predict rows it was not fitted on?  Repetition r (global id) cuts the N uploaded rows into k folds: row i carries the
+ * key  word (i & 3) of Philox4x32-10(counter = (i >> 2, 3, lo32(r), hi32(r)), key = (lo32(seed), hi32(seed)))  (counter word 1 is 3 where the
+ * bootstrap's is 0, the permutation's 1, the stratified draws' 2); the rows ordered by (key, row), the one at position j belongs to fold
+ * (j * k) / N (integer division) -- a function of (seed, r, N, k) only; fold sizes differ by at most one and every row is held out exactly once per
+ * repetition.  Problem q = r * k + f is the model estimated on the rows outside fold f of repetition r, like a bootstrap replicate (same record
+ * layout; its own n, treatment and `scaled` scalar from its moments), on the int8 Gram route with at least seven digit planes whatever
+ * "gram_path" / "i8_min_batch" say; the floor belongs to this call (a later bootstrap keeps its own planes).
+ * Plain metric handles only (no non-metric scales, no missing values, not part of a two-stage pair): PLSPM_E_ARG otherwise; PLSPM_E_LIMIT where the int8 route
+ * is closed (N >= 2^24, digit planes above their budget).  2 <= k <= 256, every training set of at least four rows, 1 <= reps, reps * k <= 2^29.
+ *
+ * plspm_cv_device: repetitions [rep_offset, rep_offset + reps).  Enqueues reps * k problems; their records stay on the handle as its last records
+ *   (plspm_bootstrap_fetch reads them), beside the fold ids, the rows in fold order and the training moments of every problem, until the next
+ *   bootstrap-like call or upload.  *d_out / *d_status / *d_iters as plspm_bootstrap_device.
+ *   fold   NULL: the folds above, drawn on the device;  else [reps*N] host bytes (test seam): row r holds the fold id of every row in repetition r,
+ *          every id below k and every fold non-empty, else PLSPM_E_ARG.
+ * plspm_cv_moments: the training moments of the last plspm_cv_device call's problems (reps, k: that call's, else PLSPM_E_ARG; PLSPM_E_STATE when a later
+ *   call replaced them), accumulated in fp64 on the resident rows (full sample minus fold).  Any output may be NULL.
+ *   n_train [reps*k];  mean [reps*k*P] the training mean of every raw column (device column order);  cross [reps*k*P(P+1)/2] the cross-products
+ *   sum (x_p - mean_p)(x_p' - mean_p') of the training rows, upper triangle by rows: (p, p'), p <= p', at p P - p (p - 1) / 2 + p' - p.
+ * plspm_cv_targets: the T target indicators -- the device columns of every latent variable that has a predecessor, ascending -- into cols
+ *   (may be NULL); returns T.
+ * plspm_cv_predict: the errors of an affine prediction x_hat = C_q [1; x_raw] (C_q [T][P + 1], x_raw in device column order) of every problem
+ *   on its held-out rows, e = x_t - x_hat_t in fp64:  sse / sae / sst [reps*k*T] = sum e^2, sum |e|, sum (x_t - training mean_t)^2;
+ *   rows [reps*k] = the held-out rows the problem covered.  A problem whose matrix holds a NaN covers nothing: its sums and rows are 0.
+ *   coef   NULL: the PLS prediction of each problem's own fit.  The score of latent variable l for an unseen row is the one plspm_fit's `scores`
+ *          would give it under the training fit (training means, the training `scaled` scalar, the normalised weights, the fit's sign); the
+ *          predicted score of an endogenous j is sum_i beta_ji y_i over its predecessors -- technique 0 ("direct antecedents"): y_i the row's own
+ *          score; technique 1 ("earliest antecedents"): the predicted score where i has predecessors itself --; indicator p of j is predicted as
+ *          training mean_p + loading_p sd_p * predicted score (sd_p the training rows' population standard deviation; the scores' is 1).
+ *          A problem whose status is not PLSPM_OK gets a NaN matrix.
+ *          else [reps*k*T*(P+1)] host: explicit matrices (the linear-model benchmark; tests); technique is ignored.
+ *   pred_sum [N*T], pred_cnt [N] (both or neither): per row the sum of its predictions over the problems that covered it, and their number
+ *          (added up by atomics: the order of the repetitions' terms is not fixed).
+ *   PLSPM_E_LIMIT when the model has more than 256 targets, or its matrix -- (P + 1) x T doubles beside a tile of 16 rows -- does not fit the
+ *   160 KiB of LDS (128 targets among 128 columns fit).
+ */
+int plspm_cv_device(plspm_model_t* m, int64_t reps, int32_t k, uint64_t seed, int64_t rep_offset, const uint8_t* fold, void** d_out, void** d_status,
+                    void** d_iters);
+int plspm_cv_moments(plspm_model_t* m, int64_t reps, int32_t k, double* n_train, double* mean, double* cross);
+int plspm_cv_targets(plspm_model_t* m, int32_t* cols);
+int plspm_cv_predict(plspm_model_t* m, int64_t reps, int32_t k, int32_t technique, const double* coef, double* sse, double* sae, double* sst,
+                     int64_t* rows, double* pred_sum, int32_t* pred_cnt);
 
 /*
  * ---- Multi-GPU: replicate shards + ONE RCCL all-gather --------------------------------------------------------------------------

@@ -43,6 +43,15 @@ int plspm_permutation_members(uint64_t seed, int64_t perm, int64_t N, int64_t n1
  * of group a (member = 1), [n_a, N) those of group b -- the layout of its `draws`.  PLSPM_E_ARG when a group has fewer than two rows. */
 int plspm_stratified_draws(uint64_t seed, int64_t rep, int64_t N, const uint8_t* member, int32_t* rows);
 
+/* The fold ids the on-device draw of plspm_cv_device gives the rows in repetition `rep` (host-side mirror, for tests): fold [N] bytes below k.
+ * PLSPM_E_ARG unless 2 <= k <= 256 and N >= k. */
+int plspm_cv_folds(uint64_t seed, int64_t rep, int64_t N, int32_t k, uint8_t* fold);
+
+/* Test seam: what the last plspm_cv_device call (reps, k: that call's) left on the handle -- fold [reps*N] the fold id of every row, order [reps*N]
+ * the rows of every repetition in fold order (ascending inside a fold), offsets [reps*(k+1)]: fold f of repetition r is order[r*N + offsets[r*(k+1) + f]
+ * .. r*N + offsets[r*(k+1) + f + 1]).  Any output may be NULL. */
+int plspm_cv_fold_ids(plspm_model_t* m, int64_t reps, int32_t k, uint8_t* fold, int32_t* order, int32_t* offsets);
+
 /* Test seam, host arithmetic only (no device is touched): how the six-plane int8 Gram cuts `count_tiles` (16 replicates each) x
  * `pair_tiles` (32 pair columns each) into tile rows on `cus` CUs ("i8_rt" 0).  *tall rows of 20 count tiles and, with `mix` != 0, *shrt
  * rows of 16 in one launch; returns 1 when that launch is taken, 0 when the 256-replicate kernel is no slower, PLSPM_E_ARG on bad sizes. */

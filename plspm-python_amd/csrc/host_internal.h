@@ -137,3 +137,10 @@ int launch_perm_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB
 struct StratSpec { uint64_t seed; int64_t rep_offset; int64_t n_a; const int32_t* d_rows; const int32_t* d_draws; };
 // run_gram_i8 on a stratified call (m->strat set): the counts of problems [prob0, prob0 + nb) (prob0, nb even) into `cd`, same layout
 int launch_strat_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
+
+// ---- plspm_cv.hip (k-fold cross-validation: out-of-sample prediction)
+// One call's folds: problem r * k + f = the rows of repetition rep_offset + r outside fold f; `d_fold` [reps][N] fold ids (drawn on the device from
+// the Philox keys or uploaded, kernels_cv.h) -- ready on the handle's stream before plspm_detail_bootstrap runs.
+struct CvSpec { int64_t reps; int k; const uint8_t* d_fold; };
+// run_gram_i8 on a cross-validation call (m->cv set): the 0/1 counts of problems [prob0, prob0 + nb) into `cd`, layout of resample_i8_kernel
+int launch_cv_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);

@@ -31,6 +31,8 @@ void plspm_stream_release(hipStream_t s);
 struct PermSpec;
 // Draw spec of a stratified bootstrap call of the two-group test (plspm_permute.hip) while plspm_detail_bootstrap runs it.
 struct StratSpec;
+// Fold spec of a cross-validation call (plspm_cv.hip) while plspm_detail_bootstrap runs it.
+struct CvSpec;
 
 struct ProfSlot { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, pool; double total_ms = 0.0; int64_t launches = 0; };
 
@@ -138,6 +140,9 @@ struct plspm_model {
     const StratSpec* strat = nullptr;        // plspm_stratified_bootstrap_device: the batch's problems are resamples drawn inside each group (int8 route)
     Buf strat_rows, strat_draws, strat_io, strat_u;      // ... both groups' row lists, explicit draws, the pair counts' in / out block and u values
     std::vector<uint8_t> strat_member;       // ... the memberships strat_rows was built from (uploaded again only when they change)
+    const CvSpec* cv = nullptr;              // plspm_cv_device: problem r * k + f is the training set of fold f of repetition r (int8 route, 0/1 counts)
+    Buf cv_fold, cv_thr, cv_idx, cv_off, cv_mom, cv_coef, cv_io, cv_pred, cv_tab;      // ... fold ids, thresholds, rows in fold order + offsets, training moments, coefficient matrices, error sums, predictions, small tables
+    int64_t cv_reps = 0; int cv_k = 0;       // ... the last plspm_cv_device call whose folds, moments and records are on the handle (0: none)
     int last_gram_path = 0;       // 1 fp64 MFMA, 2 int8 digit planes: what the last bootstrap call used (plspm_model_get_info)
     int last_i8_dma = 0;          // 1 global_load_lds, 2 buffer_load ... lds: the LDS-DMA form of the last int8 Gram launch
     int last_i8_persist = 0;      // 1: ... as one persistent workgroup per CU (gram_i8pp_kernel)

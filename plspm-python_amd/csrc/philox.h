@@ -49,3 +49,10 @@ __host__ __device__ __forceinline__ u32x4 permute_quad(uint64_t seed, uint64_t p
 __host__ __device__ __forceinline__ u32x4 strat_quad(uint64_t seed, uint64_t s, uint32_t q) {
     return philox4x32_10(q, 2u, (uint32_t)s, (uint32_t)(s >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
 }
+
+// Sort key of row i (0 <= i < N) in repetition `rep` of the k-fold cross-validation: word (i & 3) of Philox(counter = (i >> 2, 3, rep), key = seed).
+// Counter word 1 is 3 (bootstrap 0, permutation 1, stratified draws 2): the four streams never share a block.  The rows ordered by (key, row): the
+// one at position j belongs to fold (j * k) / N -- kernels_cv.h, plspm_cv_folds.
+__host__ __device__ __forceinline__ u32x4 cv_quad(uint64_t seed, uint64_t rep, uint32_t q) {
+    return philox4x32_10(q, 3u, (uint32_t)rep, (uint32_t)(rep >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+}

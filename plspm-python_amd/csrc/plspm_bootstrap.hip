@@ -28,8 +28,8 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     // non-metric models on the int8 route with Philox draws (round 3): the dense stop-rule pass reads its row multiplicities from the int8
     // counts the Gram consumed -- no second resample kernel, no (row,count) lists, no uint16 histograms (set_option "nm_counts8" 0: the
     // round-2 path, kept for A/B and for the cases below)
-    // (a two-group permutation call, plspm_permute.hip, always takes the int8 route: its caller checked that the route is open)
-    const int gpath_plan = (m->perm || m->strat) ? 2 : choose_gram_path(m, B);
+    // (a two-group permutation call, plspm_permute.hip, always takes the int8 route: its caller checked that the route is open; so does a cross-validation call, plspm_cv.hip)
+    const int gpath_plan = (m->perm || m->strat || m->cv) ? 2 : choose_gram_path(m, B);
     // (explicit index lists of at most 65,535 rows keep the round-3 arrangement -- uint16 histograms beside the lists they need anyway; beyond
     //  one window the int8 counts are the only dense multiplicities there are)
     const bool counts8_plan = gpath_plan == 2 && (!d_idx || !lds_hist) && nm_counts8_possible(m);
@@ -62,13 +62,14 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     if (gpath == 2 && chunk < B) chunk = std::max<int64_t>(256, chunk & ~(int64_t)255);      // whole 256-replicate tiles per pass
     int rc;
     if (gpath == 2) {
-        if ((rc = prepare_zs(m, (m->perm || m->strat) ? 7 : 0))) return rc;      // (a permutation / stratified call: seven planes at least, plspm_permute.hip)
+        if ((rc = prepare_zs(m, (m->perm || m->strat || m->cv) ? 7 : 0))) return rc;      // (a permutation / stratified / cross-validation call: seven planes at least, plspm_permute.hip, plspm_cv.hip)
     }
     if (need_lists) {
         if ((rc = ensure(m, m->ent, (size_t)chunk * ent_stride * sizeof(int2)))) return rc;
         if ((rc = ensure(m, m->nent, (size_t)chunk * sizeof(int)))) return rc;
     }
     if ((rc = ensure(m, m->gram, (size_t)chunk * std::max<long>(psize, (rows_solver || nm_wave) ? cov_doubles(m->Pg) : 0) * sizeof(double)))) return rc;
+    if (!m->cv) m->cv_reps = 0;      // (the records of a cross-validation call are about to be replaced, or its status / iteration buffers reused)
     if (!rows_out) {
         m->rows_B = 0;
         if ((rc = ensure(m, m->rows, (size_t)B * R * sizeof(double)))) return rc;

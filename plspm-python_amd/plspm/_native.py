@@ -28,7 +28,8 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_op_inner_weights", "plspm_op_outer_weights", "plspm_op_outer_weights_nonmetric", "plspm_gram_tile_plan",
            "plspm_comm_create_ex", "plspm_comm_split", "plspm_comm_transport", "plspm_comm_max_channels", "plspm_group_set_option", "plspm_group_plan", "plspm_chunk_plan",
            "plspm_permutation_device", "plspm_permutation_counts", "plspm_permutation_members",
-           "plspm_stratified_bootstrap_device", "plspm_stratified_pair_counts", "plspm_stratified_draws"]
+           "plspm_stratified_bootstrap_device", "plspm_stratified_pair_counts", "plspm_stratified_draws",
+           "plspm_cv_folds", "plspm_cv_device", "plspm_cv_fold_ids", "plspm_cv_moments", "plspm_cv_targets", "plspm_cv_predict"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -107,6 +108,13 @@ def load():
     lib.plspm_stratified_draws.argtypes = [u64, i64, i64, vp, vp]
     lib.plspm_stratified_bootstrap_device.argtypes = [vp, i64, u64, i64, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     lib.plspm_stratified_pair_counts.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    lib.plspm_cv_folds.argtypes = [u64, i64, i64, i32, vp]
+    lib.plspm_cv_device.argtypes = [vp, i64, i32, u64, i64, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.plspm_cv_fold_ids.argtypes = [vp, i64, i32, vp, vp, vp]
+    lib.plspm_cv_moments.argtypes = [vp, i64, i32, vp, vp, vp]
+    lib.plspm_cv_targets.restype = i32
+    lib.plspm_cv_targets.argtypes = [vp, vp]
+    lib.plspm_cv_predict.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.plspm_profile_enable.argtypes = [vp, i32]
     lib.plspm_profile_read.argtypes = [vp, i32, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
     lib.plspm_profile_reset.argtypes = [vp]
@@ -200,6 +208,15 @@ def stratified_draws(seed, rep, member):
     if rc:
         raise NativeBackendError("plspm_stratified_draws failed (%d)" % rc)
     return rows
+
+
+def cv_folds(seed, rep, n, k):
+    """Host mirror of the on-device fold draw of the k-fold cross-validation: [n] uint8, the fold of every row in repetition ``rep``."""
+    fold = np.empty(n, dtype=np.uint8)
+    rc = load().plspm_cv_folds(seed, rep, n, k, _ptr(fold))
+    if rc:
+        raise NativeBackendError("plspm_cv_folds failed (%d)" % rc)
+    return fold
 
 
 def i8_tile_plan(count_tiles, pair_tiles, cus=256, mix=True):
@@ -432,6 +449,58 @@ class NativeModel:
         self._check(self._lib.plspm_stratified_pair_counts(self._h, B, _ptr(center_a), _ptr(center_b), _ptr(above), ctypes.byref(used_a),
                                                            ctypes.byref(used_b)), "plspm_stratified_pair_counts")
         return above, used_a.value, used_b.value
+
+    def cv(self, reps, k, seed=0, rep_offset=0, fold=None):
+        """Enqueue ``reps`` repetitions of a k-fold cross-validation (plspm_cv_device): reps * k records stay on the handle, record r * k + f =
+        the fit on the rows outside fold f of repetition rep_offset + r.  ``fold`` [reps, N] uint8: explicit fold ids instead of the on-device
+        draw (tests)."""
+        if fold is not None:
+            fold = np.ascontiguousarray(fold, dtype=np.uint8)
+            if fold.shape != (reps, self.N):
+                raise ValueError("fold must have shape (reps, N)")
+        d_out, d_st, d_it = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.plspm_cv_device(self._h, reps, k, seed, rep_offset, _ptr(fold), ctypes.byref(d_out), ctypes.byref(d_st), ctypes.byref(d_it)),
+                    "plspm_cv_device")
+        self.last_B = reps * k
+        return d_out.value, d_st.value, d_it.value
+
+    def cv_fold_ids(self, reps, k):
+        """What the last ``cv`` call left on the handle (plspm_cv_fold_ids): (fold [reps, N] uint8, order [reps, N] int32, offsets [reps, k + 1] int32)."""
+        fold = np.empty((reps, self.N), dtype=np.uint8)
+        order = np.empty((reps, self.N), dtype=np.int32)
+        offsets = np.empty((reps, k + 1), dtype=np.int32)
+        self._check(self._lib.plspm_cv_fold_ids(self._h, reps, k, _ptr(fold), _ptr(order), _ptr(offsets)), "plspm_cv_fold_ids")
+        return fold, order, offsets
+
+    def cv_moments(self, reps, k, cross=True):
+        """Training moments of the last ``cv`` call's problems (plspm_cv_moments): (n_train [reps * k], mean [reps * k, P] of the raw columns,
+        cross [reps * k, P (P + 1) / 2] centred cross-products, upper triangle by rows -- or None)."""
+        nprob, P = reps * k, self.P
+        n_train, mean = np.empty(nprob), np.empty((nprob, P))
+        packed = np.empty((nprob, P * (P + 1) // 2)) if cross else None
+        self._check(self._lib.plspm_cv_moments(self._h, reps, k, _ptr(n_train), _ptr(mean), _ptr(packed)), "plspm_cv_moments")
+        return n_train, mean, packed
+
+    def cv_targets(self):
+        """Device columns of the target indicators (plspm_cv_targets): the MVs of every LV that has a predecessor."""
+        cols = np.empty(self.P, dtype=np.int32)
+        return cols[:self._lib.plspm_cv_targets(self._h, _ptr(cols))].copy()
+
+    def cv_predict(self, reps, k, technique=0, coef=None, predictions=False):
+        """Out-of-sample errors of the last ``cv`` call's problems (plspm_cv_predict): (sse, sae, sst [reps * k, T], rows [reps * k], pred_sum [N, T]
+        or None, pred_cnt [N] or None).  ``coef`` [reps * k, T, P + 1]: explicit affine maps of the raw row instead of the PLS prediction."""
+        nprob, T = reps * k, len(self.cv_targets())
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, dtype=np.float64)
+            if coef.shape != (nprob, T, self.P + 1):
+                raise ValueError("coef must have shape (reps * k, T, P + 1)")
+        sse, sae, sst = np.empty((nprob, T)), np.empty((nprob, T)), np.empty((nprob, T))
+        rows = np.empty(nprob, dtype=np.int64)
+        pred_sum = np.empty((self.N, T)) if predictions else None
+        pred_cnt = np.empty(self.N, dtype=np.int32) if predictions else None
+        self._check(self._lib.plspm_cv_predict(self._h, reps, k, int(technique), _ptr(coef), _ptr(sse), _ptr(sae), _ptr(sst), _ptr(rows), _ptr(pred_sum),
+                                               _ptr(pred_cnt)), "plspm_cv_predict")
+        return sse, sae, sst, rows, pred_sum, pred_cnt
 
     def summary(self, B, original, d_rows=None, stride=0):
         """Device-side _create_summary of the last bootstrap on this handle (or of the device records at ``d_rows``).
