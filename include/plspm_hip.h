@@ -450,6 +450,50 @@ int plspm_cv_predict(plspm_model_t* m, int64_t reps, int32_t k, int32_t techniqu
                      int64_t* rows, double* pred_sum, int32_t* pred_cnt);
 
 /*
+ * ---- Jackknife (delete-one / delete-a-group) ------------------------------------------------------------------------------------
+ * Problem g of G (2 <= G <= N) is the model estimated on the rows i with i % G != g: G = N is the ordinary leave-one-out jackknife, G < N the
+ * delete-a-group jackknife (group sizes differ by at most one; every problem keeps at least four rows, else PLSPM_E_ARG).  Problems are estimated
+ * like bootstrap replicates (same record layout; each problem's own n, treatment and `scaled` scalar from its moments) on the int8 Gram route with
+ * at least seven digit planes whatever "gram_path" / "i8_min_batch" say; the floor belongs to this call (a later bootstrap keeps its own planes).
+ * Plain metric handles only (no non-metric scales, no missing values, not part of a two-stage pair): PLSPM_E_ARG otherwise; PLSPM_E_LIMIT where
+ * the int8 route is closed (N >= 2^24, digit planes above their budget).
+ *
+ * plspm_jackknife_device: enqueues the G problems.  Their records, status and iteration counts live in buffers of their own: the records of the
+ *   handle's last bootstrap-like call (plspm_bootstrap_fetch / _summary / _intervals), its status and its iteration counts are untouched, bit
+ *   for bit.  *d_out [G * plspm_row_stride()] / *d_status / *d_iters [G]: device pointers owned by the handle, valid until the next
+ *   plspm_jackknife_device or upload (any may be NULL).
+ * plspm_jackknife_fetch: host copy of problems [first, first + count) of the last plspm_jackknife_device call: out [count*R], status, iters
+ *   [count] (any may be NULL).  PLSPM_E_STATE without a jackknife on the handle.
+ * plspm_jackknife_stats: per record column over the n problems of status PLSPM_OK (G: the last plspm_jackknife_device call's, else PLSPM_E_ARG;
+ *   PLSPM_E_STATE without one), every sum in one fixed order (bit-reproducible), with d_g = mean - theta_(g):
+ *     mean = sum theta_(g) / n,   std_error = sqrt((n - 1) / n  sum d_g^2),   accel = sum d_g^3 / (6 (sum d_g^2)^1.5)  (NaN where sum d_g^2 = 0)
+ *   mean, std_error, accel [R] host (any may be NULL); *n_used = n (may be NULL); n = 0: every output NaN.
+ */
+int plspm_jackknife_device(plspm_model_t* m, int64_t G, void** d_out, void** d_status, void** d_iters);
+int plspm_jackknife_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status, int32_t* iters);
+int plspm_jackknife_stats(plspm_model_t* m, int64_t G, double* mean, double* std_error, double* accel, int64_t* n_used);
+
+/*
+ * ---- Bootstrap confidence intervals ---------------------------------------------------------------------------------------------
+ * Two-sided intervals at a chosen level on bootstrap records in HBM, every handle kind; d_rows / B / stride as plspm_bootstrap_summary (NULL: the
+ * handle's last records; else a device buffer in the record layout, e.g. the gathered records of all GPUs).  Per result column c over the m
+ * replicates of status PLSPM_OK:  out[c*6 + 0..5] = lower, upper, z0, accel, level.lower, level.upper.
+ * With alpha = (1 - level) / 2 and 1 - alpha = (1 + level) / 2, both rounded to twelve decimals (level 0.95 gives exactly 0.025 and 0.975), q(p) the
+ * quantile by numpy's linear interpolation at position p (m - 1) -- plspm_bootstrap_summary's rule --, theta the column's `original`:
+ *   method 0 percentile  lower = q(alpha), upper = q(1 - alpha)          (level 0.95: perc.025 / perc.975 of the summary, bit for bit)
+ *          1 basic       lower = 2 theta - q(1 - alpha), upper = 2 theta - q(alpha)
+ *          2 bc          as bca with a = 0
+ *          3 bca         z0 = Phi^-1(#{theta* < theta} / m) (strict inequality); lower = q(p_lo), upper = q(p_hi),
+ *                        p = Phi(z0 + (z0 + z) / (1 - a (z0 + z))) for z = Phi^-1(alpha), Phi^-1(1 - alpha); a = accel[c] (plspm_jackknife_stats)
+ * level.lower / level.upper: the two levels the quantiles were taken at.  z0 is reported by every method; accel is NaN for methods 0 and 1, 0 for 2.
+ * NaN: all six where m = 0 or original[c] is NaN; lower, upper and both levels of bc / bca where the proportion is 0 or 1 (z0 is -inf / +inf there:
+ * constant columns such as absent paths); lower, upper, accel and both levels of bca where accel[c] is NaN.
+ *   original [R] host;  accel [R] host, NULL unless method 3 (then PLSPM_E_ARG);  0 < level < 1;  out [R*6] host;  n_used: m (may be NULL)
+ */
+int plspm_bootstrap_intervals(plspm_model_t* m, const void* d_rows, int64_t B, int32_t stride, const double* original, const double* accel,
+                              int32_t method, double level, double* out, int64_t* n_used);
+
+/*
  * ---- Multi-GPU: replicate shards + ONE RCCL all-gather --------------------------------------------------------------------------
  * Reference: Bootstrap.__init__ forks `processes` workers, each running iterations / processes replicates, and merges their
  * frames through a Queue (plspm/bootstrap.py:89-111; `processes` kwarg plspm/plspm.py:35-37,60-61).  Here a GROUP of handles --

@@ -144,3 +144,9 @@ int launch_strat_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int K
 struct CvSpec { int64_t reps; int k; const uint8_t* d_fold; };
 // run_gram_i8 on a cross-validation call (m->cv set): the 0/1 counts of problems [prob0, prob0 + nb) into `cd`, layout of resample_i8_kernel
 int launch_cv_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
+
+// ---- plspm_jackknife.hip (delete-one / delete-a-group jackknife)
+// One call's problems: problem g of G leaves out the rows i with i % G == g.
+struct JackSpec { int64_t G; };
+// run_gram_i8 on a jackknife call (m->jack set): the 0/1 counts of problems [prob0, prob0 + nb) into `cd`, layout of resample_i8_kernel
+int launch_jack_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);

@@ -33,6 +33,7 @@ struct PermSpec;
 struct StratSpec;
 // Fold spec of a cross-validation call (plspm_cv.hip) while plspm_detail_bootstrap runs it.
 struct CvSpec;
+struct JackSpec;
 
 struct ProfSlot { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, pool; double total_ms = 0.0; int64_t launches = 0; };
 
@@ -143,6 +144,9 @@ struct plspm_model {
     const CvSpec* cv = nullptr;              // plspm_cv_device: problem r * k + f is the training set of fold f of repetition r (int8 route, 0/1 counts)
     Buf cv_fold, cv_thr, cv_idx, cv_off, cv_mom, cv_coef, cv_io, cv_pred, cv_tab;      // ... fold ids, thresholds, rows in fold order + offsets, training moments, coefficient matrices, error sums, predictions, small tables
     int64_t cv_reps = 0; int cv_k = 0;       // ... the last plspm_cv_device call whose folds, moments and records are on the handle (0: none)
+    const JackSpec* jack = nullptr;          // plspm_jackknife_device: problem g leaves out the rows i with i % G == g (int8 route, 0/1 counts)
+    Buf jack_rows, jack_status, jack_iters, jack_io;      // ... its records, status and iteration counts (buffers of their own: the bootstrap's survive the call), the statistics' out block
+    int64_t jack_G = 0;                      // ... the last plspm_jackknife_device call whose records are on the handle (0: none)
     int last_gram_path = 0;       // 1 fp64 MFMA, 2 int8 digit planes: what the last bootstrap call used (plspm_model_get_info)
     int last_i8_dma = 0;          // 1 global_load_lds, 2 buffer_load ... lds: the LDS-DMA form of the last int8 Gram launch
     int last_i8_persist = 0;      // 1: ... as one persistent workgroup per CU (gram_i8pp_kernel)
@@ -181,6 +185,9 @@ void plspm_detail_group_orphan(void* group);
 int plspm_detail_h2d(plspm_model* m, void* dst, const void* src, size_t bytes);
 // Summary statistics of device records (plspm_bootstrap_summary without the argument checks on `rows`).
 int plspm_detail_summary(plspm_model* m, const double* rows, int64_t B, int32_t stride, const double* original, double* summary, int64_t* n_used);
+// Confidence intervals of device records (plspm_bootstrap_intervals without the argument checks on `rows`).
+int plspm_detail_intervals(plspm_model* m, const double* rows, int64_t B, int32_t stride, const double* original, const double* accel, int32_t method, double level, double* out,
+                           int64_t* n_used);
 // Host copy of device records [B x stride] -> rows [B x R], status, iters (any may be NULL), through the pinned staging buffer.
 int plspm_detail_fetch_records(plspm_model* m, const double* d_records, int64_t B, int32_t stride, double* out, int32_t* status, int32_t* iters);
 

@@ -1,11 +1,12 @@
 // plspm_bootstrap.hip -- host side, part 4: the bootstrap driver (resample -> Gram -> solver per chunk of replicates), its C-ABI entry points,
-// the record download and the device summaries.  Kernels: kernels_resample.h, kernels_summary.h.
+// the record download, the device summaries and the confidence intervals.  Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h.
 #include "host_internal.h"
 
 #include "philox.h"
 #include "wave_ops.h"
 #include "kernels_resample.h"
 #include "kernels_summary.h"
+#include "kernels_intervals.h"
 
 // dense [C x C] symmetric moment matrix of every replicate out of the tile-packed one (plspm_bootstrap_moments)
 __global__ void __launch_bounds__(256) moments_unpack_kernel(const double* __restrict__ gram, long psize, int T, int C, double* __restrict__ out) {
@@ -28,8 +29,8 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     // non-metric models on the int8 route with Philox draws (round 3): the dense stop-rule pass reads its row multiplicities from the int8
     // counts the Gram consumed -- no second resample kernel, no (row,count) lists, no uint16 histograms (set_option "nm_counts8" 0: the
     // round-2 path, kept for A/B and for the cases below)
-    // (a two-group permutation call, plspm_permute.hip, always takes the int8 route: its caller checked that the route is open; so does a cross-validation call, plspm_cv.hip)
-    const int gpath_plan = (m->perm || m->strat || m->cv) ? 2 : choose_gram_path(m, B);
+    // (a two-group permutation call, plspm_permute.hip, always takes the int8 route: its caller checked that the route is open; so do a cross-validation call, plspm_cv.hip, and a jackknife call, plspm_jackknife.hip)
+    const int gpath_plan = (m->perm || m->strat || m->cv || m->jack) ? 2 : choose_gram_path(m, B);
     // (explicit index lists of at most 65,535 rows keep the round-3 arrangement -- uint16 histograms beside the lists they need anyway; beyond
     //  one window the int8 counts are the only dense multiplicities there are)
     const bool counts8_plan = gpath_plan == 2 && (!d_idx || !lds_hist) && nm_counts8_possible(m);
@@ -62,21 +63,24 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     if (gpath == 2 && chunk < B) chunk = std::max<int64_t>(256, chunk & ~(int64_t)255);      // whole 256-replicate tiles per pass
     int rc;
     if (gpath == 2) {
-        if ((rc = prepare_zs(m, (m->perm || m->strat || m->cv) ? 7 : 0))) return rc;      // (a permutation / stratified / cross-validation call: seven planes at least, plspm_permute.hip, plspm_cv.hip)
+        if ((rc = prepare_zs(m, (m->perm || m->strat || m->cv || m->jack) ? 7 : 0))) return rc;      // (a permutation / stratified / cross-validation / jackknife call: seven planes at least, plspm_permute.hip, plspm_cv.hip, plspm_jackknife.hip)
     }
     if (need_lists) {
         if ((rc = ensure(m, m->ent, (size_t)chunk * ent_stride * sizeof(int2)))) return rc;
         if ((rc = ensure(m, m->nent, (size_t)chunk * sizeof(int)))) return rc;
     }
     if ((rc = ensure(m, m->gram, (size_t)chunk * std::max<long>(psize, (rows_solver || nm_wave) ? cov_doubles(m->Pg) : 0) * sizeof(double)))) return rc;
-    if (!m->cv) m->cv_reps = 0;      // (the records of a cross-validation call are about to be replaced, or its status / iteration buffers reused)
+    // (a jackknife call writes records, status and iteration counts into buffers of its own: whatever the handle holds survives it)
+    if (!m->cv && !m->jack) m->cv_reps = 0;      // (the records of a cross-validation call are about to be replaced, or its status / iteration buffers reused)
     if (!rows_out) {
         m->rows_B = 0;
         if ((rc = ensure(m, m->rows, (size_t)B * R * sizeof(double)))) return rc;
         rows_out = (double*)m->rows.p;
     }
-    if ((rc = ensure(m, m->status, (size_t)B * sizeof(int)))) return rc;
-    if ((rc = ensure(m, m->iters, (size_t)B * sizeof(int)))) return rc;
+    plspm_model::Buf& status_buf = m->jack ? m->jack_status : m->status;
+    plspm_model::Buf& iters_buf = m->jack ? m->jack_iters : m->iters;
+    if ((rc = ensure(m, status_buf, (size_t)B * sizeof(int)))) return rc;
+    if ((rc = ensure(m, iters_buf, (size_t)B * sizeof(int)))) return rc;
     const void* err_before = m->err.p;
     if ((rc = ensure(m, m->err, sizeof(int)))) return rc;
     if (m->err.p != err_before) m->err_clean = false;
@@ -135,7 +139,7 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
             continue;
         }
         SolverOut so{};
-        so.row = rows_out + b0 * R; so.row_stride = R; so.status = (int*)m->status.p + b0; so.iters = (int*)m->iters.p + b0;
+        so.row = rows_out + b0 * R; so.row_stride = R; so.status = (int*)status_buf.p + b0; so.iters = (int*)iters_buf.p + b0;
         const bool lists = need_lists && !cd8;                         // (built above only when the int8 counts are not used)
         const int2* ent_l = lists ? (const int2*)m->ent.p : nullptr;
         const int* nent_l = lists ? (const int*)m->nent.p : nullptr;
@@ -287,6 +291,23 @@ int plspm_bootstrap_summary(plspm_model_t* m, const void* d_rows, int64_t B, int
         stride = plspm_row_stride(m);
     }
     return plspm_detail_summary(m, rows, B, stride, original, summary, n_used);
+}
+
+int plspm_bootstrap_intervals(plspm_model_t* m, const void* d_rows, int64_t B, int32_t stride, const double* original, const double* accel, int32_t method, double level,
+                              double* out, int64_t* n_used) {
+    if (!m || !original || !out || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: bad arguments (1 <= B <= 2^30)");
+    if (method < CI_PERCENTILE || method > CI_BCA) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: method must be 0 (percentile), 1 (basic), 2 (bc) or 3 (bca)");
+    if (!(level > 0.0 && level < 1.0)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: level must lie strictly between 0 and 1");
+    if (method == CI_BCA && !accel) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: the bca method needs the acceleration of every column (plspm_jackknife_stats)");
+    const double* rows = (const double*)d_rows;
+    if (!rows) {
+        // the handle's own records, as plspm_bootstrap_summary takes them
+        if (!m->rows_B || !m->rows.p) return fail(m, PLSPM_E_STATE, "plspm_bootstrap_intervals: no bootstrap result on this handle");
+        if (B != m->rows_B) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: B differs from the last bootstrap on this handle");
+        rows = (const double*)m->rows.p;
+        stride = plspm_row_stride(m);
+    }
+    return plspm_detail_intervals(m, rows, B, stride, original, accel, method, level, out, n_used);
 }
 
 }  // extern "C"
@@ -463,6 +484,53 @@ int plspm_detail_summary(plspm_model* m, const double* rows, int64_t B, int32_t 
         fprintf(stderr, "[plspm summary clocks] compaction %lld  mean+var %lld  select %lld  successors %lld  total %lld\n", h[1] - h[0], h[2] - h[1], h[3] - h[2], h[4] - h[3], h[4] - h[0]);
     }
 #endif
+    return 0;
+}
+
+// The nominal levels of a two-sided interval, alpha = (1 - level) / 2 and 1 - alpha = (1 + level) / 2, rounded to twelve decimals: 1 - 0.95 is not 0.05 in
+// binary, and the percentile interval at level 0.95 has to interpolate at exactly the summary's 0.025 and 0.975 (plspm.bootstrap._ci_levels is the same rule).
+static void ci_levels(double level, double* lo, double* hi) {
+    *lo = nearbyint((1.0 - level) * 0.5 * 1e12) / 1e12;
+    *hi = nearbyint((1.0 + level) * 0.5 * 1e12) / 1e12;
+}
+
+int plspm_detail_intervals(plspm_model* m, const double* rows, int64_t B, int32_t stride, const double* original, const double* accel, int32_t method, double level, double* out,
+                           int64_t* n_used) {
+    HIPCHK(m, hipSetDevice(m->device));
+    const int R = plspm_row_width(m);
+    if (stride < R + 1) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: stride must cover the status column");
+    const int npad = (int)((B + 1) & ~(int64_t)1);
+    const bool in_lds = npad <= CI_LDS_VALUES;
+    int rc;
+    if ((rc = pin_ready(m))) return rc;
+    if ((size_t)R * 8 * sizeof(double) + 64 > m->h_pin_cap) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: record too wide for the staging area");
+    if (!in_lds && (rc = ensure(m, m->sum_buf, (size_t)R * npad * sizeof(double)))) return rc;
+    // [original R | accel R | intervals 6R | n_used] in the handle's pinned staging area, read and written by the kernel itself (plspm_detail_summary)
+    double* h_io = (double*)m->h_pin;
+    memcpy(h_io, original, sizeof(double) * R);
+    if (accel) memcpy(h_io + R, accel, sizeof(double) * R);
+    const long cols_ld = (long)((B + 63) & ~(int64_t)63);
+    if ((rc = ensure(m, m->cols, (size_t)(R + 1) * cols_ld * sizeof(double)))) return rc;
+    const double* cols = (const double*)m->cols.p;
+    hipLaunchKernelGGL(records_transpose_kernel, dim3((unsigned)((B + 63) / 64), (unsigned)((R + 1 + 63) / 64)), dim3(256), 0, m->stream, rows, (long)B, (int)stride, R + 1, (double*)m->cols.p,
+                       cols_ld);
+    double* h_out = h_io + 2 * (size_t)R;
+    int* h_used = (int*)(h_out + (size_t)R * 6);
+    double a_lo, a_hi;
+    ci_levels(level, &a_lo, &a_hi);
+    if (in_lds) {
+        const size_t lds = (size_t)npad * sizeof(double);
+        if ((rc = allow_lds(m, (const void*)intervals_kernel<true>, lds))) return rc;
+        hipLaunchKernelGGL((intervals_kernel<true>), dim3(R), dim3(SUM_NT), lds, m->stream, cols, cols_ld, (long)B, R, (const double*)h_io, (const double*)(h_io + R), (int)method, a_lo, a_hi,
+                           (double*)nullptr, npad, h_out, h_used);
+    } else {
+        hipLaunchKernelGGL((intervals_kernel<false>), dim3(R), dim3(SUM_NT), 0, m->stream, cols, cols_ld, (long)B, R, (const double*)h_io, (const double*)(h_io + R), (int)method, a_lo, a_hi,
+                           (double*)m->sum_buf.p, npad, h_out, h_used);
+    }
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    memcpy(out, h_out, sizeof(double) * R * 6);
+    if (n_used) *n_used = *(const int*)h_used;
     return 0;
 }
 

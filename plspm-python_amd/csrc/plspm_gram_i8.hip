@@ -336,7 +336,7 @@ int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const i
     plspm_model::Buf& cd = slot ? m->cd1 : m->cd;
     const size_t cd_bytes = (size_t)MT * 16 * ((size_t)KB + I8_SLACK_KB) * 64;
     if (cd_bytes > cd.cap) { if (m->aux) HIPCHK(m, hipStreamSynchronize(m->aux)); if ((rc = ensure(m, cd, cd_bytes))) return rc; m->cdfree_set[slot] = false; }
-    if (!d_idx && !m->perm && !m->strat && !m->cv && m->aux) {
+    if (!d_idx && !m->perm && !m->strat && !m->cv && !m->jack && m->aux) {
         // Philox draws: on the low-priority stream, as soon as the Gram that last read this buffer is done -- i.e. beside the Gram and the
         // solver of the PREVIOUS call when the host runs ahead; this call's Gram waits for the counts by event
         if (m->cdfree_set[slot]) HIPCHK(m, hipStreamWaitEvent(m->aux, m->ev_cdfree[slot], 0));
@@ -355,6 +355,7 @@ int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const i
         if (m->perm) { if ((rc = launch_perm_counts(m, nb, rep0, MT, KB, cd.p))) return rc; }      // (two-group permutation test: 0/1 counts of random splits, plspm_permute.hip)
         else if (m->strat) { if ((rc = launch_strat_counts(m, nb, rep0, MT, KB, cd.p))) return rc; }      // (... its stratified bootstrap: draws inside each group)
         else if (m->cv) { if ((rc = launch_cv_counts(m, nb, rep0, MT, KB, cd.p))) return rc; }      // (cross-validation: 0/1 counts of the training folds, plspm_cv.hip)
+        else if (m->jack) { if ((rc = launch_jack_counts(m, nb, rep0, MT, KB, cd.p))) return rc; }      // (jackknife: 0/1 counts of the rows a problem keeps, plspm_jackknife.hip)
         else
         if (hist_nib) hipLaunchKernelGGL(resample_i8_nib_kernel, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->stream, (int)m->N, KB, MT, seed, rep0, (uint4*)cd.p, (int*)m->err.p, nib_slow);
         else

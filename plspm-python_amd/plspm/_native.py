@@ -29,7 +29,10 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_comm_create_ex", "plspm_comm_split", "plspm_comm_transport", "plspm_comm_max_channels", "plspm_group_set_option", "plspm_group_plan", "plspm_chunk_plan",
            "plspm_permutation_device", "plspm_permutation_counts", "plspm_permutation_members",
            "plspm_stratified_bootstrap_device", "plspm_stratified_pair_counts", "plspm_stratified_draws",
-           "plspm_cv_folds", "plspm_cv_device", "plspm_cv_fold_ids", "plspm_cv_moments", "plspm_cv_targets", "plspm_cv_predict"]
+           "plspm_cv_folds", "plspm_cv_device", "plspm_cv_fold_ids", "plspm_cv_moments", "plspm_cv_targets", "plspm_cv_predict",
+           "plspm_jackknife_device", "plspm_jackknife_fetch", "plspm_jackknife_stats", "plspm_bootstrap_intervals"]
+CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
+CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
 UNIQUE_ID_BYTES = 128
 
 
@@ -115,6 +118,10 @@ def load():
     lib.plspm_cv_targets.restype = i32
     lib.plspm_cv_targets.argtypes = [vp, vp]
     lib.plspm_cv_predict.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.plspm_jackknife_device.argtypes = [vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.plspm_jackknife_fetch.argtypes = [vp, i64, i64, vp, vp, vp]
+    lib.plspm_jackknife_stats.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    lib.plspm_bootstrap_intervals.argtypes = [vp, vp, i64, i32, vp, vp, i32, dbl, vp, ctypes.POINTER(i64)]
     lib.plspm_profile_enable.argtypes = [vp, i32]
     lib.plspm_profile_read.argtypes = [vp, i32, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
     lib.plspm_profile_reset.argtypes = [vp]
@@ -501,6 +508,51 @@ class NativeModel:
         self._check(self._lib.plspm_cv_predict(self._h, reps, k, int(technique), _ptr(coef), _ptr(sse), _ptr(sae), _ptr(sst), _ptr(rows), _ptr(pred_sum),
                                                _ptr(pred_cnt)), "plspm_cv_predict")
         return sse, sae, sst, rows, pred_sum, pred_cnt
+
+    def jackknife(self, groups=None):
+        """Enqueue the jackknife (plspm_jackknife_device): problem g of ``groups`` (None: N, leave-one-out) is the fit on the rows i with
+        i % groups != g.  Its records live beside the handle's bootstrap records, which survive the call.  Returns the device pointers
+        (rows, status, iters)."""
+        G = self.N if groups is None else int(groups)
+        d_out, d_st, d_it = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.plspm_jackknife_device(self._h, G, ctypes.byref(d_out), ctypes.byref(d_st), ctypes.byref(d_it)), "plspm_jackknife_device")
+        self.last_G = G
+        return d_out.value, d_st.value, d_it.value
+
+    def jackknife_fetch(self, first=0, count=None):
+        """Host copy of problems [first, first + count) of the last ``jackknife`` call: (rows [count, R], status, iters)."""
+        if count is None:
+            count = getattr(self, "last_G", 0) - first
+        rows = np.empty((max(count, 0), self.row_width))
+        status = np.empty(max(count, 0), dtype=np.int32)
+        iters = np.empty(max(count, 0), dtype=np.int32)
+        self._check(self._lib.plspm_jackknife_fetch(self._h, first, count, _ptr(rows), _ptr(status), _ptr(iters)), "plspm_jackknife_fetch")
+        return rows, status, iters
+
+    def jackknife_stats(self, groups=None):
+        """Device reduction of the last ``jackknife`` call (plspm_jackknife_stats): (mean [R], std_error [R], accel [R], number of OK problems)."""
+        G = self.N if groups is None else int(groups)
+        mean, se, accel = np.empty(self.row_width), np.empty(self.row_width), np.empty(self.row_width)
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_jackknife_stats(self._h, G, _ptr(mean), _ptr(se), _ptr(accel), ctypes.byref(used)), "plspm_jackknife_stats")
+        return mean, se, accel, used.value
+
+    def intervals(self, B, original, method="percentile", level=0.95, accel=None, d_rows=None, stride=0):
+        """Device confidence intervals of the last bootstrap on this handle, or of the device records at ``d_rows`` (plspm_bootstrap_intervals).
+        Returns ([R, 6] array: lower, upper, z0, accel, level.lower, level.upper; number of OK replicates)."""
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (self.row_width,):
+            raise ValueError("original must have row_width entries")
+        if accel is not None:
+            accel = np.ascontiguousarray(accel, dtype=np.float64)
+            if accel.shape != (self.row_width,):
+                raise ValueError("accel must have row_width entries")
+        mid = CI_METHODS.index(method) if isinstance(method, str) else int(method)
+        out = np.empty((self.row_width, 6))
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_bootstrap_intervals(self._h, d_rows, B, stride, _ptr(original), _ptr(accel), mid, float(level), _ptr(out), ctypes.byref(used)),
+                    "plspm_bootstrap_intervals")
+        return out, used.value
 
     def summary(self, B, original, d_rows=None, stride=0):
         """Device-side _create_summary of the last bootstrap on this handle (or of the device records at ``d_rows``).
