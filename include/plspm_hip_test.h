@@ -17,6 +17,11 @@ extern "C" {
  *   "i8_short_rows"   -1 (default) | n   n short tile rows behind as many tall ones as it takes (forced cuts of the int8 Gram's tile rows:
  *                     the matrices must be bit-identical for every cut)
  *   "gram_lds_kb"     0 .. 160   pads the dynamic LDS of gram_rows_kernel (occupancy experiments)
+ *   "boot_pass"       0 (default: automatic) | n, a multiple of 256   caps the problems per pass of a batch (bootstrap, permutation, stratified
+ *                     bootstrap, cross-validation, jackknife): the automatic size -- 2 GiB of scratch -- takes millions of rows to reach a second pass.
+ *                     Only ever lowers the automatic size; records, status and iteration counts must be bit-identical for every cut.
+ *   "last_boot_passes"   read-only: the passes the last such batch was cut into (plspm_bootstrap() runs its sub-batches as batches of their own:
+ *                     the last sub-batch's)
  *
  * Experiments build only (make -C plspm-python_amd/csrc experiments, loaded through PLSPM_HIP_LIB; the release library answers PLSPM_E_ARG):
  * "i8_waves" 4 (four-wave forms of the round-3 kernel: measured equal), "i8_shape" 32 (v_mfma_i32_32x32x32_i8 layout: 16 % slower), "i8_sched" 1

@@ -61,6 +61,8 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     //  into passes multiplies that tail: 16 GiB of the 288 for it instead of 2)
     int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(((cat_one ? 16ull : 2ull) << 30) / per_rep)));
     if (gpath == 2 && chunk < B) chunk = std::max<int64_t>(256, chunk & ~(int64_t)255);      // whole 256-replicate tiles per pass
+    if (m->tune.boot_pass > 0 && m->tune.boot_pass < chunk) chunk = m->tune.boot_pass;        // test seam "boot_pass" (a multiple of 256): later passes at test sizes
+    m->last_boot_passes = (int)((B + chunk - 1) / chunk);
     int rc;
     if (gpath == 2) {
         if ((rc = prepare_zs(m, (m->perm || m->strat || m->cv || m->jack) ? 7 : 0))) return rc;      // (a permutation / stratified / cross-validation / jackknife call: seven planes at least, plspm_permute.hip, plspm_cv.hip, plspm_jackknife.hip)

@@ -492,6 +492,7 @@ int plspm_model_set_option(plspm_model_t* m, const char* key, int32_t value) {
     else if (k == "boot_chunks") { if (value < 0 || value > kBootChunksMax) return bad(); m->tune.boot_chunks = value; }
     else if (k == "boot_ratio") { if (value < 10 || value > 100) return bad(); m->tune.boot_ratio = value; }
     else if (k == "boot_align") { if (value < 0 || value > (1 << 20)) return bad(); m->tune.boot_align = value; }
+    else if (k == "boot_pass") { if (value < 0 || value > (1 << 30) || (value & 255)) return bad(); m->tune.boot_pass = value; }      // test seam: cap on the replicates per pass (plspm_detail_bootstrap)
     else return fail(m, PLSPM_E_ARG, "plspm_model_set_option: unknown option '" + k + "'");
     if (m->group) plspm_detail_group_plan_changed(m->group);
     return 0;
@@ -570,6 +571,8 @@ int plspm_model_get_option(const plspm_model_t* m, const char* key, int32_t* val
     else if (k == "boot_ratio") *value = m->tune.boot_ratio;
     else if (k == "boot_align") *value = m->tune.boot_align;
     else if (k == "boot_round_units") *value = (int32_t)plspm_detail_round_units_peek(m);      // (64 until the digit planes of this upload exist: a query builds nothing)
+    else if (k == "boot_pass") *value = m->tune.boot_pass;
+    else if (k == "last_boot_passes") *value = m->last_boot_passes;
     else if (k == "last_gram_path") *value = m->last_gram_path;
     else if (k == "build_experiments") {
 #ifdef PLSPM_I8_EXPERIMENTS

@@ -22,6 +22,20 @@ def cv_folds(seed, rep, n, k):
     return fold
 
 
+def _find_cv_tie(seed, n, reps):
+    """(rep, k, row a, row b): in repetition `rep` the rows a < b share a key, sit at adjacent sorted positions, and with k folds a fold boundary
+    falls between them."""
+    for rep in reps:
+        keys = cv_keys(seed, rep, n)
+        order = np.lexsort((np.arange(n), keys))
+        ks = keys[order]
+        for j in np.flatnonzero(ks[1:] == ks[:-1]):
+            for k in range(2, 257):
+                if (int(j) * k) // n != ((int(j) + 1) * k) // n:
+                    return rep, k, int(order[j]), int(order[j + 1])
+    return None
+
+
 def targets(model):
     """Data columns of the target indicators in device column order: the blocks of every LV that has a predecessor."""
     return np.concatenate([model.blocks[l] for l in range(model.L) if model.C[l].sum() > 0])
@@ -115,3 +129,55 @@ def mean_predictions(problems, n, key="pred"):
             count[p["rows"]] += 1
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(count[:, None] > 0, total / count[:, None], np.nan)
+
+
+# ------------------------------------------------------------------ launch geometry of the prediction kernels, restated (plspm_cv.hip, kernels_cv.h)
+CV_NT = 256                     # threads of a cv_apply_kernel workgroup
+CV_MAX_LDS = 160 * 1024         # LDS a workgroup may take
+CV_CACHE_ROWS = 12288           # up to this many rows cv_threshold_kernel keeps the keys in LDS
+
+
+def cv_apply_lds(P, T, nrg):
+    """Bytes of LDS cv_apply_kernel takes for T targets of P columns with row groups of nrg x 4 rows: the transposed matrix [P + 1][TS], the row tile
+    [P][4 nrg + 2], the targets' means [TS] (doubles), their columns [TS] and the tile's rows [4 nrg] (ints); TS = T rounded up to four."""
+    TS, XS = (T + 3) & ~3, 4 * nrg + 2
+    return ((P + 1) * TS + P * XS + TS) * 8 + (TS + 4 * nrg) * 4
+
+
+def cv_apply_row_groups(P, T):
+    """Row groups per workgroup plspm_cv_predict picks: the first of 16, 8, 4 with a thread per (row group, four targets) whose tile fits the LDS; 0: refused."""
+    for nrg in (16, 8, 4):
+        if (CV_NT // nrg) * 4 >= T and cv_apply_lds(P, T, nrg) <= CV_MAX_LDS:
+            return nrg
+    return 0
+
+
+def synth_sized(n, C, sizes, seed):
+    """orc.synth with a block of sizes[l] indicators for LV l: (X [n, sum(sizes)], blocks)."""
+    full, _ = orc.synth(n, np.asarray(C), max(sizes), seed=seed)
+    m = max(sizes)
+    X = np.column_stack([full[:, l * m:l * m + s] for l, s in enumerate(sizes)])
+    off = np.concatenate(([0], np.cumsum(sizes)))
+    return X, [np.arange(off[l], off[l + 1]) for l in range(len(sizes))]
+
+
+def training_moments_longdouble(Xd, train):
+    """(mean [P], centred cross-products [P, P], population sd [P]) of Xd[train] in extended precision, rounded to fp64 at the end."""
+    assert np.finfo(np.longdouble).eps <= 2.0 ** -63, "np.longdouble is not an extended format on this machine"
+    x = Xd[train].astype(np.longdouble)
+    n = x.shape[0]
+    mean = x.sum(axis=0) / n
+    xc = x - mean
+    cross = np.empty((x.shape[1], x.shape[1]), dtype=np.longdouble)
+    for p in range(x.shape[1]):                                # (a longdouble matmul is not BLAS: column by column keeps the temporaries small)
+        cross[p] = (xc[:, [p]] * xc).sum(axis=0)
+    sd = np.sqrt(np.diag(cross) / n)
+    return mean.astype(np.float64), cross.astype(np.float64), sd.astype(np.float64)
+
+
+def training_moments_two_pass(Xd, train):
+    """The same in plain fp64 NumPy: mean, then the product of the centred rows."""
+    x = Xd[train]
+    mean = x.mean(axis=0)
+    xc = x - mean
+    return mean, xc.T @ xc

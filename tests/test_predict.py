@@ -15,7 +15,7 @@ from plspm.scheme import Scheme
 
 from helpers import SAT_ADD_ORDER, SAT_PREFIX, satisfaction_frame
 from helpers_mga import find_tie, permutation_keys, philox4x32_10
-from helpers_predict import cross_validate, cv_folds, cv_keys, lm_predict, metrics, pls_predict
+from helpers_predict import _find_cv_tie, cross_validate, cv_folds, cv_keys, lm_predict, metrics, pls_predict
 
 
 @pytest.mark.parametrize("seed,rep,n,k", [(0, 0, 250, 10), (7, 3, 250, 7), (7, 4, 251, 2), (0xC0FFEE, 12345, 10000, 10), (2 ** 63 + 5, 2 ** 33 + 1, 10007, 256),
@@ -26,20 +26,6 @@ def test_folds_match_the_numpy_philox_restatement(seed, rep, n, k):
     assert np.array_equal(mine, cv_folds(seed, rep, n, k))
     sizes = np.bincount(mine, minlength=k)
     assert sizes.sum() == n and sizes.min() >= 1 and sizes.max() - sizes.min() <= 1
-
-
-def _find_cv_tie(seed, n, reps):
-    """(rep, k, row a, row b): in repetition `rep` the rows a < b share a key, sit at adjacent sorted positions, and with k folds a fold boundary
-    falls between them."""
-    for rep in reps:
-        keys = cv_keys(seed, rep, n)
-        order = np.lexsort((np.arange(n), keys))
-        ks = keys[order]
-        for j in np.flatnonzero(ks[1:] == ks[:-1]):
-            for k in range(2, 257):
-                if (int(j) * k) // n != ((int(j) + 1) * k) // n:
-                    return rep, k, int(order[j]), int(order[j + 1])
-    return None
 
 
 def test_folds_break_key_ties_by_row():
