@@ -494,6 +494,47 @@ int plspm_bootstrap_intervals(plspm_model_t* m, const void* d_rows, int64_t B, i
                               int32_t method, double level, double* out, int64_t* n_used);
 
 /*
+ * ---- Measurement-model assessment of the bootstrap ------------------------------------------------------------------------------
+ * Reliability and discriminant validity of every replicate, computed on the device from the replicate's moment matrix -- which exists only between the
+ * Gram and the next pass -- and the weights w and loadings lambda of its record (one more kernel behind the solver).  With n, the column
+ * sums and the cross products M of a replicate:  c_pq = M_pq / n - mu_p mu_q,  s_p = sqrt(c_pp),  r_pq = c_pq / (s_p s_q);  v_p = w_p s_p, normalised per
+ * block so that v_b' R_bb v_b = 1 (the `scaled` scalar cancels);  u_p = sum_{q in block(p)} r_pq v_q;  sigma_l = sign(sum_{p in l} u_p lambda_p), +1 for 0.
+ *   per LV l of k items (k = 1: all four are 1)
+ *     alpha   max(0, k / (k - 1) * 2 sum_{i>j} r_ij / sum_ij r_ij)
+ *     rho_a   Mode A: (v'v)^2 v'(R_bb - I)v / ((v'v)^2 - sum v_p^4)  (Dijkstra-Henseler);  Mode B: 1
+ *     rho_c   (sum lambda)^2 / ((sum lambda)^2 + sum (1 - lambda^2))
+ *     ave     sum lambda^2 / k
+ *   per LV pair (i, j), i < j, i-major; npairs = L (L - 1) / 2
+ *     htmt    mean_{p in i, q in j} |r_pq| / sqrt(m_i m_j),  m_l = mean of |r_pq| over p < q in block l (1 for a single item)
+ *     htmt2   the same with geometric means (exp of the mean log; a zero correlation gives 0)
+ *     lv_cor  sigma_i sigma_j v_i' R_ij v_j
+ * Assessment record, width A = 4 L + 3 npairs:  alpha[L] | rho_a[L] | rho_c[L] | ave[L] | htmt[npairs] | htmt2[npairs] | lv_cor[npairs];  device records
+ * carry the replicate's status and iteration count behind it as doubles (pitch A + 2).  A replicate whose status is not PLSPM_OK has NaN in all A values;
+ * IEEE results stand where a formula divides by zero.  Plain metric handles only (no non-metric scales, no missing values, not part of a two-stage pair):
+ * PLSPM_E_ARG otherwise.
+ *
+ * plspm_assess_enable: on != 0: every later plspm_bootstrap / plspm_bootstrap_device call on this handle also writes the assessment records of its
+ *   replicates into a buffer of their own, indexed like the bootstrap's records; the bootstrap's records, status and iteration counts are bit for bit
+ *   what they are without it.  Off (the default): no launch, no allocation.  Permutation, stratified, cross-validation, jackknife and group calls write
+ *   none.
+ * plspm_assess_width: A.
+ * plspm_assess_fit: the full-sample values, out [A]: the same kernel on the moments of all uploaded rows and one solver problem (plspm_fit's); *status (may
+ *   be NULL): that problem's status.  Needs no plspm_assess_enable.
+ * plspm_assess_fetch: host copy of the assessment records [first, first + count) of the last assessed bootstrap: out [count*A], status [count] (may be NULL).
+ * plspm_assess_summary / plspm_assess_intervals: plspm_bootstrap_summary / plspm_bootstrap_intervals on the assessment records (B: the last assessed
+ *   bootstrap's, else PLSPM_E_ARG): original [A] host, summary / out [A*6] host, *n_used (may be NULL).  Methods 0 (percentile), 1 (basic), 2 (bc); 3 (bca)
+ *   is PLSPM_E_ARG: the jackknife writes no assessment records.
+ * PLSPM_E_STATE from the last three without assessment records on the handle (none written yet; an upload, or a later call that replaced the bootstrap's
+ * records, voids them).
+ */
+int plspm_assess_enable(plspm_model_t* m, int32_t on);
+int32_t plspm_assess_width(const plspm_model_t* m);
+int plspm_assess_fit(plspm_model_t* m, double* out, int32_t* status);
+int plspm_assess_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
+int plspm_assess_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
+int plspm_assess_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
+
+/*
  * ---- Multi-GPU: replicate shards + ONE RCCL all-gather --------------------------------------------------------------------------
  * Reference: Bootstrap.__init__ forks `processes` workers, each running iterations / processes replicates, and merges their
  * frames through a Queue (plspm/bootstrap.py:89-111; `processes` kwarg plspm/plspm.py:35-37,60-61).  Here a GROUP of handles --
@@ -623,8 +664,8 @@ int plspm_op_outer_weights_nonmetric(int32_t device_id, int32_t mode, const doub
                                      double correction, double* w, double* Y);
 
 /* Kernel timing with HIP events on the handle's own stream (for the roofline figures in bench.py).
- * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce. */
-enum { PLSPM_K_RESAMPLE = 0, PLSPM_K_GRAM = 1, PLSPM_K_SOLVER = 2, PLSPM_K_SCORES = 3, PLSPM_K_PACK = 4, PLSPM_K_REDUCE = 5, PLSPM_K_COUNT = 6 };
+ * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce, 6 assessment. */
+enum { PLSPM_K_RESAMPLE = 0, PLSPM_K_GRAM = 1, PLSPM_K_SOLVER = 2, PLSPM_K_SCORES = 3, PLSPM_K_PACK = 4, PLSPM_K_REDUCE = 5, PLSPM_K_ASSESS = 6, PLSPM_K_COUNT = 7 };
 /* on: 0 off, 1 every kernel, 2 + id only kernel `id` (an event pair costs dispatch latency on both sides: bracketing one kernel of a
  * step perturbs the step less than bracketing all of them). */
 int plspm_profile_enable(plspm_model_t* m, int32_t on);

@@ -147,6 +147,12 @@ struct plspm_model {
     const JackSpec* jack = nullptr;          // plspm_jackknife_device: problem g leaves out the rows i with i % G == g (int8 route, 0/1 counts)
     Buf jack_rows, jack_status, jack_iters, jack_io;      // ... its records, status and iteration counts (buffers of their own: the bootstrap's survive the call), the statistics' out block
     int64_t jack_G = 0;                      // ... the last plspm_jackknife_device call whose records are on the handle (0: none)
+    // measurement-model assessment of a plain bootstrap's replicates (kernels_assess.h; plspm_assess_*): records [assess_B x (A + 2)] in a buffer of their own,
+    // indexed by the replicate's position in the whole call
+    bool assess_on = false;                  // plspm_assess_enable
+    Buf assess_rows, assess_fit;             // ... the replicates' records; the full-sample record + its solver problem (plspm_assess_fit)
+    int64_t assess_B = 0;                    // ... the last plain bootstrap whose assessment records are on the handle (0: none)
+    int64_t assess_off = -1;                 // ... >= 0 while plspm_bootstrap() runs a sub-batch: its first replicate's position in the call (the buffer is the caller's to size)
     int last_gram_path = 0;       // 1 fp64 MFMA, 2 int8 digit planes: what the last bootstrap call used (plspm_model_get_info)
     int last_boot_passes = 0;     // passes the last plspm_detail_bootstrap batch was cut into (read-only option "last_boot_passes")
     int last_i8_dma = 0;          // 1 global_load_lds, 2 buffer_load ... lds: the LDS-DMA form of the last int8 Gram launch
@@ -184,10 +190,11 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
 void plspm_detail_group_orphan(void* group);
 // Host -> device copy through the handle's pinned staging halves (chunked; returns when the source may be re-used).
 int plspm_detail_h2d(plspm_model* m, void* dst, const void* src, size_t bytes);
-// Summary statistics of device records (plspm_bootstrap_summary without the argument checks on `rows`).
-int plspm_detail_summary(plspm_model* m, const double* rows, int64_t B, int32_t stride, const double* original, double* summary, int64_t* n_used);
+// Summary statistics of device records (plspm_bootstrap_summary without the argument checks on `rows`): `ncols` value columns, the status in column `ncols`
+// (bootstrap records: plspm_row_width; assessment records: plspm_assess_width).
+int plspm_detail_summary(plspm_model* m, const double* rows, int64_t B, int32_t stride, int32_t ncols, const double* original, double* summary, int64_t* n_used);
 // Confidence intervals of device records (plspm_bootstrap_intervals without the argument checks on `rows`).
-int plspm_detail_intervals(plspm_model* m, const double* rows, int64_t B, int32_t stride, const double* original, const double* accel, int32_t method, double level, double* out,
+int plspm_detail_intervals(plspm_model* m, const double* rows, int64_t B, int32_t stride, int32_t ncols, const double* original, const double* accel, int32_t method, double level, double* out,
                            int64_t* n_used);
 // Host copy of device records [B x stride] -> rows [B x R], status, iters (any may be NULL), through the pinned staging buffer.
 int plspm_detail_fetch_records(plspm_model* m, const double* d_records, int64_t B, int32_t stride, double* out, int32_t* status, int32_t* iters);

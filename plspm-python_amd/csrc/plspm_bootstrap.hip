@@ -1,5 +1,6 @@
 // plspm_bootstrap.hip -- host side, part 4: the bootstrap driver (resample -> Gram -> solver per chunk of replicates), its C-ABI entry points,
-// the record download, the device summaries and the confidence intervals.  Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h.
+// the record download, the device summaries and the confidence intervals, and the measurement-model assessment of the replicates (plspm_assess_*).
+// Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h, kernels_assess.h.
 #include "host_internal.h"
 
 #include "philox.h"
@@ -7,12 +8,47 @@
 #include "kernels_resample.h"
 #include "kernels_summary.h"
 #include "kernels_intervals.h"
+#include "kernels_assess.h"
 
 // dense [C x C] symmetric moment matrix of every replicate out of the tile-packed one (plspm_bootstrap_moments)
 __global__ void __launch_bounds__(256) moments_unpack_kernel(const double* __restrict__ gram, long psize, int T, int C, double* __restrict__ out) {
     const double* g = gram + (long)blockIdx.x * psize;
     double* o = out + (long)blockIdx.x * C * C;
     for (int e = threadIdx.x; e < C * C; e += 256) { const int p = e / C, q = e - p * C; o[e] = g[packed_index(T, p, q)]; }
+}
+
+static inline int assess_width(const plspm_model* m) { return 4 * m->L + 3 * (m->L * (m->L - 1) / 2); }
+// the handle kinds the assessment covers: plain metric (as the two-group tests, the cross-validation and the jackknife)
+static inline bool assess_covers(const plspm_model* m) { return !m->nonmetric && !m->categorical && !m->n_ind && !m->nmx_K && !m->stage1 && !m->stage2; }
+
+// Assessment records of `nb` problems: their moment matrices at `gram` (dense: [(P+1) x cov_ld(P)] upper triangles; else tile-packed), their records at `rows`
+// (row_stride 0: one problem) -> out [nb x (A + 2)].  One wave per problem, four per workgroup (kernels_assess.h).
+static int launch_assess(plspm_model* m, long nb, bool dense, const double* gram, const double* rows, long row_stride, double* out) {
+    const size_t lds = (size_t)ASSESS_WAVES * assess_wave_doubles(m->P, m->L) * sizeof(double);
+    auto k = dense ? assess_kernel<true> : assess_kernel<false>;
+    if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
+    AssessArgs a{};
+    a.gram = gram; a.gstride = dense ? cov_doubles(m->P) : packed_size(m->T); a.ld = dense ? cov_ld(m->P) : m->T;
+    a.P = m->P; a.L = m->L; a.R = plspm_row_width(m);
+    a.boff = m->d_boff; a.lvof = m->d_lvof; a.mode = m->d_mode;
+    a.rows = rows; a.row_stride = row_stride; a.out = out; a.nb = nb;
+#ifdef PLSPM_DEBUG_MARKS      // phase clocks of one problem (make marks); never in the release library
+    HIPCHK(m, plspm_dmalloc((void**)&a.marks, 4 * sizeof(long long)));
+#endif
+    {
+        ProfScope ps(m, PLSPM_K_ASSESS);
+        hipLaunchKernelGGL(k, dim3((unsigned)((nb + ASSESS_WAVES - 1) / ASSESS_WAVES)), dim3(64 * ASSESS_WAVES), lds, m->stream, a);
+    }
+#ifdef PLSPM_DEBUG_MARKS
+    {
+        long long h[4];
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        HIPCHK(m, hipMemcpy(h, a.marks, sizeof(h), hipMemcpyDeviceToHost));
+        fprintf(stderr, "[plspm assess clocks] per-MV values %lld  diagonal blocks %lld  block pairs %lld  total %lld\n", h[1] - h[0], h[2] - h[1], h[3] - h[2], h[3] - h[0]);
+        plspm_dfree(a.marks);
+    }
+#endif
+    return 0;
 }
 
 int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep_offset, const int32_t* d_idx, double* rows_out) {
@@ -74,6 +110,15 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     if ((rc = ensure(m, m->gram, (size_t)chunk * std::max<long>(psize, (rows_solver || nm_wave) ? cov_doubles(m->Pg) : 0) * sizeof(double)))) return rc;
     // (a jackknife call writes records, status and iteration counts into buffers of its own: whatever the handle holds survives it)
     if (!m->cv && !m->jack) m->cv_reps = 0;      // (the records of a cross-validation call are about to be replaced, or its status / iteration buffers reused)
+    // Assessment records (plspm_assess_enable) of a plain bootstrap: a call of its own (rows_out null) sizes the buffer and starts at record 0; a sub-batch of
+    // plspm_bootstrap() writes from its position in that call (m->assess_off; the buffer is plspm_bootstrap's).  Any other owner of the records (a group's
+    // shard) gets none.  Whatever replaces the handle's bootstrap records voids the assessment records that went with them.
+    const bool assess = m->assess_on && assess_covers(m) && !m->perm && !m->strat && !m->cv && !m->jack && !m->moments_out && (!rows_out || m->assess_off >= 0);
+    const bool assess_own = !rows_out;
+    const int64_t assess_base = assess_own ? 0 : m->assess_off;
+    const int AS = assess_width(m) + 2;
+    if (!m->jack && m->assess_off <= 0) m->assess_B = 0;
+    if (assess && assess_own && (rc = ensure(m, m->assess_rows, (size_t)B * AS * sizeof(double)))) return rc;
     if (!rows_out) {
         m->rows_B = 0;
         if ((rc = ensure(m, m->rows, (size_t)B * R * sizeof(double)))) return rc;
@@ -171,9 +216,12 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
             continue;
         }
         if ((rc = launch_batch_solver(m, nb, (rows_solver && !f64_gram) ? route : ROUTE_LDS, so))) return rc;
+        // the chunk's moment matrices are still in m->gram: dense where a dense solver read them, tile-packed for the LDS solver (fp64 Gram, int8 chunks that fell back)
+        if (assess && (rc = launch_assess(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, (double*)m->assess_rows.p + (assess_base + b0) * AS))) return rc;
     }
     HIPCHK(m, hipGetLastError());
     if (rows_out == (double*)m->rows.p) m->rows_B = B;
+    if (assess && assess_own) m->assess_B = B;
     return 0;
 }
 // (m->stop_event: only the last chunk's solver launch may take it -- plspm_detail_bootstrap parks it while earlier chunks run)
@@ -226,12 +274,19 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     m->rows_B = 0;
     if ((rc = ensure(m, m->rows, (size_t)B * RS * sizeof(double)))) return rc;
     double* const rows = (double*)m->rows.p;
+    // assessment records follow the sub-batches: one buffer for the whole call, every part writes from its first replicate's position (m->assess_off)
+    const bool assess = m->assess_on && assess_covers(m) && !m->moments_out;
+    m->assess_B = 0;
+    if (assess && (rc = ensure(m, m->assess_rows, (size_t)B * (assess_width(m) + 2) * sizeof(double)))) return rc;
     int* h_err = (int*)m->h_flag + 10;                   // (+8: plspm_bootstrap_fetch, +9: run_gram_i8's look at the multiplicity flag of an explicit index list)
     h_err[0] = h_err[1] = 0;
     FetchSeg segs[kBootChunksMax];
     int64_t b0 = 0;
     for (int k = 0; k < nparts; ++k) {
-        if ((rc = plspm_detail_bootstrap(m, parts[k], seed, rep_offset + b0, d_idx ? d_idx + b0 * m->N : nullptr, rows + b0 * RS))) return rc;
+        if (assess) m->assess_off = b0;
+        rc = plspm_detail_bootstrap(m, parts[k], seed, rep_offset + b0, d_idx ? d_idx + b0 * m->N : nullptr, rows + b0 * RS);
+        m->assess_off = -1;
+        if (rc) return rc;
         if (k == nparts - 1) {
             // ONE error word, read with the last sub-batch: copied behind the last kernel, in front of the event its download waits for
             HIPCHK(m, hipMemcpyAsync(h_err, m->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
@@ -245,6 +300,7 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     if (nparts > 1) HIPCHK(m, hipStreamSynchronize(m->stream));      // (done already: the last download waited for the last kernel; keeps the handle's invariants simple)
     if (rc) return rc;
     m->rows_B = B;
+    if (assess) m->assess_B = B;
     if (h_err[0] & 4) return fail(m, PLSPM_E_STATE, "plspm_bootstrap: the persistent Gram gave up waiting for a partial tile (device shared with a long-running kernel?); set_option i8_sched 0");
     if (h_err[0] & 1) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: resample index outside [0, N)");
     if ((h_err[0] & 2) || h_err[1]) return fail(m, PLSPM_E_LIMIT, "plspm_bootstrap: a resample multiplicity exceeded 127 on the int8 Gram path (set_option gram_path 1)");
@@ -292,7 +348,7 @@ int plspm_bootstrap_summary(plspm_model_t* m, const void* d_rows, int64_t B, int
         rows = (const double*)m->rows.p;
         stride = plspm_row_stride(m);
     }
-    return plspm_detail_summary(m, rows, B, stride, original, summary, n_used);
+    return plspm_detail_summary(m, rows, B, stride, plspm_row_width(m), original, summary, n_used);
 }
 
 int plspm_bootstrap_intervals(plspm_model_t* m, const void* d_rows, int64_t B, int32_t stride, const double* original, const double* accel, int32_t method, double level,
@@ -309,7 +365,7 @@ int plspm_bootstrap_intervals(plspm_model_t* m, const void* d_rows, int64_t B, i
         rows = (const double*)m->rows.p;
         stride = plspm_row_stride(m);
     }
-    return plspm_detail_intervals(m, rows, B, stride, original, accel, method, level, out, n_used);
+    return plspm_detail_intervals(m, rows, B, stride, plspm_row_width(m), original, accel, method, level, out, n_used);
 }
 
 }  // extern "C"
@@ -445,9 +501,9 @@ int plspm_detail_fetch_records(plspm_model* m, const double* d_records, int64_t 
     return fetch_segments(m, m->stream, d_records, stride, &seg, 1, B, out, status, iters);
 }
 
-int plspm_detail_summary(plspm_model* m, const double* rows, int64_t B, int32_t stride, const double* original, double* summary, int64_t* n_used) {
+int plspm_detail_summary(plspm_model* m, const double* rows, int64_t B, int32_t stride, int32_t ncols, const double* original, double* summary, int64_t* n_used) {
     HIPCHK(m, hipSetDevice(m->device));
-    const int R = plspm_row_width(m);
+    const int R = ncols;
     if (stride < R + 1) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_summary: stride must cover the status column");
     const int npad = (int)((B + 1) & ~(int64_t)1);                   // values per column (no padding needed: nothing is sorted)
     const bool in_lds = (size_t)npad * sizeof(double) <= (size_t)128 * 1024;
@@ -496,10 +552,10 @@ static void ci_levels(double level, double* lo, double* hi) {
     *hi = nearbyint((1.0 + level) * 0.5 * 1e12) / 1e12;
 }
 
-int plspm_detail_intervals(plspm_model* m, const double* rows, int64_t B, int32_t stride, const double* original, const double* accel, int32_t method, double level, double* out,
-                           int64_t* n_used) {
+int plspm_detail_intervals(plspm_model* m, const double* rows, int64_t B, int32_t stride, int32_t ncols, const double* original, const double* accel, int32_t method, double level,
+                           double* out, int64_t* n_used) {
     HIPCHK(m, hipSetDevice(m->device));
-    const int R = plspm_row_width(m);
+    const int R = ncols;
     if (stride < R + 1) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: stride must cover the status column");
     const int npad = (int)((B + 1) & ~(int64_t)1);
     const bool in_lds = npad <= CI_LDS_VALUES;
@@ -565,6 +621,83 @@ int plspm_bootstrap_moments(plspm_model_t* m, int64_t B, uint64_t seed, int64_t 
     plspm_dfree(d_out);
     m->rows_B = 0;
     return rc;
+}
+
+}  // extern "C"
+
+// ---- measurement-model assessment: per-replicate records [alpha | rho_a | rho_c | ave | htmt | htmt2 | lv_cor | status | iterations]
+static int assess_state(plspm_model* m, int64_t B, const char* who) {
+    if (!m->assess_B || !m->assess_rows.p) return fail(m, PLSPM_E_STATE, std::string(who) + ": no assessment records on this handle (plspm_assess_enable, then a plain bootstrap; an upload or a later call replaced them)");
+    if (B != m->assess_B) return fail(m, PLSPM_E_ARG, std::string(who) + ": B differs from the last assessed bootstrap on this handle");
+    return 0;
+}
+
+extern "C" {
+
+int plspm_assess_enable(plspm_model_t* m, int32_t on) {
+    if (!m) return fail(m, PLSPM_E_ARG, "plspm_assess_enable: no handle");
+    if (on && !assess_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_assess_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    m->assess_on = on != 0;
+    return 0;
+}
+
+int32_t plspm_assess_width(const plspm_model_t* m) { return m ? assess_width(m) : 0; }
+
+int plspm_assess_fit(plspm_model_t* m, double* out, int32_t* status) {
+    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_assess_fit: bad arguments");
+    if (!assess_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_assess_fit: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_assess_fit: no data uploaded");
+    HIPCHK(m, hipSetDevice(m->device));
+    const int RS = plspm_row_stride(m), A = assess_width(m);
+    int rc;
+    // [record RS | assessment A + 2 | status, iterations (int)]
+    if ((rc = ensure(m, m->assess_fit, (size_t)(RS + A + 2) * sizeof(double) + 2 * sizeof(int)))) return rc;
+    double* d = (double*)m->assess_fit.p;
+    int* d_int = (int*)(d + RS + A + 2);
+    if ((rc = dense_moments(m))) return rc;                       // the full sample's moments, tile-packed, in m->gram
+    SolverOut so{};
+    so.row = d; so.row_stride = 0; so.status = d_int; so.iters = d_int + 1;
+    {
+        const double* Mp; long mp_stride;
+        if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;
+        ProfScope ps(m, PLSPM_K_SOLVER);
+        if ((rc = launch_solver(m, 1, Mp, mp_stride, so, 256))) return rc;      // (the problem plspm_fit solves)
+    }
+    if ((rc = launch_assess(m, 1, false, (const double*)m->gram.p, d, 0, d + RS))) return rc;
+    HIPCHK(m, hipGetLastError());
+    std::vector<double> h((size_t)A + 2);
+    HIPCHK(m, hipMemcpyAsync(h.data(), d + RS, h.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    std::copy(h.begin(), h.begin() + A, out);
+    if (status) *status = (h[A] == h[A]) ? (int32_t)h[A] : -1;
+    return 0;
+}
+
+int plspm_assess_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
+    if (!m || first < 0 || count < 1) return fail(m, PLSPM_E_ARG, "plspm_assess_fetch: bad arguments");
+    if (!m->assess_B || !m->assess_rows.p) return fail(m, PLSPM_E_STATE, "plspm_assess_fetch: no assessment records on this handle (plspm_assess_enable, then a plain bootstrap; an upload or a later call replaced them)");
+    if (first + count > m->assess_B) return fail(m, PLSPM_E_ARG, "plspm_assess_fetch: range exceeds the last assessed bootstrap's replicates");
+    HIPCHK(m, hipSetDevice(m->device));
+    const int AS = assess_width(m) + 2;
+    return plspm_detail_fetch_records(m, (const double*)m->assess_rows.p + first * AS, count, AS, out, status, nullptr);
+}
+
+int plspm_assess_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
+    if (!m || !original || !summary || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_assess_summary: bad arguments (1 <= B <= 2^30)");
+    int rc;
+    if ((rc = assess_state(m, B, "plspm_assess_summary"))) return rc;
+    const int A = assess_width(m);
+    return plspm_detail_summary(m, (const double*)m->assess_rows.p, B, A + 2, A, original, summary, n_used);
+}
+
+int plspm_assess_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
+    if (!m || !original || !out || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_assess_intervals: bad arguments (1 <= B <= 2^30)");
+    if (method < CI_PERCENTILE || method >= CI_BCA) return fail(m, PLSPM_E_ARG, "plspm_assess_intervals: method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no assessment records, so there is no bca");
+    if (!(level > 0.0 && level < 1.0)) return fail(m, PLSPM_E_ARG, "plspm_assess_intervals: level must lie strictly between 0 and 1");
+    int rc;
+    if ((rc = assess_state(m, B, "plspm_assess_intervals"))) return rc;
+    const int A = assess_width(m);
+    return plspm_detail_intervals(m, (const double*)m->assess_rows.p, B, A + 2, A, original, nullptr, method, level, out, n_used);
 }
 
 }  // extern "C"

@@ -834,7 +834,7 @@ int plspm_group_summary(plspm_group_t* g, const double* original, double* summar
             GHIP(g, hipStreamWaitEvent(l.m->stream, l.gathered[g->last_slot], 0));
             int64_t used = 0;
             rc0 = check_peer_shards(g);
-            if (!rc0) { rc0 = plspm_detail_summary(l.m, (const double*)l.recv[g->last_slot].p, g->last_cap * g->nranks, plspm_row_stride(l.m), original, host.data() + 2, &used); if (rc0) g->error = l.m->error; }
+            if (!rc0) { rc0 = plspm_detail_summary(l.m, (const double*)l.recv[g->last_slot].p, g->last_cap * g->nranks, plspm_row_stride(l.m), plspm_row_width(l.m), original, host.data() + 2, &used); if (rc0) g->error = l.m->error; }
             host[0] = (double)rc0; host[1] = (double)used;
             GHIP(g, hipMemcpyAsync(l.bcast.p, host.data(), bytes, hipMemcpyHostToDevice, l.cstream));
         }
@@ -851,7 +851,7 @@ int plspm_group_summary(plspm_group_t* g, const double* original, double* summar
     GHIP(g, hipStreamWaitEvent(l.m->stream, l.gathered[g->last_slot], 0));
     int rc = check_peer_shards(g);
     if (rc) return rc;
-    rc = plspm_detail_summary(l.m, (const double*)l.recv[g->last_slot].p, g->last_cap * g->nranks, plspm_row_stride(l.m), original, summary, n_used);
+    rc = plspm_detail_summary(l.m, (const double*)l.recv[g->last_slot].p, g->last_cap * g->nranks, plspm_row_stride(l.m), plspm_row_width(l.m), original, summary, n_used);
     if (rc) return gfail(g, rc, l.m->error);
     return 0;
 }

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PLSPM_HIP_LIB", os.path.join(_HERE, "_lib", "libplspm
 ABI_VERSION = 4
 
 STATUS_OK, STATUS_NOT_CONVERGED, STATUS_SINGULAR, STATUS_NONFINITE = 0, 1, 2, 3
-KERNELS = {"resample": 0, "gram": 1, "solver": 2, "scores": 3, "pack": 4, "reduce": 5}
+KERNELS = {"resample": 0, "gram": 1, "solver": 2, "scores": 3, "pack": 4, "reduce": 5, "assess": 6}
 EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm_model_create", "plspm_model_destroy", "plspm_model_set_nonmetric", "plspm_model_set_categorical", "plspm_model_set_missing", "plspm_model_attach_second_stage", "plspm_model_set_incomplete_rows",
            "plspm_upload", "plspm_effect_pairs", "plspm_row_width", "plspm_row_stride", "plspm_fit", "plspm_bootstrap", "plspm_bootstrap_device", "plspm_bootstrap_summary",
            "plspm_sync", "plspm_stream", "plspm_bootstrap_indices", "plspm_profile_enable", "plspm_profile_read", "plspm_profile_reset",
@@ -30,7 +30,8 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_permutation_device", "plspm_permutation_counts", "plspm_permutation_members",
            "plspm_stratified_bootstrap_device", "plspm_stratified_pair_counts", "plspm_stratified_draws",
            "plspm_cv_folds", "plspm_cv_device", "plspm_cv_fold_ids", "plspm_cv_moments", "plspm_cv_targets", "plspm_cv_predict",
-           "plspm_jackknife_device", "plspm_jackknife_fetch", "plspm_jackknife_stats", "plspm_bootstrap_intervals"]
+           "plspm_jackknife_device", "plspm_jackknife_fetch", "plspm_jackknife_stats", "plspm_bootstrap_intervals",
+           "plspm_assess_enable", "plspm_assess_width", "plspm_assess_fit", "plspm_assess_fetch", "plspm_assess_summary", "plspm_assess_intervals"]
 CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
 CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
 UNIQUE_ID_BYTES = 128
@@ -122,6 +123,13 @@ def load():
     lib.plspm_jackknife_fetch.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.plspm_jackknife_stats.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_bootstrap_intervals.argtypes = [vp, vp, i64, i32, vp, vp, i32, dbl, vp, ctypes.POINTER(i64)]
+    lib.plspm_assess_enable.argtypes = [vp, i32]
+    lib.plspm_assess_width.restype = i32
+    lib.plspm_assess_width.argtypes = [vp]
+    lib.plspm_assess_fit.argtypes = [vp, vp, ctypes.POINTER(i32)]
+    lib.plspm_assess_fetch.argtypes = [vp, i64, i64, vp, vp]
+    lib.plspm_assess_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
+    lib.plspm_assess_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
     lib.plspm_profile_enable.argtypes = [vp, i32]
     lib.plspm_profile_read.argtypes = [vp, i32, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
     lib.plspm_profile_reset.argtypes = [vp]
@@ -536,6 +544,52 @@ class NativeModel:
         used = ctypes.c_int64(0)
         self._check(self._lib.plspm_jackknife_stats(self._h, G, _ptr(mean), _ptr(se), _ptr(accel), ctypes.byref(used)), "plspm_jackknife_stats")
         return mean, se, accel, used.value
+
+    def assess_enable(self, on=True):
+        """Measurement-model assessment (plspm_assess_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the assessment record
+        alpha | rho_a | rho_c | ave [L each] | htmt | htmt2 | lv_cor [L (L - 1) / 2 each] of every replicate; the bootstrap's own records do not change."""
+        self._check(self._lib.plspm_assess_enable(self._h, int(bool(on))), "plspm_assess_enable")
+
+    @property
+    def assess_width(self):
+        return int(self._lib.plspm_assess_width(self._h))
+
+    def assess_fit(self):
+        """The full-sample assessment record (plspm_assess_fit): ([A] values, status of the solver problem behind them)."""
+        out = np.empty(self.assess_width)
+        status = ctypes.c_int32(-1)
+        self._check(self._lib.plspm_assess_fit(self._h, _ptr(out), ctypes.byref(status)), "plspm_assess_fit")
+        return out, status.value
+
+    def assess_fetch(self, first=0, count=None):
+        """Host copy of the assessment records [first, first + count) of the last assessed bootstrap: (records [count, A], status [count])."""
+        if count is None:
+            count = self.last_B - first
+        out = np.empty((max(count, 0), self.assess_width))
+        status = np.empty(max(count, 0), dtype=np.int32)
+        self._check(self._lib.plspm_assess_fetch(self._h, first, count, _ptr(out), _ptr(status)), "plspm_assess_fetch")
+        return out, status
+
+    def assess_summary(self, B, original):
+        """``summary`` on the assessment records (plspm_assess_summary): ([A, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (self.assess_width,):
+            raise ValueError("original must have assess_width entries")
+        out = np.empty((self.assess_width, 6))
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_assess_summary(self._h, B, _ptr(original), _ptr(out), ctypes.byref(used)), "plspm_assess_summary")
+        return out, used.value
+
+    def assess_intervals(self, B, original, method="percentile", level=0.95):
+        """``intervals`` on the assessment records (plspm_assess_intervals; no bca): ([A, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (self.assess_width,):
+            raise ValueError("original must have assess_width entries")
+        mid = CI_METHODS.index(method) if isinstance(method, str) else int(method)
+        out = np.empty((self.assess_width, 6))
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_assess_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_assess_intervals")
+        return out, used.value
 
     def intervals(self, B, original, method="percentile", level=0.95, accel=None, d_rows=None, stride=0):
         """Device confidence intervals of the last bootstrap on this handle, or of the device records at ``d_rows`` (plspm_bootstrap_intervals).

@@ -5,7 +5,7 @@ bootstrap workers (plspm.py:35-37, bootstrap.py:89-94) -- caps the number of GPU
 over once the caller NAMES GPUs (``devices=[...]`` or the ``PLSPM_DEVICES`` allow-list; also capped by
 ``parallel.MIN_REPLICATES_PER_GPU`` replicates per GPU; ONE RCCL all-gather merges the shards; the rows do not depend on it).
 Without named GPUs everything runs on ``device_id``.  Keyword extensions: ``seed`` (reproducible bootstrap), ``device_id``, ``devices``,
-``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
+``quality`` (with ``bootstrap=True``: the measurement-model assessment of every replicate, ``quality()``), ``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
 reference's own fp64 accumulation on the data at hand; "strict": always seven planes = correctly rounded sums, ~20 % slower).
 """
 import time
@@ -66,7 +66,7 @@ class Plspm:
 
     def __init__(self, data: pd.DataFrame, config: c.Config, scheme: Scheme = Scheme.CENTROID, iterations: int = 100,
                  tolerance: float = 0.000001, bootstrap: bool = False, bootstrap_iterations: int = 100, processes: int = 2,
-                 seed: int = None, device_id: int = 0, devices=None, precision: str = "auto"):
+                 seed: int = None, device_id: int = 0, devices=None, precision: str = "auto", quality: bool = False):
         iterations, bootstrap_iterations = _normalise_arguments(scheme, iterations, tolerance, bootstrap_iterations, processes)
         t_start = time.perf_counter()
         estimator = Estimator(config)
@@ -86,6 +86,13 @@ class Plspm:
             # (HOC models: on a two-stage handle pair -- Scale.NUM / RAW and, since round 3, Scale.ORD / NOM data alike: both stages of
             #  every replicate run on the device, estimator.two_stage_bootstrap_handles)
             boot_on = estimator.two_stage_bootstrap_handles(calculator, observations) if config.hoc() else fit
+            if quality:
+                # the assessment kernel runs behind the solver of every replicate batch on this handle (plspm.quality)
+                from plspm import quality as pq
+                why = pq._unsupported(config, observations)
+                if why is not None:
+                    raise NotImplementedError("the assessment covers metric data without missing cells and without higher-order constructs: this model has " + why)
+                boot_on.native.assess_enable(True)
             pending = launch_bootstrap(boot_on, bootstrap_iterations, processes, seed, devices=devices)
         self._result = fit
         # The report frames only re-label / post-process the device outputs already on the host (fit.raw); they are built on first
@@ -111,6 +118,11 @@ class Plspm:
         if bootstrap:
             self._bootstrap = Bootstrap(model_spec, observations, self._inner_model, self._outer_model, calculator,
                                         bootstrap_iterations, processes, pending=pending)
+        self._quality = None
+        if bootstrap and quality:
+            if self._bootstrap.ranks() != 1:
+                raise NotImplementedError("the assessment runs on one GPU: this bootstrap was sharded over %d" % self._bootstrap.ranks())
+            self._quality = pq.Quality.of_bootstrap(fit.native, fit.compiled, bootstrap_iterations)
         # fit_s: filter + upload + device fit; bootstrap_s: what the bootstrap adds (the wait for the replicates + the device summaries);
         # bootstrap_latency_s: enqueue of the replicates -> summaries on the host
         self._timings = {"fit_s": t_fit - t_start, "bootstrap_s": time.perf_counter() - t_fit,
@@ -170,6 +182,12 @@ class Plspm:
         if self._bootstrap is None:
             raise Exception("To perform bootstrap validation, set the parameter bootstrap to True when calling Plspm")
         return self._bootstrap
+
+    def quality(self):
+        """The :class:`plspm.quality.Quality` assessment of the bootstrap; raises unless bootstrap=True and quality=True were requested."""
+        if self._quality is None:
+            raise Exception("To assess the measurement model, set the parameters bootstrap and quality to True when calling Plspm")
+        return self._quality
 
     # --- extension: solver diagnostics -------------------------------------------------------------------
     def timings(self) -> dict:
