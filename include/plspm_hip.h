@@ -535,6 +535,40 @@ int plspm_assess_summary(plspm_model_t* m, int64_t B, const double* original, do
 int plspm_assess_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
 
 /*
+ * ---- MICOM: permutation test of measurement invariance --------------------------------------------------------------------------
+ * Measurement invariance of composite models (Henseler, Ringle and Sarstedt 2016), steps 2 and 3, for every permutation of plspm_permutation_device: one more
+ * kernel behind the solver reads both halves' moment matrices and records.  Per group g of a permutation (problem 2r: a, 2r + 1: b), from its
+ * moments M_g:  mu_g,p = M_p1 / n_g,  c_g,pq = M_pq / n_g - mu_g,p mu_g,q,  s_g,p = sqrt(c_g,pp) (zero below the solver's 1e-9 threshold),  v_g,p = w_g,p s_g,p
+ * with the record's weights w_g.  From ALL uploaded rows, once per upload: the sds s_0, the diagonal blocks R_0,ll of the correlation matrix, the weights w_0
+ * of the full-sample fit (plspm_fit's problem), v_0,p = w_0,p s_0,p normalised per block so that v_0' R_0,ll v_0 = 1, and u_p = v_0,p / s_0,p.  Per LV l:
+ *     c        v_a' R_0,ll v_b / sqrt((v_a' R_0,ll v_a) (v_b' R_0,ll v_b))      compositional invariance (step 2): the correlation over all rows of the two
+ *                                                                             composites of pooled-standardised indicators; it carries a genuine sign
+ *     dmean    sum_{p in l} u_p (mu_a,p - mu_b,p)                                step 3: mean of the pooled composite, a - b
+ *     dlogvar  log(n_a / (n_a - 1) u' C_a,ll u) - log(n_b / (n_b - 1) u' C_b,ll u)   step 3: log ratio of its (ddof = 1) variances
+ * MICOM record, width 3 L:  c[L] | dmean[L] | dlogvar[L];  device records carry a status (0 iff both problems are PLSPM_OK, else the first problem's status
+ * when that is not OK, else the second's) and the larger of the two iteration counts behind it as doubles (pitch 3 L + 2).  A permutation whose status is not 0
+ * has NaN in all 3 L values; IEEE results stand where a formula divides by zero.  Plain metric handles only: PLSPM_E_ARG otherwise.
+ *
+ * plspm_micom_enable: on != 0: every later plspm_permutation_device call on this handle also writes the MICOM records of its B permutations into a buffer of
+ *   their own (record p of the call at position p); the 2B permutation records, status and iteration counts are bit for bit what they are without it.  Off (the
+ *   default): no launch, no allocation.  The observed split's record is a B = 1 call with explicit `member`.
+ * plspm_micom_width: 3 L.
+ * plspm_micom_fetch: host copy of the MICOM records [first, first + count) of the last MICOM permutation call: out [count*3L], status [count] (may be NULL).
+ * plspm_micom_summary / plspm_micom_intervals: plspm_bootstrap_summary / plspm_bootstrap_intervals on the MICOM records (B: that call's, else PLSPM_E_ARG):
+ *   original [3L] host, summary / out [3L*6] host, *n_used (may be NULL).  Methods 0 (percentile), 1 (basic), 2 (bc).
+ * plspm_micom_counts: per record column j over the valid records (status 0) of that call, on the records in HBM: below[j] = #{r : x_rj <= observed[j]},
+ *   exceed[j] = #{r : |x_rj| >= |observed[j]|} (a NaN on either side compares false); *n_used: the valid records.  observed [3L], below / exceed [3L] host.
+ * PLSPM_E_STATE from the last four without MICOM records on the handle (none written yet; an upload, or a later call that replaced the handle's records,
+ * voids them).
+ */
+int plspm_micom_enable(plspm_model_t* m, int32_t on);
+int32_t plspm_micom_width(const plspm_model_t* m);
+int plspm_micom_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
+int plspm_micom_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
+int plspm_micom_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
+int plspm_micom_counts(plspm_model_t* m, int64_t B, const double* observed, int64_t* below, int64_t* exceed, int64_t* n_used);
+
+/*
  * ---- Multi-GPU: replicate shards + ONE RCCL all-gather --------------------------------------------------------------------------
  * Reference: Bootstrap.__init__ forks `processes` workers, each running iterations / processes replicates, and merges their
  * frames through a Queue (plspm/bootstrap.py:89-111; `processes` kwarg plspm/plspm.py:35-37,60-61).  Here a GROUP of handles --
@@ -664,7 +698,7 @@ int plspm_op_outer_weights_nonmetric(int32_t device_id, int32_t mode, const doub
                                      double correction, double* w, double* Y);
 
 /* Kernel timing with HIP events on the handle's own stream (for the roofline figures in bench.py).
- * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce, 6 assessment. */
+ * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM kernel). */
 enum { PLSPM_K_RESAMPLE = 0, PLSPM_K_GRAM = 1, PLSPM_K_SOLVER = 2, PLSPM_K_SCORES = 3, PLSPM_K_PACK = 4, PLSPM_K_REDUCE = 5, PLSPM_K_ASSESS = 6, PLSPM_K_COUNT = 7 };
 /* on: 0 off, 1 every kernel, 2 + id only kernel `id` (an event pair costs dispatch latency on both sides: bracketing one kernel of a
  * step perturbs the step less than bracketing all of them). */

@@ -22,6 +22,7 @@ extern "C" {
  *                     Only ever lowers the automatic size; records, status and iteration counts must be bit-identical for every cut.
  *   "last_boot_passes"   read-only: the passes the last such batch was cut into (plspm_bootstrap() runs its sub-batches as batches of their own:
  *                     the last sub-batch's)
+ *   "last_micom_layout"  read-only: the moment layout the last MICOM launch read (plspm_micom_enable): 1 dense upper triangles, 2 tile-packed; 0: none yet
  *
  * Experiments build only (make -C plspm-python_amd/csrc experiments, loaded through PLSPM_HIP_LIB; the release library answers PLSPM_E_ARG):
  * "i8_waves" 4 (four-wave forms of the round-3 kernel: measured equal), "i8_shape" 32 (v_mfma_i32_32x32x32_i8 layout: 16 % slower), "i8_sched" 1

@@ -150,3 +150,11 @@ int launch_cv_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, 
 struct JackSpec { int64_t G; };
 // run_gram_i8 on a jackknife call (m->jack set): the 0/1 counts of problems [prob0, prob0 + nb) into `cd`, layout of resample_i8_kernel
 int launch_jack_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
+
+// ---- plspm_micom.hip (MICOM: measurement invariance of composite models on a permutation call's splits)
+inline bool micom_covers(const plspm_model* m) { return !m->nonmetric && !m->categorical && !m->n_ind && !m->nmx_K && !m->stage1 && !m->stage2; }
+// the pooled inputs of the resident rows (u [P], the diagonal blocks of R_0) into m->micom_pool, once per upload; overwrites m->gram
+int micom_prepare(plspm_model* m);
+// MICOM records of `nperm` permutations: problems 2p / 2p + 1 at `gram` (dense: [(P+1) x cov_ld(P)] upper triangles; else tile-packed) and `rows` (pitch
+// plspm_row_stride) -> out [nperm x (3 L + 2)].  One wave per permutation (kernels_micom.h).
+int launch_micom(plspm_model* m, long nperm, bool dense, const double* gram, const double* rows, double* out);

@@ -153,6 +153,13 @@ struct plspm_model {
     Buf assess_rows, assess_fit;             // ... the replicates' records; the full-sample record + its solver problem (plspm_assess_fit)
     int64_t assess_B = 0;                    // ... the last plain bootstrap whose assessment records are on the handle (0: none)
     int64_t assess_off = -1;                 // ... >= 0 while plspm_bootstrap() runs a sub-batch: its first replicate's position in the call (the buffer is the caller's to size)
+    // MICOM records of a permutation call's splits (kernels_micom.h; plspm_micom_*): records [micom_B x (3 L + 2)] in a buffer of their own, indexed by the
+    // permutation's position in the call; the pooled inputs (u, the diagonal blocks of R_0; plspm_micom.hip micom_prepare) once per upload
+    bool micom_on = false;                   // plspm_micom_enable
+    Buf micom_rows, micom_pool, micom_io;    // ... the permutations' records; the pooled inputs + the full-sample solver problem behind them; the counts' in / out block
+    int64_t micom_B = 0;                     // ... the last permutation call whose MICOM records are on the handle (0: none)
+    bool micom_pool_valid = false;           // ... micom_pool describes the rows that are resident now
+    int last_micom_layout = 0;               // 1 dense / 2 tile-packed: the moment layout the last MICOM launch read (read-only option "last_micom_layout"; 0: none yet)
     int last_gram_path = 0;       // 1 fp64 MFMA, 2 int8 digit planes: what the last bootstrap call used (plspm_model_get_info)
     int last_boot_passes = 0;     // passes the last plspm_detail_bootstrap batch was cut into (read-only option "last_boot_passes")
     int last_i8_dma = 0;          // 1 global_load_lds, 2 buffer_load ... lds: the LDS-DMA form of the last int8 Gram launch

@@ -119,6 +119,12 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     const int AS = assess_width(m) + 2;
     if (!m->jack && m->assess_off <= 0) m->assess_B = 0;
     if (assess && assess_own && (rc = ensure(m, m->assess_rows, (size_t)B * AS * sizeof(double)))) return rc;
+    // MICOM records (plspm_micom_enable) of a permutation call: one per pair of problems, from position 0 of the call.  Whatever replaces the handle's records
+    // voids the MICOM records that went with them (a jackknife call keeps records of its own).
+    const bool micom = m->micom_on && m->perm && micom_covers(m) && !rows_out;
+    const int MS = 3 * m->L + 2;
+    if (!m->jack) m->micom_B = 0;
+    if (micom && (rc = ensure(m, m->micom_rows, (size_t)(B / 2) * MS * sizeof(double)))) return rc;
     if (!rows_out) {
         m->rows_B = 0;
         if ((rc = ensure(m, m->rows, (size_t)B * R * sizeof(double)))) return rc;
@@ -218,10 +224,13 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
         if ((rc = launch_batch_solver(m, nb, (rows_solver && !f64_gram) ? route : ROUTE_LDS, so))) return rc;
         // the chunk's moment matrices are still in m->gram: dense where a dense solver read them, tile-packed for the LDS solver (fp64 Gram, int8 chunks that fell back)
         if (assess && (rc = launch_assess(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, (double*)m->assess_rows.p + (assess_base + b0) * AS))) return rc;
+        // (a chunk holds whole 256-problem tiles: the pairs stay together, and the chunk that starts at problem b0 starts at permutation b0 / 2)
+        if (micom && (rc = launch_micom(m, nb / 2, rows_solver && !f64_gram, gram_buf, so.row, (double*)m->micom_rows.p + (b0 / 2) * MS))) return rc;
     }
     HIPCHK(m, hipGetLastError());
     if (rows_out == (double*)m->rows.p) m->rows_B = B;
     if (assess && assess_own) m->assess_B = B;
+    if (micom) m->micom_B = B / 2;
     return 0;
 }
 // (m->stop_event: only the last chunk's solver launch may take it -- plspm_detail_bootstrap parks it while earlier chunks run)
@@ -329,7 +338,7 @@ int plspm_bootstrap_store(plspm_model_t* m, const double* records, int64_t B) {
     if (!m || !records || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_store: bad arguments");
     HIPCHK(m, hipSetDevice(m->device));
     const size_t bytes = (size_t)B * plspm_row_stride(m) * sizeof(double);
-    m->rows_B = 0;
+    m->rows_B = 0; m->micom_B = 0;
     int rc;
     if ((rc = ensure(m, m->rows, bytes))) return rc;
     if ((rc = plspm_detail_h2d(m, m->rows.p, records, bytes))) return rc;

@@ -300,7 +300,7 @@ void plspm_model_destroy(plspm_model_t* m) {
                     m->nmw_maps.p, m->nmw_ints.p, m->nmw_vsum.p, m->zs.p, m->cd.p, m->cd1.p, m->codes.p, m->ind8.p, m->tab8.p, m->scl8.p, m->err2.p, m->pp_ctl.p, m->sk_partial.p, m->sk_flags.p, m->pair_tab.p, m->pair_scale.p, m->zs_stat.p,
                     m->perm_thr.p, m->perm_member.p, m->perm_io.p, m->strat_rows.p, m->strat_draws.p, m->strat_io.p, m->strat_u.p,
                     m->cv_fold.p, m->cv_thr.p, m->cv_idx.p, m->cv_off.p, m->cv_mom.p, m->cv_coef.p, m->cv_io.p, m->cv_pred.p, m->cv_tab.p,
-                    m->jack_rows.p, m->jack_status.p, m->jack_iters.p, m->jack_io.p, m->assess_rows.p, m->assess_fit.p};
+                    m->jack_rows.p, m->jack_status.p, m->jack_iters.p, m->jack_io.p, m->assess_rows.p, m->assess_fit.p, m->micom_rows.p, m->micom_pool.p, m->micom_io.p};
     for (void* p : ptrs) if (p) plspm_dfree(p);
     for (void* p : m->blobs) if (p) plspm_dfree(p);
     if (m->h_stage) plspm_hfree(m->h_stage);
@@ -347,7 +347,7 @@ int plspm_upload(plspm_model_t* m, const double* X, int64_t N, int32_t src_cols,
     if (m->aux) HIPCHK(m, hipStreamSynchronize(m->aux));
     HIPCHK(m, hipStreamSynchronize(m->stream));
     // whatever was resident is gone from here on (a failed upload leaves an empty, re-usable handle)
-    m->N = 0; m->d_Xa = nullptr; m->Xt_valid = false; m->codes_valid = false; m->ind8_valid = false; if (m->stage2) { m->stage2->codes_valid = false; m->stage2->ind8_valid = false; } m->rows_B = 0; m->cv_reps = 0; m->jack_G = 0; m->assess_B = 0; m->dcnt_ready = false; m->zs_valid = false; m->zs_stats_ready = false;
+    m->N = 0; m->d_Xa = nullptr; m->Xt_valid = false; m->codes_valid = false; m->ind8_valid = false; if (m->stage2) { m->stage2->codes_valid = false; m->stage2->ind8_valid = false; } m->rows_B = 0; m->cv_reps = 0; m->jack_G = 0; m->assess_B = 0; m->micom_B = 0; m->micom_pool_valid = false; m->dcnt_ready = false; m->zs_valid = false; m->zs_stats_ready = false;
     drop_incomplete_rows(m);
     // persistent grow-only buffers: a repeated upload of the same shape allocates nothing
     const size_t raw_bytes = (size_t)N * src_cols * sizeof(double);
@@ -574,6 +574,7 @@ int plspm_model_get_option(const plspm_model_t* m, const char* key, int32_t* val
     else if (k == "boot_pass") *value = m->tune.boot_pass;
     else if (k == "last_boot_passes") *value = m->last_boot_passes;
     else if (k == "last_gram_path") *value = m->last_gram_path;
+    else if (k == "last_micom_layout") *value = m->last_micom_layout;
     else if (k == "build_experiments") {
 #ifdef PLSPM_I8_EXPERIMENTS
         *value = 1;

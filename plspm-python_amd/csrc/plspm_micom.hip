@@ -1,0 +1,140 @@
+// plspm_micom.hip -- host side, part 9: MICOM, the permutation test of measurement invariance of composite models.  The pooled inputs of the
+// resident rows (once per upload), the launch of the per-permutation kernel behind a permutation batch's solver (plspm_bootstrap.hip hooks it in beside the
+// assessment), the counts on the records in HBM and the C-ABI entry points (plspm_micom_*).  Kernels: kernels_micom.h (assess_moment: kernels_assess.h).
+#include "host_internal.h"
+
+#include "wave_ops.h"
+#include "kernels_assess.h"
+#include "kernels_micom.h"
+
+static inline int micom_width(const plspm_model* m) { return 3 * m->L; }
+static inline int micom_largest_block(const plspm_model* m) {
+    int kb = 1;
+    for (int l = 0; l < m->L; ++l) kb = std::max(kb, m->boff[l + 1] - m->boff[l]);
+    return kb;
+}
+static inline long micom_r0_doubles(const plspm_model* m) {
+    long s = 0;
+    for (int l = 0; l < m->L; ++l) { const long k = m->boff[l + 1] - m->boff[l]; s += k * k; }
+    return s;
+}
+
+// m->micom_pool: [u P | s_0 P | R_0's diagonal blocks | the full-sample problem's record RS | its status, iterations (int)]
+int micom_prepare(plspm_model* m) {
+    if (m->micom_pool_valid) return 0;
+    const int P = m->P, RS = plspm_row_stride(m);
+    const long K2 = micom_r0_doubles(m);
+    int rc;
+    if ((rc = ensure(m, m->micom_pool, (size_t)(2L * P + K2 + RS) * sizeof(double) + 2 * sizeof(int)))) return rc;
+    double* u = (double*)m->micom_pool.p;
+    double *s0 = u + P, *r0 = s0 + P, *rec = r0 + K2;
+    int* d_int = (int*)(rec + RS);
+    if ((rc = dense_moments(m))) return rc;                       // the full sample's moments, tile-packed, in m->gram
+    SolverOut so{};
+    so.row = rec; so.row_stride = 0; so.status = d_int; so.iters = d_int + 1;
+    {
+        const double* Mp; long mp_stride;
+        if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;
+        ProfScope ps(m, PLSPM_K_SOLVER);
+        if ((rc = launch_solver(m, 1, Mp, mp_stride, so, 256))) return rc;      // (the problem plspm_fit and plspm_assess_fit solve)
+    }
+    hipLaunchKernelGGL(micom_pooled_kernel, dim3(1), dim3(64), 0, m->stream, (const double*)m->gram.p, m->T, P, m->L, (const int*)m->d_boff, (const double*)rec, plspm_row_width(m), u, s0, r0);
+    HIPCHK(m, hipGetLastError());
+    m->micom_pool_valid = true;
+    return 0;
+}
+
+int launch_micom(plspm_model* m, long nperm, bool dense, const double* gram, const double* rows, double* out) {
+    const int kb = micom_largest_block(m);
+    const size_t lds = (size_t)MICOM_WAVES * micom_wave_doubles(kb) * sizeof(double);
+    auto k = dense ? micom_kernel<true> : micom_kernel<false>;
+    if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
+    MicomArgs a{};
+    a.gram = gram; a.gstride = dense ? cov_doubles(m->P) : packed_size(m->T); a.ld = dense ? cov_ld(m->P) : m->T;
+    a.P = m->P; a.L = m->L; a.R = plspm_row_width(m); a.kb = kb;
+    a.boff = m->d_boff;
+    a.rows = rows; a.row_stride = plspm_row_stride(m);
+    a.u = (const double*)m->micom_pool.p; a.r0 = a.u + 2L * m->P;
+    a.out = out; a.np = nperm;
+    {
+        ProfScope ps(m, PLSPM_K_ASSESS);
+        hipLaunchKernelGGL(k, dim3((unsigned)((nperm + MICOM_WAVES - 1) / MICOM_WAVES)), dim3(64 * MICOM_WAVES), lds, m->stream, a);
+    }
+    m->last_micom_layout = dense ? 1 : 2;
+    return 0;
+}
+
+static int micom_state(plspm_model* m, int64_t B, const char* who) {
+    if (!m->micom_B || !m->micom_rows.p) return fail(m, PLSPM_E_STATE, std::string(who) + ": no MICOM records on this handle (plspm_micom_enable, then plspm_permutation_device; an upload or a later call replaced them)");
+    if (B != m->micom_B) return fail(m, PLSPM_E_ARG, std::string(who) + ": B differs from the last MICOM permutation call on this handle");
+    return 0;
+}
+
+extern "C" {
+
+int plspm_micom_enable(plspm_model_t* m, int32_t on) {
+    if (!m) return fail(m, PLSPM_E_ARG, "plspm_micom_enable: no handle");
+    if (on && !micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    m->micom_on = on != 0;
+    return 0;
+}
+
+int32_t plspm_micom_width(const plspm_model_t* m) { return m ? micom_width(m) : 0; }
+
+int plspm_micom_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
+    if (!m || first < 0 || count < 1) return fail(m, PLSPM_E_ARG, "plspm_micom_fetch: bad arguments");
+    if (!micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_fetch: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (!m->micom_B || !m->micom_rows.p) return fail(m, PLSPM_E_STATE, "plspm_micom_fetch: no MICOM records on this handle (plspm_micom_enable, then plspm_permutation_device; an upload or a later call replaced them)");
+    if (first + count > m->micom_B) return fail(m, PLSPM_E_ARG, "plspm_micom_fetch: range exceeds the last MICOM permutation call's permutations");
+    HIPCHK(m, hipSetDevice(m->device));
+    const int MS = micom_width(m) + 2;
+    return plspm_detail_fetch_records(m, (const double*)m->micom_rows.p + first * MS, count, MS, out, status, nullptr);
+}
+
+int plspm_micom_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
+    if (!m || !original || !summary || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_micom_summary: bad arguments (1 <= B <= 2^30)");
+    if (!micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_summary: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    int rc;
+    if ((rc = micom_state(m, B, "plspm_micom_summary"))) return rc;
+    const int W = micom_width(m);
+    return plspm_detail_summary(m, (const double*)m->micom_rows.p, B, W + 2, W, original, summary, n_used);
+}
+
+int plspm_micom_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
+    if (!m || !original || !out || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_micom_intervals: bad arguments (1 <= B <= 2^30)");
+    if (!micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_intervals: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (method < 0 || method > 2) return fail(m, PLSPM_E_ARG, "plspm_micom_intervals: method must be 0 (percentile), 1 (basic) or 2 (bc)");
+    if (!(level > 0.0 && level < 1.0)) return fail(m, PLSPM_E_ARG, "plspm_micom_intervals: level must lie strictly between 0 and 1");
+    int rc;
+    if ((rc = micom_state(m, B, "plspm_micom_intervals"))) return rc;
+    const int W = micom_width(m);
+    return plspm_detail_intervals(m, (const double*)m->micom_rows.p, B, W + 2, W, original, nullptr, method, level, out, n_used);
+}
+
+int plspm_micom_counts(plspm_model_t* m, int64_t B, const double* observed, int64_t* below, int64_t* exceed, int64_t* n_used) {
+    if (!m || B < 1 || !observed || !below || !exceed) return fail(m, PLSPM_E_ARG, "plspm_micom_counts: bad arguments");
+    if (!micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_counts: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    int rc;
+    if ((rc = micom_state(m, B, "plspm_micom_counts"))) return rc;
+    HIPCHK(m, hipSetDevice(m->device));
+    const int W = micom_width(m);
+    // [observed W | below W | exceed W | valid records]
+    if ((rc = ensure(m, m->micom_io, (size_t)(3 * W + 1) * sizeof(double)))) return rc;
+    double* d_obs = (double*)m->micom_io.p;
+    unsigned long long* d_cnt = (unsigned long long*)(d_obs + W);
+    HIPCHK(m, hipMemcpyAsync(d_obs, observed, (size_t)W * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    {
+        ProfScope ps(m, PLSPM_K_REDUCE);
+        hipLaunchKernelGGL(micom_count_kernel, dim3((unsigned)W), dim3(MICOM_COUNT_NT), 0, m->stream, (const double*)m->micom_rows.p, (long)B, W, (const double*)d_obs, d_cnt, d_cnt + W,
+                           d_cnt + 2 * W);
+    }
+    HIPCHK(m, hipGetLastError());
+    std::vector<unsigned long long> h((size_t)2 * W + 1);
+    HIPCHK(m, hipMemcpyAsync(h.data(), d_cnt, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    for (int j = 0; j < W; ++j) { below[j] = (int64_t)h[(size_t)j]; exceed[j] = (int64_t)h[(size_t)W + j]; }
+    if (n_used) *n_used = (int64_t)h[(size_t)2 * W];
+    return 0;
+}
+
+}  // extern "C"

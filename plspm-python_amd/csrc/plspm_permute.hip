@@ -231,6 +231,7 @@ int plspm_permutation_device(plspm_model_t* m, int64_t B, uint64_t seed, int64_t
         if ((rc = plspm_detail_h2d(m, m->perm_member.p, member, bytes))) return rc;
         d_member = (const uint8_t*)m->perm_member.p;
     }
+    if (m->micom_on && (rc = micom_prepare(m))) return rc;               // (the pooled inputs of the MICOM records: once per upload, in front of the batch that overwrites m->gram)
     const PermSpec spec{seed, rep_offset, n1, d_member};
     m->perm = &spec;
     rc = plspm_detail_bootstrap(m, 2 * B, 0, 0, nullptr, nullptr);       // problems 2p / 2p + 1 = the groups of permutation rep_offset + p

@@ -31,7 +31,8 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_stratified_bootstrap_device", "plspm_stratified_pair_counts", "plspm_stratified_draws",
            "plspm_cv_folds", "plspm_cv_device", "plspm_cv_fold_ids", "plspm_cv_moments", "plspm_cv_targets", "plspm_cv_predict",
            "plspm_jackknife_device", "plspm_jackknife_fetch", "plspm_jackknife_stats", "plspm_bootstrap_intervals",
-           "plspm_assess_enable", "plspm_assess_width", "plspm_assess_fit", "plspm_assess_fetch", "plspm_assess_summary", "plspm_assess_intervals"]
+           "plspm_assess_enable", "plspm_assess_width", "plspm_assess_fit", "plspm_assess_fetch", "plspm_assess_summary", "plspm_assess_intervals",
+           "plspm_micom_enable", "plspm_micom_width", "plspm_micom_fetch", "plspm_micom_summary", "plspm_micom_intervals", "plspm_micom_counts"]
 CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
 CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
 UNIQUE_ID_BYTES = 128
@@ -130,6 +131,13 @@ def load():
     lib.plspm_assess_fetch.argtypes = [vp, i64, i64, vp, vp]
     lib.plspm_assess_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_assess_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
+    lib.plspm_micom_enable.argtypes = [vp, i32]
+    lib.plspm_micom_width.restype = i32
+    lib.plspm_micom_width.argtypes = [vp]
+    lib.plspm_micom_fetch.argtypes = [vp, i64, i64, vp, vp]
+    lib.plspm_micom_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
+    lib.plspm_micom_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
+    lib.plspm_micom_counts.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_profile_enable.argtypes = [vp, i32]
     lib.plspm_profile_read.argtypes = [vp, i32, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
     lib.plspm_profile_reset.argtypes = [vp]
@@ -590,6 +598,57 @@ class NativeModel:
         used = ctypes.c_int64(0)
         self._check(self._lib.plspm_assess_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_assess_intervals")
         return out, used.value
+
+    def micom_enable(self, on=True):
+        """MICOM (plspm_micom_enable): every later ``permutation`` call also writes the record c | dmean | dlogvar [L each] of every permutation --
+        compositional invariance and the differences of the pooled composite's means and log variances; the permutation's own records do not change."""
+        self._check(self._lib.plspm_micom_enable(self._h, int(bool(on))), "plspm_micom_enable")
+
+    @property
+    def micom_width(self):
+        return int(self._lib.plspm_micom_width(self._h))
+
+    def micom_fetch(self, first=0, count=None):
+        """Host copy of the MICOM records [first, first + count) of the last MICOM permutation call: (records [count, 3 L], status [count])."""
+        if count is None:
+            count = self.last_B // 2 - first
+        out = np.empty((max(count, 0), self.micom_width))
+        status = np.empty(max(count, 0), dtype=np.int32)
+        self._check(self._lib.plspm_micom_fetch(self._h, first, count, _ptr(out), _ptr(status)), "plspm_micom_fetch")
+        return out, status
+
+    def micom_summary(self, B, original):
+        """``summary`` on the MICOM records (plspm_micom_summary): ([3 L, 6] original, mean, std.error, perc.025, perc.975, t stat.; valid permutations)."""
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (self.micom_width,):
+            raise ValueError("original must have micom_width entries")
+        out = np.empty((self.micom_width, 6))
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_micom_summary(self._h, B, _ptr(original), _ptr(out), ctypes.byref(used)), "plspm_micom_summary")
+        return out, used.value
+
+    def micom_intervals(self, B, original, method="percentile", level=0.95):
+        """``intervals`` on the MICOM records (plspm_micom_intervals; no bca): ([3 L, 6] lower, upper, z0, accel, level.lower, level.upper; valid permutations)."""
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (self.micom_width,):
+            raise ValueError("original must have micom_width entries")
+        mid = CI_METHODS.index(method) if isinstance(method, str) else int(method)
+        out = np.empty((self.micom_width, 6))
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_micom_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_micom_intervals")
+        return out, used.value
+
+    def micom_counts(self, B, observed):
+        """Counts on the MICOM records of the last MICOM permutation call (plspm_micom_counts): ([3 L] int64 #{valid r : x_r <= observed},
+        [3 L] int64 #{valid r : |x_r| >= |observed|}, number of valid permutations)."""
+        observed = np.ascontiguousarray(observed, dtype=np.float64)
+        if observed.shape != (self.micom_width,):
+            raise ValueError("observed must have micom_width entries")
+        below = np.empty(self.micom_width, dtype=np.int64)
+        exceed = np.empty(self.micom_width, dtype=np.int64)
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_micom_counts(self._h, B, _ptr(observed), _ptr(below), _ptr(exceed), ctypes.byref(used)), "plspm_micom_counts")
+        return below, exceed, used.value
 
     def intervals(self, B, original, method="percentile", level=0.95, accel=None, d_rows=None, stride=0):
         """Device confidence intervals of the last bootstrap on this handle, or of the device records at ``d_rows`` (plspm_bootstrap_intervals).

@@ -72,6 +72,18 @@ def _labels(data: pd.DataFrame, group) -> pd.Series:
     return labels
 
 
+def _observations(data: pd.DataFrame, config: c.Config, what: str) -> pd.DataFrame:
+    """The model's columns of ``data`` once the scope of the two-group procedures holds: metric scales, no higher-order constructs, no missing cells."""
+    if not config.metric():
+        raise NotImplementedError(what + " covers metric data only (no Scale.NUM / RAW / ORD / NOM)")
+    if config.hoc():
+        raise NotImplementedError(what + " does not cover higher-order constructs")
+    observations = config.filter(data)
+    if config.nan_columns(observations).any():
+        raise NotImplementedError(what + " needs complete data (no missing cells in the model's columns)")
+    return observations
+
+
 def bootstrap_tests(diff, se_a, se_b, mean_a, mean_b, n_a, n_b, above, used_a, used_b) -> dict:
     """The three tests of ``method="bootstrap"`` per result column (see the module docstring): {"parametric": (t, df, p), "welch": (t, df, p),
     "henseler": p}.  ``above``: Henseler's pair counts; ``used_a`` / ``used_b``: the valid records of each group."""
@@ -135,14 +147,7 @@ class GroupComparison:
         if method == "bootstrap" and int(resamples) < 1:
             raise ValueError("resamples must be at least 1")
         labels = _labels(data, group)
-        what = "the %s test" % method
-        if not config.metric():
-            raise NotImplementedError(what + " covers metric data only (no Scale.NUM / RAW / ORD / NOM)")
-        if config.hoc():
-            raise NotImplementedError(what + " does not cover higher-order constructs")
-        observations = config.filter(data)
-        if config.nan_columns(observations).any():
-            raise NotImplementedError(what + " needs complete data (no missing cells in the model's columns)")
+        observations = _observations(data, config, "the %s test" % method)
         a, b = sorted(labels.unique())
         in_a = (labels.loc[observations.index] == a).values
         self._labels = (a, b)
