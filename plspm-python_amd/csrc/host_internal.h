@@ -87,6 +87,13 @@ struct SolverOut {
     FitOutputs fit;     // single-fit extras (problem 0 only)
 };
 
+// the device pointers an enqueue-only entry point hands back (any of the three may be null)
+inline void hand_out(const plspm_model::Buf& rows, const plspm_model::Buf& status, const plspm_model::Buf& iters, void** d_out, void** d_status, void** d_iters) {
+    if (d_out) *d_out = rows.p;
+    if (d_status) *d_status = status.p;
+    if (d_iters) *d_iters = iters.p;
+}
+
 // ---- plspm_hip.hip
 ModelDesc make_desc(const plspm_model* m);
 HocDesc make_hoc_desc(const plspm_model* m2);
@@ -102,7 +109,8 @@ int launch_gram_lists(plspm_model* m, long nproblems, const int2* ent, const int
 int run_impute(plspm_model* m, long nproblems, const double* Min, const double** Mp, long* mp_stride);
 int launch_solver(plspm_model* m, long nproblems, const double* Mp, long mp_stride, const SolverOut& so, int threads);
 // the metric solver of a bootstrap batch: `route` as metric_batch_route chose it when the int8 Gram wrote dense matrices, else ROUTE_LDS
-int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const SolverOut& so);
+// stop: an event the launch may signal on completion (the dense solvers do, and set *stop_taken; plspm_fit.hip launch_signalling), or null
+int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const SolverOut& so, hipEvent_t stop, bool* stop_taken);
 // Scale.NUM / RAW non-metric bootstrap batches as ONE solver launch (round 6; solver_wave16.h NM; nm_route.h num_one says whether the model has such a kernel)
 // (dense moment matrices at m->gram; maps / steps as kernels_solver.h solver_nmwave_kernel takes them; force + live: the replay of `nb` listed replicates)
 int launch_nm_wave_solver(plspm_model* m, long nb, const SolverOut& so, double* maps, long maps_stride, int* steps, const int* force, const int* live);
@@ -117,42 +125,55 @@ int run_hoc_moments(plspm_model* m, plspm_model* m2, long nb);
 static inline int i8_kblocks(long N) { return (int)((N + 127) / 128) * 2; }      // k-blocks of 64 rows, an even number
 static inline long i8_pairs(const plspm_model* m) { const long C = m->Pg + 1; return C * (C + 1) / 2; }
 bool nm_counts8_possible(const plspm_model* m);
-int choose_gram_path(const plspm_model* m, int64_t B);      // 1 fp64 MFMA on (row,count) lists, 2 int8 digit planes
+bool gram_i8_closed(const plspm_model* m, int slices);      // the int8 route is closed for the resident data at this plane count (stage 1, N, non-metric window, plane budget)
+int choose_gram_path(const plspm_model* m, int64_t B);      // 1 fp64 MFMA on (row,count) lists, 2 int8 digit planes: the "gram_path" / "i8_min_batch" policy where the route is open
+// the route of the calls that bring their own counts (model.h brings_counts): open at the seven planes at least such a call cuts, whatever the policy says
+inline bool gram_counts_route_open(const plspm_model* m) { return !gram_i8_closed(m, std::max(m->tune.i8_slices, 7)); }
 int prepare_zs_stats(plspm_model* m);
 int prepare_zs(plspm_model* m, int floor = 0);      // floor: at least this many digit planes (0: the handle's own choice)
-int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const int32_t* d_idx, double* out, bool dense, bool* fallback, const void** counts = nullptr,
+// problems [b0, b0 + nb) of `call`: their counts (drawn, or the kind's own count kernel) and the product
+int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, double* out, bool dense, bool* fallback, const void** counts = nullptr,
                 int* counts_MT = nullptr, unsigned short* out16 = nullptr, bool* wrote16 = nullptr);
 // plspm_nonmetric.hip: a Scale.NUM / RAW batch as one solver launch + verification (pl.num_one)
 int run_nonmetric_wave(plspm_model* m, const NmPlan& pl, const SolverOut& so, const void* cd8, int cd8_MT);
+
+// ---- plspm_bootstrap.hip: side records -- a buffer of records [count x (width + 2)] (values | status | iterations) beside the bootstrap records, valid while
+// `count` is non-zero: the assessment records of a plain bootstrap, the MICOM records of a permutation call.  One description, and the entry points both share.
+// plain_only: the entry points refuse any other handle kind behind their argument check (MICOM; the assessment answers "no records" there).  none / differs /
+// range / method: the kind's whole messages behind "<who>" -- no records, B is not the count, a fetch past the count, a method the intervals do not take
+struct SideRecords { const plspm_model::Buf& buf; int64_t count; int width; bool plain_only; const char *none, *differs, *range, *method; };
+int side_state(plspm_model* m, const SideRecords& s, int64_t B, const char* who);       // records there, and B of them
+int side_fetch(plspm_model* m, const SideRecords& s, int64_t first, int64_t count, double* out, int32_t* status, const char* who);
+int side_summary(plspm_model* m, const SideRecords& s, int64_t B, const double* original, double* summary, int64_t* n_used, const char* who);
+int side_intervals(plspm_model* m, const SideRecords& s, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used, const char* who);
 
 // ---- plspm_permute.hip (two-group permutation test)
 // One call's splits: permutation rep_offset + p has problem 2p = group a (n1 rows), 2p + 1 = the other N - n1 rows; `d_member` [B][N] bytes 0/1
 // (explicit memberships, tests) or null (on-device splits from the Philox keys, kernels_permute.h).
 struct PermSpec { uint64_t seed; int64_t rep_offset; int64_t n1; const uint8_t* d_member; };
-// run_gram_i8 on a permutation call (m->perm set): the 0/1 counts of problems [prob0, prob0 + nb) (prob0, nb even) into `cd`, layout of
+// run_gram_i8 on a permutation call: the 0/1 counts of problems [prob0, prob0 + nb) (prob0, nb even) of the call's splits `ps` into `cd`, layout of
 // resample_i8_kernel (MT count tiles, KB k-blocks)
-int launch_perm_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
+int launch_perm_counts(plspm_model* m, const PermSpec& ps, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
 // One call's stratified resamples: resample rep_offset + p has problem 2p = n_a draws from group a's rows, 2p + 1 = n_b draws from group b's;
 // `d_rows` [N] = group a's rows then group b's, ascending; `d_draws` [B][N] explicit rows (tests) or null (Philox draws, kernels_strat.h).
 struct StratSpec { uint64_t seed; int64_t rep_offset; int64_t n_a; const int32_t* d_rows; const int32_t* d_draws; };
-// run_gram_i8 on a stratified call (m->strat set): the counts of problems [prob0, prob0 + nb) (prob0, nb even) into `cd`, same layout
-int launch_strat_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
+// run_gram_i8 on a stratified call: the counts of problems [prob0, prob0 + nb) (prob0, nb even) of the call's draws `ss` into `cd`, same layout
+int launch_strat_counts(plspm_model* m, const StratSpec& ss, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
 
 // ---- plspm_cv.hip (k-fold cross-validation: out-of-sample prediction)
 // One call's folds: problem r * k + f = the rows of repetition rep_offset + r outside fold f; `d_fold` [reps][N] fold ids (drawn on the device from
 // the Philox keys or uploaded, kernels_cv.h) -- ready on the handle's stream before plspm_detail_bootstrap runs.
 struct CvSpec { int64_t reps; int k; const uint8_t* d_fold; };
-// run_gram_i8 on a cross-validation call (m->cv set): the 0/1 counts of problems [prob0, prob0 + nb) into `cd`, layout of resample_i8_kernel
-int launch_cv_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
+// run_gram_i8 on a cross-validation call: the 0/1 counts of problems [prob0, prob0 + nb) of the call's folds `cs` into `cd`, layout of resample_i8_kernel
+int launch_cv_counts(plspm_model* m, const CvSpec& cs, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
 
 // ---- plspm_jackknife.hip (delete-one / delete-a-group jackknife)
 // One call's problems: problem g of G leaves out the rows i with i % G == g.
 struct JackSpec { int64_t G; };
-// run_gram_i8 on a jackknife call (m->jack set): the 0/1 counts of problems [prob0, prob0 + nb) into `cd`, layout of resample_i8_kernel
-int launch_jack_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
+// run_gram_i8 on a jackknife call: the 0/1 counts of problems [prob0, prob0 + nb) of the call's groups `js` into `cd`, layout of resample_i8_kernel
+int launch_jack_counts(plspm_model* m, const JackSpec& js, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
 
 // ---- plspm_micom.hip (MICOM: measurement invariance of composite models on a permutation call's splits)
-inline bool micom_covers(const plspm_model* m) { return !m->nonmetric && !m->categorical && !m->n_ind && !m->nmx_K && !m->stage1 && !m->stage2; }
 // the pooled inputs of the resident rows (u [P], the diagonal blocks of R_0) into m->micom_pool, once per upload; overwrites m->gram
 int micom_prepare(plspm_model* m);
 // MICOM records of `nperm` permutations: problems 2p / 2p + 1 at `gram` (dense: [(P+1) x cov_ld(P)] upper triangles; else tile-packed) and `rows` (pitch

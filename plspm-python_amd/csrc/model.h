@@ -26,15 +26,13 @@ void plspm_hfree(void* p);
 hipError_t plspm_stream_acquire(hipStream_t* s);
 void plspm_stream_release(hipStream_t s);
 
-// Kernel timing (plspm_profile_*): event pairs are recycled through `pool`, so a profiled launch costs two hipEventRecord only.
-// Split spec of a two-group permutation call (plspm_permute.hip) while plspm_detail_bootstrap runs it.
-struct PermSpec;
-// Draw spec of a stratified bootstrap call of the two-group test (plspm_permute.hip) while plspm_detail_bootstrap runs it.
-struct StratSpec;
-// Fold spec of a cross-validation call (plspm_cv.hip) while plspm_detail_bootstrap runs it.
-struct CvSpec;
-struct JackSpec;
+// The specs of the batch kinds that bring their own counts (host_internal.h): a BatchCall below points at its kind's.
+struct PermSpec;      // two-group permutation: the splits (plspm_permute.hip)
+struct StratSpec;     // stratified bootstrap of the two-group test: the draws inside each group (plspm_permute.hip)
+struct CvSpec;        // cross-validation: the folds (plspm_cv.hip)
+struct JackSpec;      // jackknife: the number of groups (plspm_jackknife.hip)
 
+// Kernel timing (plspm_profile_*): event pairs are recycled through `pool`, so a profiled launch costs two hipEventRecord only.
 struct ProfSlot { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, pool; double total_ms = 0.0; int64_t launches = 0; };
 
 struct plspm_model {
@@ -135,24 +133,18 @@ struct plspm_model {
     int zs_floor = 0;           // the plane floor the current planes were cut under (prepare_zs: 0 = the handle's own choice, 7 = a permutation call)
     bool zs_ind = false;        // one plane per pair group, launched through the seven-plane main loop (gram_i8_kernel<.., IND>)
     double zs_ratio = 0.0;      // smallest sum|z| / max|z| over the pair columns (automatic plane count; 0: not evaluated)
-    double* moments_out = nullptr; // plspm_bootstrap_moments: dense moment matrices go here and the solver is skipped
-    const PermSpec* perm = nullptr; // plspm_permutation_device: the batch's problems are the two groups of random splits (int8 route, no resampling)
-    Buf perm_thr, perm_member, perm_io;      // ... the splits' thresholds, explicit memberships, the exceedance counts' in / out block
-    const StratSpec* strat = nullptr;        // plspm_stratified_bootstrap_device: the batch's problems are resamples drawn inside each group (int8 route)
-    Buf strat_rows, strat_draws, strat_io, strat_u;      // ... both groups' row lists, explicit draws, the pair counts' in / out block and u values
+    Buf perm_thr, perm_member, perm_io;      // plspm_permutation_device: the splits' thresholds, explicit memberships, the exceedance counts' in / out block
+    Buf strat_rows, strat_draws, strat_io, strat_u;      // plspm_stratified_bootstrap_device: both groups' row lists, explicit draws, the pair counts' in / out block and u values
     std::vector<uint8_t> strat_member;       // ... the memberships strat_rows was built from (uploaded again only when they change)
-    const CvSpec* cv = nullptr;              // plspm_cv_device: problem r * k + f is the training set of fold f of repetition r (int8 route, 0/1 counts)
-    Buf cv_fold, cv_thr, cv_idx, cv_off, cv_mom, cv_coef, cv_io, cv_pred, cv_tab;      // ... fold ids, thresholds, rows in fold order + offsets, training moments, coefficient matrices, error sums, predictions, small tables
+    Buf cv_fold, cv_thr, cv_idx, cv_off, cv_mom, cv_coef, cv_io, cv_pred, cv_tab;      // plspm_cv_device: fold ids, thresholds, rows in fold order + offsets, training moments, coefficient matrices, error sums, predictions, small tables
     int64_t cv_reps = 0; int cv_k = 0;       // ... the last plspm_cv_device call whose folds, moments and records are on the handle (0: none)
-    const JackSpec* jack = nullptr;          // plspm_jackknife_device: problem g leaves out the rows i with i % G == g (int8 route, 0/1 counts)
-    Buf jack_rows, jack_status, jack_iters, jack_io;      // ... its records, status and iteration counts (buffers of their own: the bootstrap's survive the call), the statistics' out block
+    Buf jack_rows, jack_status, jack_iters, jack_io;      // plspm_jackknife_device: its records, status and iteration counts (buffers of their own: the bootstrap's survive the call), the statistics' out block
     int64_t jack_G = 0;                      // ... the last plspm_jackknife_device call whose records are on the handle (0: none)
     // measurement-model assessment of a plain bootstrap's replicates (kernels_assess.h; plspm_assess_*): records [assess_B x (A + 2)] in a buffer of their own,
     // indexed by the replicate's position in the whole call
     bool assess_on = false;                  // plspm_assess_enable
     Buf assess_rows, assess_fit;             // ... the replicates' records; the full-sample record + its solver problem (plspm_assess_fit)
     int64_t assess_B = 0;                    // ... the last plain bootstrap whose assessment records are on the handle (0: none)
-    int64_t assess_off = -1;                 // ... >= 0 while plspm_bootstrap() runs a sub-batch: its first replicate's position in the call (the buffer is the caller's to size)
     // MICOM records of a permutation call's splits (kernels_micom.h; plspm_micom_*): records [micom_B x (3 L + 2)] in a buffer of their own, indexed by the
     // permutation's position in the call; the pooled inputs (u, the diagonal blocks of R_0; plspm_micom.hip micom_prepare) once per upload
     bool micom_on = false;                   // plspm_micom_enable
@@ -179,7 +171,6 @@ struct plspm_model {
     enum { BLOB_MODEL = 0, BLOB_CATEGORICAL = 1, BLOB_HOC = 2, BLOB_COUNT = 3 };
     void* blobs[BLOB_COUNT] = {nullptr, nullptr, nullptr};     // descriptor blocks, one per call site (several small arrays uploaded as one: plspm_hip.hip upload_blob)
     void* group = nullptr;        // the plspm_group this handle currently belongs to (plspm_group.cpp)
-    hipEvent_t stop_event = nullptr;   // set by a caller of plspm_detail_bootstrap: the LAST kernel of a one-chunk metric batch signals it on completion (taken = reset to null)
     // plspm_bootstrap as sub-batches (plspm_bootstrap.hip): the copy stream the records of sub-batch k leave on while sub-batch k + 1 computes,
     // one event per sub-batch
     hipStream_t dl = nullptr;
@@ -190,9 +181,63 @@ struct plspm_model {
     std::string error;
 };
 
-// Core of plspm_bootstrap_device (plspm_bootstrap.hip): enqueue B replicates on the handle's stream, records written at `rows_out`
-// (pitch plspm_row_stride) or into the handle's own `rows` buffer when rows_out is NULL.  No host synchronisation for metric models.
-int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep_offset, const int32_t* d_idx, double* rows_out);
+// One call of the batch driver, described in full: nothing about a call lives on the handle while it runs.  The entry points of every kind fill one in
+// and hand it to plspm_detail_bootstrap; the properties of a kind that the driver, the int8 Gram and plspm_bootstrap() act on are the predicates below.
+struct BatchCall {
+    // where the problems' counts come from: PLAIN draws B resamples (Philox keys of `seed`, replicates rep_offset .., or the explicit rows at d_idx [B][N]);
+    // the other kinds bring a spec (host_internal.h) their own count kernel reads, and leave seed / rep_offset / d_idx at zero
+    enum Kind { PLAIN, PERMUTATION, STRATIFIED, CROSS_VALIDATION, JACKKNIFE } kind = PLAIN;
+    union { const PermSpec* perm = nullptr; const StratSpec* strat; const CvSpec* cv; const JackSpec* jack; };
+    int64_t B = 0, rep_offset = 0;       // B problems
+    uint64_t seed = 0;
+    const int32_t* d_idx = nullptr;
+    // where the results go: null = the handle's own buffer, which the driver sizes (records: `rows`, valid afterwards as rows_B; `status`; `iters`).  A caller's
+    // record buffer (pitch plspm_row_stride: a group's send buffer, a sub-batch's place in `rows`, the jackknife's jack_rows) is the caller's to size; caller's
+    // status / iteration buffers (the jackknife's) are grown by the driver
+    double* rows_out = nullptr;
+    plspm_model::Buf *status_out = nullptr, *iters_out = nullptr;
+    double* moments_out = nullptr;       // test seam (plspm_bootstrap_moments): the problems' dense moment matrices go here and the solver is skipped
+    int64_t assess_off = -1;             // >= 0: the call is a sub-batch of plspm_bootstrap() whose assessment records start here in the caller's assess_rows
+    // in: the LAST kernel of the batch may signal this event on completion instead of a hipEventRecord behind it (plspm_group.cpp: ~5 us of every step);
+    // out: a launch took it (the dense metric solvers do, plspm_fit.hip launch_signalling; every other route leaves the event to the caller)
+    hipEvent_t stop_event = nullptr;
+    bool stop_taken = false;
+};
+// The kind brings its own counts: the int8 route whatever "gram_path" / "i8_min_batch" say (its caller asked gram_counts_route_open), seven digit planes at
+// least (their counts add up to less than N: plspm_gram_i8.hip prepare_zs), and no draws on the aux stream.
+inline bool brings_counts(const BatchCall& c) { return c.kind != BatchCall::PLAIN; }
+// The call's launches may raise the device error word (index out of range / multiplicity above 127 / stream-K wait expired): explicit indices, draws inside a
+// group, the persistent Gram -- and data sets of fewer than 128 rows, which cannot exceed a multiplicity of 127 but take the short-N launch forms that share
+// the word with the index check.  A Philox call on the tiled launch neither raises nor needs to clear it.
+inline bool may_raise(const plspm_model* m, const BatchCall& c) { return c.d_idx != nullptr || c.kind == BatchCall::STRATIFIED || m->tune.i8_sched != 0 || m->N < 128; }
+// The call leaves the handle's records alone (the jackknife: buffers of its own, so that the bootstrap whose BCa intervals ask for it keeps its records).
+inline bool keeps_records(const BatchCall& c) { return c.kind == BatchCall::JACKKNIFE; }
+// Problems 2p / 2p + 1 are the two sides of split p of the resident rows: what a MICOM record compares.
+inline bool pairs_problems(const BatchCall& c) { return c.kind == BatchCall::PERMUTATION; }
+// The handle kinds the two-group tests, the cross-validation, the jackknife, the assessment and MICOM cover.
+inline bool plain_metric(const plspm_model* m) { return !m->nonmetric && !m->categorical && !m->n_ind && !m->nmx_K && !m->stage1 && !m->stage2; }
+// A plain bootstrap whose replicates get assessment records (plspm_assess_enable) if the owner of the bootstrap records takes them: a call into the handle's
+// own `rows` does, plspm_bootstrap() does for its sub-batches (assess_off), a group's shard does not.
+inline bool assessable(const plspm_model* m, const BatchCall& c) { return m->assess_on && plain_metric(m) && c.kind == BatchCall::PLAIN && !c.moments_out; }
+
+// The records on a handle, and the one place that voids them.  A batch call voids whatever went with the bootstrap records it replaces (REC_ROWS itself only
+// when it writes the handle's own `rows`); plspm_bootstrap_store replaces the bootstrap records from the host; an upload voids everything.
+enum : unsigned { REC_ROWS = 1, REC_CV = 2, REC_ASSESS = 4, REC_MICOM = 8, REC_JACK = 16, REC_ALL = 31 };
+inline void void_records(plspm_model* m, unsigned which) {
+    if (which & REC_ROWS) m->rows_B = 0;
+    if (which & REC_CV) m->cv_reps = 0;
+    if (which & REC_ASSESS) m->assess_B = 0;
+    if (which & REC_MICOM) m->micom_B = 0;
+    if (which & REC_JACK) m->jack_G = 0;
+}
+// (an entry point voids its own kind's records before it prepares the call -- plspm_cv_device REC_CV, plspm_jackknife_device REC_JACK -- and sets the count
+//  again behind the driver; so does plspm_bootstrap() with REC_ASSESS, which every one of its sub-batches voids here once more)
+inline void void_records(plspm_model* m, const BatchCall& c) {
+    if (!keeps_records(c)) void_records(m, REC_CV | REC_ASSESS | REC_MICOM | (c.rows_out ? 0u : REC_ROWS));
+}
+
+// The batch driver (plspm_bootstrap.hip): enqueue the call's problems on the handle's stream.  No host synchronisation for metric models.
+int plspm_detail_bootstrap(plspm_model* m, BatchCall& call);
 // plspm_group.cpp: a handle that is destroyed while bound to a group takes the group's hold on every handle with it.
 void plspm_detail_group_orphan(void* group);
 // Host -> device copy through the handle's pinned staging halves (chunked; returns when the source may be re-used).

@@ -18,8 +18,6 @@ __global__ void __launch_bounds__(256) moments_unpack_kernel(const double* __res
 }
 
 static inline int assess_width(const plspm_model* m) { return 4 * m->L + 3 * (m->L * (m->L - 1) / 2); }
-// the handle kinds the assessment covers: plain metric (as the two-group tests, the cross-validation and the jackknife)
-static inline bool assess_covers(const plspm_model* m) { return !m->nonmetric && !m->categorical && !m->n_ind && !m->nmx_K && !m->stage1 && !m->stage2; }
 
 // Assessment records of `nb` problems: their moment matrices at `gram` (dense: [(P+1) x cov_ld(P)] upper triangles; else tile-packed), their records at `rows`
 // (row_stride 0: one problem) -> out [nb x (A + 2)].  One wave per problem, four per workgroup (kernels_assess.h).
@@ -51,9 +49,14 @@ static int launch_assess(plspm_model* m, long nb, bool dense, const double* gram
     return 0;
 }
 
-int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep_offset, const int32_t* d_idx, double* rows_out) {
+int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
+    const int64_t B = call.B, rep_offset = call.rep_offset;
+    const int32_t* const d_idx = call.d_idx;
+    call.stop_taken = false;
     if (!m || B < 1 || rep_offset < 0 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: bad arguments (1 <= B <= 2^30, rep_offset >= 0)");
     if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_bootstrap: no data uploaded");
+    // (run_gram_i8 hands a count kernel rep_offset + b0 as its first problem)
+    if (brings_counts(call) && (rep_offset || d_idx)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: a call that brings its own counts takes no offset or indices");
     const long N = m->N;
     const bool lds_hist = (N <= 65535);        // N * 2 bytes of LDS histogram (16-bit counters, <= 128 KB); beyond that a global scratch slice per replicate
     HIPCHK(m, hipSetDevice(m->device));
@@ -66,24 +69,23 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     // counts the Gram consumed -- no second resample kernel, no (row,count) lists, no uint16 histograms (set_option "nm_counts8" 0: the
     // round-2 path, kept for A/B and for the cases below)
     // (a two-group permutation call, plspm_permute.hip, always takes the int8 route: its caller checked that the route is open; so do a cross-validation call, plspm_cv.hip, and a jackknife call, plspm_jackknife.hip)
-    const int gpath_plan = (m->perm || m->strat || m->cv || m->jack) ? 2 : choose_gram_path(m, B);
+    const int gpath = brings_counts(call) ? 2 : choose_gram_path(m, B);
     // (explicit index lists of at most 65,535 rows keep the round-3 arrangement -- uint16 histograms beside the lists they need anyway; beyond
     //  one window the int8 counts are the only dense multiplicities there are)
-    const bool counts8_plan = gpath_plan == 2 && (!d_idx || !lds_hist) && nm_counts8_possible(m);
+    const bool counts8_plan = gpath == 2 && (!d_idx || !lds_hist) && nm_counts8_possible(m);
     const bool want_dcnt = m->nonmetric && lds_hist && !counts8_plan;
     const long dcnt_stride = ((N + 15) & ~15L);
-    const int gpath = gpath_plan;
     m->last_gram_path = gpath;
     // metric models on the int8 Gram: a solver on dense moment matrices (solver_route.h) unless the model is outside every dense solver's class
     const SolverRoute route = metric_batch_route(route_shape(m), m->tune.solver_wave, m->tune.solver_quad, m->tune.solver_rows);
-    const bool rows_solver = gpath == 2 && route != ROUTE_LDS && !m->n_ind && !m->nonmetric && !m->moments_out;
+    const bool rows_solver = gpath == 2 && route != ROUTE_LDS && !m->n_ind && !m->nonmetric && !call.moments_out;
     // The non-metric route of the call as its batches will take it (nm_route.h): planned here with the int8 counts the call expects, and again per chunk with
     // what the chunk has (a chunk whose explicit indices made the int8 Gram fall back to the fp64 one has none) -- the same function, so buffers and launches agree.
     // round 6: Scale.NUM / RAW batches on the int8 route as one solver launch on dense moment matrices + a verification pass (plspm_nonmetric.hip
     // run_nonmetric_wave) -- needs the int8 counts the Gram consumed (explicit index lists of at most 65,535 rows keep the per-iteration launches and their
     // uint16 histograms)
     const NmPlan nm = m->nonmetric ? plan_nonmetric(m, B, counts8_plan, false, false, true) : NmPlan{};
-    const bool nm_wave = gpath == 2 && !m->moments_out && nm.num_one;
+    const bool nm_wave = gpath == 2 && !call.moments_out && nm.num_one;
     // the fp64 Gram walks (row,count) lists (explicit indices may fall back to it); so do the stop-rule passes of the non-metric solvers
     const bool need_lists = gpath == 1 || d_idx != nullptr || (m->nonmetric && !counts8_plan);
     const size_t kpad = (size_t)i8_kblocks(N) * 64;
@@ -101,37 +103,32 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     m->last_boot_passes = (int)((B + chunk - 1) / chunk);
     int rc;
     if (gpath == 2) {
-        if ((rc = prepare_zs(m, (m->perm || m->strat || m->cv || m->jack) ? 7 : 0))) return rc;      // (a permutation / stratified / cross-validation / jackknife call: seven planes at least, plspm_permute.hip, plspm_cv.hip, plspm_jackknife.hip)
+        if ((rc = prepare_zs(m, brings_counts(call) ? 7 : 0))) return rc;      // (a permutation / stratified / cross-validation / jackknife call: seven planes at least, plspm_permute.hip, plspm_cv.hip, plspm_jackknife.hip)
     }
     if (need_lists) {
         if ((rc = ensure(m, m->ent, (size_t)chunk * ent_stride * sizeof(int2)))) return rc;
         if ((rc = ensure(m, m->nent, (size_t)chunk * sizeof(int)))) return rc;
     }
     if ((rc = ensure(m, m->gram, (size_t)chunk * std::max<long>(psize, (rows_solver || nm_wave) ? cov_doubles(m->Pg) : 0) * sizeof(double)))) return rc;
-    // (a jackknife call writes records, status and iteration counts into buffers of its own: whatever the handle holds survives it)
-    if (!m->cv && !m->jack) m->cv_reps = 0;      // (the records of a cross-validation call are about to be replaced, or its status / iteration buffers reused)
+    // Whatever replaces the handle's bootstrap records voids the cross-validation, assessment and MICOM records that went with them (or whose status / iteration
+    // buffers are reused); a jackknife call writes into buffers of its own, and whatever the handle holds survives it.
+    void_records(m, call);
     // Assessment records (plspm_assess_enable) of a plain bootstrap: a call of its own (rows_out null) sizes the buffer and starts at record 0; a sub-batch of
-    // plspm_bootstrap() writes from its position in that call (m->assess_off; the buffer is plspm_bootstrap's).  Any other owner of the records (a group's
-    // shard) gets none.  Whatever replaces the handle's bootstrap records voids the assessment records that went with them.
-    const bool assess = m->assess_on && assess_covers(m) && !m->perm && !m->strat && !m->cv && !m->jack && !m->moments_out && (!rows_out || m->assess_off >= 0);
-    const bool assess_own = !rows_out;
-    const int64_t assess_base = assess_own ? 0 : m->assess_off;
+    // plspm_bootstrap() writes from its position in that call (call.assess_off; the buffer is plspm_bootstrap's).  Any other owner of the records (a group's
+    // shard) gets none.
+    const bool assess_own = !call.rows_out;
+    const bool assess = assessable(m, call) && (assess_own || call.assess_off >= 0);
+    const int64_t assess_base = assess_own ? 0 : call.assess_off;
     const int AS = assess_width(m) + 2;
-    if (!m->jack && m->assess_off <= 0) m->assess_B = 0;
     if (assess && assess_own && (rc = ensure(m, m->assess_rows, (size_t)B * AS * sizeof(double)))) return rc;
-    // MICOM records (plspm_micom_enable) of a permutation call: one per pair of problems, from position 0 of the call.  Whatever replaces the handle's records
-    // voids the MICOM records that went with them (a jackknife call keeps records of its own).
-    const bool micom = m->micom_on && m->perm && micom_covers(m) && !rows_out;
+    // MICOM records (plspm_micom_enable) of a permutation call: one per pair of problems, from position 0 of the call.
+    const bool micom = m->micom_on && pairs_problems(call) && plain_metric(m) && !call.rows_out;
     const int MS = 3 * m->L + 2;
-    if (!m->jack) m->micom_B = 0;
     if (micom && (rc = ensure(m, m->micom_rows, (size_t)(B / 2) * MS * sizeof(double)))) return rc;
-    if (!rows_out) {
-        m->rows_B = 0;
-        if ((rc = ensure(m, m->rows, (size_t)B * R * sizeof(double)))) return rc;
-        rows_out = (double*)m->rows.p;
-    }
-    plspm_model::Buf& status_buf = m->jack ? m->jack_status : m->status;
-    plspm_model::Buf& iters_buf = m->jack ? m->jack_iters : m->iters;
+    if (!call.rows_out && (rc = ensure(m, m->rows, (size_t)B * R * sizeof(double)))) return rc;
+    double* const rows_out = call.rows_out ? call.rows_out : (double*)m->rows.p;
+    plspm_model::Buf& status_buf = call.status_out ? *call.status_out : m->status;
+    plspm_model::Buf& iters_buf = call.iters_out ? *call.iters_out : m->iters;
     if ((rc = ensure(m, status_buf, (size_t)B * sizeof(int)))) return rc;
     if ((rc = ensure(m, iters_buf, (size_t)B * sizeof(int)))) return rc;
     const void* err_before = m->err.p;
@@ -140,30 +137,25 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     if (need_ghist && (rc = ensure(m, m->ghist, (size_t)chunk * N * sizeof(unsigned)))) return rc;
     if (want_dcnt && (rc = ensure(m, m->dcnt, (size_t)chunk * dcnt_stride * sizeof(unsigned short)))) return rc;
     m->dcnt_stride = dcnt_stride; m->dcnt_ready = want_dcnt;
-    // The error word (index out of range / multiplicity above 127 / stream-K wait expired) can only be raised by a call that brings explicit
-    // indices or runs the persistent Gram (data sets of fewer than 128 rows cannot exceed a multiplicity of 127; they are kept on the clearing
-    // side because their launches take the short-N forms that share the word with the index check): a Philox call on the tiled launch neither raises nor needs to clear it (the 4-byte memset is a
-    // kernel of its own on the stream: ~8 us with its gaps, 1.5 % of a 5,000-replicate step)
-    const bool may_raise = d_idx != nullptr || m->strat != nullptr || m->tune.i8_sched != 0 || N < 128;
-    if (!m->err_clean || may_raise) HIPCHK(m, hipMemsetAsync(m->err.p, 0, sizeof(int), m->stream));
-    m->err_clean = !may_raise;
+    // The error word is cleared only in front of a call that may raise it (model.h may_raise), or behind one that could have: the 4-byte memset is a kernel of
+    // its own on the stream, ~8 us with its gaps, 1.5 % of a 5,000-replicate step
+    const bool raises = may_raise(m, call);
+    if (!m->err_clean || raises) HIPCHK(m, hipMemsetAsync(m->err.p, 0, sizeof(int), m->stream));
+    m->err_clean = !raises;
     double* const gram_buf = (double*)m->gram.p;
     // round 5: all-indicator categorical models on the wave step -- the int8 product writes the uint16 count matrices the step streams itself (no fp64 slots, no
     // scatter pass: kernels_gram_i8.h IND epilogue, kernels_nonmetric.h nmg_kernel<4>); option "nm_direct16" 0: the packed fp64 matrices + nmg_kernel<3>
-    const bool want16 = gpath == 2 && m->nonmetric && !m->moments_out && nm.direct16;
+    const bool want16 = gpath == 2 && m->nonmetric && !call.moments_out && nm.direct16;
     if (want16 && (rc = ensure(m, m->gK16, (size_t)chunk * (m->P + 1) * ((m->P + 1 + 7) & ~7) * sizeof(unsigned short) + 64))) return rc;
-    hipEvent_t parked_stop = m->stop_event;
-    m->stop_event = nullptr;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t nb = std::min<int64_t>(chunk, B - b0);
-        if (b0 + nb >= B) m->stop_event = parked_stop;       // the last chunk's solver launch may signal the caller's event
         bool f64_gram = gpath == 1;
         const void* cd8 = nullptr;
         int cd8_MT = 0;
         bool wrote16 = false;
         if (gpath == 2) {
             bool fallback = false;
-            if ((rc = run_gram_i8(m, nb, seed, rep_offset + b0, d_idx ? d_idx + b0 * N : nullptr, gram_buf, rows_solver || nm_wave, &fallback, &cd8, &cd8_MT,
+            if ((rc = run_gram_i8(m, call, nb, b0, gram_buf, rows_solver || nm_wave, &fallback, &cd8, &cd8_MT,
                                   want16 ? (unsigned short*)m->gK16.p : nullptr, &wrote16))) return rc;
             f64_gram = fallback;
         }
@@ -174,11 +166,11 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
                 if ((rc = allow_lds(m, (const void*)resample_kernel, hist_bytes))) return rc;
                 ProfScope ps(m, PLSPM_K_RESAMPLE);
                 hipLaunchKernelGGL(resample_kernel, dim3((unsigned)nb), dim3(256), hist_bytes, m->stream, (int)N,
-                                   d_idx ? d_idx + b0 * N : nullptr, seed, rep_offset + b0, (int2*)m->ent.p, (int*)m->nent.p, ent_stride, (int*)m->err.p,
+                                   d_idx ? d_idx + b0 * N : nullptr, call.seed, rep_offset + b0, (int2*)m->ent.p, (int*)m->nent.p, ent_stride, (int*)m->err.p,
                                    want_dcnt ? (unsigned short*)m->dcnt.p : (unsigned short*)nullptr, dcnt_stride);
             } else {
                 ProfScope ps(m, PLSPM_K_RESAMPLE);
-                hipLaunchKernelGGL(resample_global_kernel, dim3((unsigned)nb), dim3(256), 0, m->stream, (int)N, d_idx ? d_idx + b0 * N : nullptr, seed,
+                hipLaunchKernelGGL(resample_global_kernel, dim3((unsigned)nb), dim3(256), 0, m->stream, (int)N, d_idx ? d_idx + b0 * N : nullptr, call.seed,
                                    rep_offset + b0, (unsigned*)m->ghist.p, (int2*)m->ent.p, (int*)m->nent.p, ent_stride, (int*)m->err.p);
             }
         }
@@ -186,9 +178,9 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
             ProfScope ps(m, PLSPM_K_GRAM);
             if ((rc = launch_gram_lists(m, nb, (const int2*)m->ent.p, (const int*)m->nent.p, ent_stride, (double*)m->gram.p))) return rc;
         }
-        if (m->moments_out) {                      // plspm_bootstrap_moments (test seam): the replicates' moment matrices, dense, no solver
+        if (call.moments_out) {                      // plspm_bootstrap_moments (test seam): the replicates' moment matrices, dense, no solver
             const int C = m->Pg + 1;
-            hipLaunchKernelGGL(moments_unpack_kernel, dim3((unsigned)nb), dim3(256), 0, m->stream, (const double*)m->gram.p, psize, m->T, C, m->moments_out + b0 * C * C);
+            hipLaunchKernelGGL(moments_unpack_kernel, dim3((unsigned)nb), dim3(256), 0, m->stream, (const double*)m->gram.p, psize, m->T, C, call.moments_out + b0 * C * C);
             continue;
         }
         SolverOut so{};
@@ -221,7 +213,8 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
             if ((rc = run_nonmetric(m, plan_nonmetric(m, nb, cd8 != nullptr, lists, wrote16, true), (const double*)m->gram.p, psize, so, ent_l, nent_l, ent_stride, nm_threads, cd8, cd8_MT))) return rc;
             continue;
         }
-        if ((rc = launch_batch_solver(m, nb, (rows_solver && !f64_gram) ? route : ROUTE_LDS, so))) return rc;
+        // (only the last chunk's solver launch may signal the caller's event)
+        if ((rc = launch_batch_solver(m, nb, (rows_solver && !f64_gram) ? route : ROUTE_LDS, so, b0 + nb >= B ? call.stop_event : nullptr, &call.stop_taken))) return rc;
         // the chunk's moment matrices are still in m->gram: dense where a dense solver read them, tile-packed for the LDS solver (fp64 Gram, int8 chunks that fell back)
         if (assess && (rc = launch_assess(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, (double*)m->assess_rows.p + (assess_base + b0) * AS))) return rc;
         // (a chunk holds whole 256-problem tiles: the pairs stay together, and the chunk that starts at problem b0 starts at permutation b0 / 2)
@@ -233,20 +226,28 @@ int plspm_detail_bootstrap(plspm_model* m, int64_t B, uint64_t seed, int64_t rep
     if (micom) m->micom_B = B / 2;
     return 0;
 }
-// (m->stop_event: only the last chunk's solver launch may take it -- plspm_detail_bootstrap parks it while earlier chunks run)
 
 static int fetch_segments(plspm_model* m, hipStream_t cs, const double* d_records, int32_t stride, const FetchSeg* segs, int nsegs, int64_t B_total, double* out, int32_t* status,
                           int32_t* iters);
+
+// explicit resample rows [B][N] of a host entry point (may be null) -> m->idx
+static int upload_idx(plspm_model* m, const int32_t* idx, int64_t B, const int32_t** d_idx) {
+    if (!idx) return 0;
+    const size_t bytes = (size_t)B * m->N * sizeof(int32_t);
+    if (int rc = ensure(m, m->idx, bytes)) return rc;
+    *d_idx = (const int32_t*)m->idx.p;
+    return plspm_detail_h2d(m, m->idx.p, idx, bytes);
+}
 
 extern "C" {
 
 int plspm_bootstrap_device(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offset, const int32_t* d_idx, void** d_out, void** d_status,
                            void** d_iters) {
-    int rc = plspm_detail_bootstrap(m, B, seed, rep_offset, d_idx, nullptr);
+    BatchCall call;
+    call.B = B; call.seed = seed; call.rep_offset = rep_offset; call.d_idx = d_idx;
+    int rc = plspm_detail_bootstrap(m, call);
     if (rc) return rc;
-    if (d_out) *d_out = m->rows.p;
-    if (d_status) *d_status = m->status.p;
-    if (d_iters) *d_iters = m->iters.p;
+    hand_out(m->rows, m->status, m->iters, d_out, d_status, d_iters);
     return 0;
 }
 
@@ -256,12 +257,7 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     HIPCHK(m, hipSetDevice(m->device));
     const int32_t* d_idx = nullptr;
     int rc;
-    if (idx) {
-        const size_t bytes = (size_t)B * m->N * sizeof(int32_t);
-        if ((rc = ensure(m, m->idx, bytes))) return rc;
-        if ((rc = plspm_detail_h2d(m, m->idx.p, idx, bytes))) return rc;
-        d_idx = (const int32_t*)m->idx.p;
-    }
+    if ((rc = upload_idx(m, idx, B, &d_idx))) return rc;
     // The call as SUB-BATCHES (round 5): the records of sub-batch k cross PCIe on a copy stream of the handle's own
     // -- and are unpacked into the caller's buffers -- while the kernels of sub-batch k + 1 run; only the last, smallest sub-batch's download is
     // exposed.  Metric models on Philox draws (explicit index lists and the non-metric iteration make host round trips inside the call as
@@ -270,32 +266,31 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     int64_t parts[kBootChunksMax];
     int nparts = 1;
     parts[0] = B;
-    // (a call whose launches may raise the device error word -- plspm_detail_bootstrap's may_raise -- clears that word at the start of every
+    // (a call whose launches may raise the device error word -- model.h may_raise, the driver's own test -- clears that word at the start of every
     //  sub-batch, which would wipe the bits of the sub-batch before: such calls run as one batch, one memset, one read)
-    const bool may_raise = m->tune.i8_sched != 0 || m->N < 128;
-    if (!d_idx && !m->nonmetric && !m->moments_out && !may_raise)
+    BatchCall call;
+    call.seed = seed; call.d_idx = d_idx;
+    if (!m->nonmetric && !may_raise(m, call))
         nparts = plspm_detail_chunk_plan(B, (int64_t)RS * (int64_t)sizeof(double), m->tune.boot_chunks, m->tune.boot_ratio, parts, m->tune.boot_align > 0 ? m->tune.boot_align : plspm_detail_round_units(m));
     if (nparts > 1) {
         if (!m->dl) HIPCHK(m, plspm_stream_acquire(&m->dl));
         for (int k = 0; k < nparts; ++k)
             if (!m->ev_part[k]) HIPCHK(m, hipEventCreateWithFlags(&m->ev_part[k], hipEventDisableTiming));
     }
-    m->rows_B = 0;
+    void_records(m, REC_ROWS | REC_ASSESS);
     if ((rc = ensure(m, m->rows, (size_t)B * RS * sizeof(double)))) return rc;
     double* const rows = (double*)m->rows.p;
-    // assessment records follow the sub-batches: one buffer for the whole call, every part writes from its first replicate's position (m->assess_off)
-    const bool assess = m->assess_on && assess_covers(m) && !m->moments_out;
-    m->assess_B = 0;
+    // assessment records follow the sub-batches: one buffer for the whole call, every part writes from its first replicate's position (call.assess_off)
+    const bool assess = assessable(m, call);
     if (assess && (rc = ensure(m, m->assess_rows, (size_t)B * (assess_width(m) + 2) * sizeof(double)))) return rc;
     int* h_err = (int*)m->h_flag + 10;                   // (+8: plspm_bootstrap_fetch, +9: run_gram_i8's look at the multiplicity flag of an explicit index list)
     h_err[0] = h_err[1] = 0;
     FetchSeg segs[kBootChunksMax];
     int64_t b0 = 0;
     for (int k = 0; k < nparts; ++k) {
-        if (assess) m->assess_off = b0;
-        rc = plspm_detail_bootstrap(m, parts[k], seed, rep_offset + b0, d_idx ? d_idx + b0 * m->N : nullptr, rows + b0 * RS);
-        m->assess_off = -1;
-        if (rc) return rc;
+        call.B = parts[k]; call.rep_offset = rep_offset + b0; call.d_idx = d_idx ? d_idx + b0 * m->N : nullptr;
+        call.rows_out = rows + b0 * RS; call.assess_off = assess ? b0 : -1;
+        if ((rc = plspm_detail_bootstrap(m, call))) return rc;
         if (k == nparts - 1) {
             // ONE error word, read with the last sub-batch: copied behind the last kernel, in front of the event its download waits for
             HIPCHK(m, hipMemcpyAsync(h_err, m->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
@@ -338,7 +333,7 @@ int plspm_bootstrap_store(plspm_model_t* m, const double* records, int64_t B) {
     if (!m || !records || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_store: bad arguments");
     HIPCHK(m, hipSetDevice(m->device));
     const size_t bytes = (size_t)B * plspm_row_stride(m) * sizeof(double);
-    m->rows_B = 0; m->micom_B = 0;
+    void_records(m, REC_ROWS | REC_MICOM);
     int rc;
     if ((rc = ensure(m, m->rows, bytes))) return rc;
     if ((rc = plspm_detail_h2d(m, m->rows.p, records, bytes))) return rc;
@@ -610,42 +605,70 @@ int plspm_bootstrap_moments(plspm_model_t* m, int64_t B, uint64_t seed, int64_t 
     HIPCHK(m, hipSetDevice(m->device));
     const int32_t* d_idx = nullptr;
     int rc;
-    if (idx) {
-        const size_t bytes = (size_t)B * m->N * sizeof(int32_t);
-        if ((rc = ensure(m, m->idx, bytes))) return rc;
-        if ((rc = plspm_detail_h2d(m, m->idx.p, idx, bytes))) return rc;
-        d_idx = (const int32_t*)m->idx.p;
-    }
+    if ((rc = upload_idx(m, idx, B, &d_idx))) return rc;
     const size_t C = (size_t)m->Pg + 1, bytes = (size_t)B * C * C * sizeof(double);
     double* d_out = nullptr;
     HIPCHK(m, plspm_dmalloc((void**)&d_out, bytes));
-    m->moments_out = d_out;
-    rc = plspm_detail_bootstrap(m, B, seed, rep_offset, d_idx, nullptr);
-    m->moments_out = nullptr;
+    BatchCall call;
+    call.B = B; call.seed = seed; call.rep_offset = rep_offset; call.d_idx = d_idx; call.moments_out = d_out;
+    rc = plspm_detail_bootstrap(m, call);
     if (!rc) {
         hipError_t e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, m->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
         if (e != hipSuccess) rc = fail(m, -(int)e, std::string("plspm_bootstrap_moments: ") + hipGetErrorString(e));
     } else hipStreamSynchronize(m->stream);
     plspm_dfree(d_out);
-    m->rows_B = 0;
+    void_records(m, REC_ROWS);      // (the driver left B in rows_B for records it never wrote; a call it refused for its arguments voids them too, as ever)
     return rc;
 }
 
 }  // extern "C"
 
-// ---- measurement-model assessment (DESIGN.md 5m): per-replicate records [alpha | rho_a | rho_c | ave | htmt | htmt2 | lv_cor | status | iterations]
-static int assess_state(plspm_model* m, int64_t B, const char* who) {
-    if (!m->assess_B || !m->assess_rows.p) return fail(m, PLSPM_E_STATE, std::string(who) + ": no assessment records on this handle (plspm_assess_enable, then a plain bootstrap; an upload or a later call replaced them)");
-    if (B != m->assess_B) return fail(m, PLSPM_E_ARG, std::string(who) + ": B differs from the last assessed bootstrap on this handle");
+// ---- side records (host_internal.h SideRecords): the state check, the fetch, the summary and the intervals that plspm_assess_* and plspm_micom_* share
+int side_state(plspm_model* m, const SideRecords& s, int64_t B, const char* who) {
+    if (!s.count || !s.buf.p) return fail(m, PLSPM_E_STATE, std::string(who) + s.none);
+    if (B != s.count) return fail(m, PLSPM_E_ARG, std::string(who) + s.differs);
     return 0;
+}
+static int side_scope(plspm_model* m, const SideRecords& s, const char* who) {
+    return s.plain_only && !plain_metric(m) ? fail(m, PLSPM_E_ARG, std::string(who) + ": plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)") : 0;
+}
+int side_fetch(plspm_model* m, const SideRecords& s, int64_t first, int64_t count, double* out, int32_t* status, const char* who) {
+    if (first < 0 || count < 1) return fail(m, PLSPM_E_ARG, std::string(who) + ": bad arguments");
+    if (int rc = side_scope(m, s, who)) return rc;
+    if (!s.count || !s.buf.p) return fail(m, PLSPM_E_STATE, std::string(who) + s.none);
+    if (first + count > s.count) return fail(m, PLSPM_E_ARG, std::string(who) + s.range);
+    HIPCHK(m, hipSetDevice(m->device));
+    return plspm_detail_fetch_records(m, (const double*)s.buf.p + first * (s.width + 2), count, s.width + 2, out, status, nullptr);
+}
+int side_summary(plspm_model* m, const SideRecords& s, int64_t B, const double* original, double* summary, int64_t* n_used, const char* who) {
+    if (!original || !summary || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, std::string(who) + ": bad arguments (1 <= B <= 2^30)");
+    int rc;
+    if ((rc = side_scope(m, s, who)) || (rc = side_state(m, s, B, who))) return rc;
+    return plspm_detail_summary(m, (const double*)s.buf.p, B, s.width + 2, s.width, original, summary, n_used);
+}
+int side_intervals(plspm_model* m, const SideRecords& s, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used, const char* who) {
+    if (!original || !out || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, std::string(who) + ": bad arguments (1 <= B <= 2^30)");
+    if (int rc = side_scope(m, s, who)) return rc;
+    if (method < CI_PERCENTILE || method >= CI_BCA) return fail(m, PLSPM_E_ARG, std::string(who) + s.method);
+    if (!(level > 0.0 && level < 1.0)) return fail(m, PLSPM_E_ARG, std::string(who) + ": level must lie strictly between 0 and 1");
+    if (int rc = side_state(m, s, B, who)) return rc;
+    return plspm_detail_intervals(m, (const double*)s.buf.p, B, s.width + 2, s.width, original, nullptr, method, level, out, n_used);
+}
+
+// ---- measurement-model assessment (DESIGN.md 5m): per-replicate records [alpha | rho_a | rho_c | ave | htmt | htmt2 | lv_cor | status | iterations]
+static SideRecords assess_records(const plspm_model* m) {
+    return {m->assess_rows, m->assess_B, assess_width(m), false,
+            ": no assessment records on this handle (plspm_assess_enable, then a plain bootstrap; an upload or a later call replaced them)",
+            ": B differs from the last assessed bootstrap on this handle", ": range exceeds the last assessed bootstrap's replicates",
+            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no assessment records, so there is no bca"};
 }
 
 extern "C" {
 
 int plspm_assess_enable(plspm_model_t* m, int32_t on) {
     if (!m) return fail(m, PLSPM_E_ARG, "plspm_assess_enable: no handle");
-    if (on && !assess_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_assess_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (on && !plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_assess_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
     m->assess_on = on != 0;
     return 0;
 }
@@ -654,7 +677,7 @@ int32_t plspm_assess_width(const plspm_model_t* m) { return m ? assess_width(m) 
 
 int plspm_assess_fit(plspm_model_t* m, double* out, int32_t* status) {
     if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_assess_fit: bad arguments");
-    if (!assess_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_assess_fit: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_assess_fit: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
     if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_assess_fit: no data uploaded");
     HIPCHK(m, hipSetDevice(m->device));
     const int RS = plspm_row_stride(m), A = assess_width(m);
@@ -683,30 +706,15 @@ int plspm_assess_fit(plspm_model_t* m, double* out, int32_t* status) {
 }
 
 int plspm_assess_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    if (!m || first < 0 || count < 1) return fail(m, PLSPM_E_ARG, "plspm_assess_fetch: bad arguments");
-    if (!m->assess_B || !m->assess_rows.p) return fail(m, PLSPM_E_STATE, "plspm_assess_fetch: no assessment records on this handle (plspm_assess_enable, then a plain bootstrap; an upload or a later call replaced them)");
-    if (first + count > m->assess_B) return fail(m, PLSPM_E_ARG, "plspm_assess_fetch: range exceeds the last assessed bootstrap's replicates");
-    HIPCHK(m, hipSetDevice(m->device));
-    const int AS = assess_width(m) + 2;
-    return plspm_detail_fetch_records(m, (const double*)m->assess_rows.p + first * AS, count, AS, out, status, nullptr);
+    return m ? side_fetch(m, assess_records(m), first, count, out, status, "plspm_assess_fetch") : fail(m, PLSPM_E_ARG, "plspm_assess_fetch: bad arguments");
 }
 
 int plspm_assess_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    if (!m || !original || !summary || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_assess_summary: bad arguments (1 <= B <= 2^30)");
-    int rc;
-    if ((rc = assess_state(m, B, "plspm_assess_summary"))) return rc;
-    const int A = assess_width(m);
-    return plspm_detail_summary(m, (const double*)m->assess_rows.p, B, A + 2, A, original, summary, n_used);
+    return m ? side_summary(m, assess_records(m), B, original, summary, n_used, "plspm_assess_summary") : fail(m, PLSPM_E_ARG, "plspm_assess_summary: bad arguments (1 <= B <= 2^30)");
 }
 
 int plspm_assess_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    if (!m || !original || !out || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_assess_intervals: bad arguments (1 <= B <= 2^30)");
-    if (method < CI_PERCENTILE || method >= CI_BCA) return fail(m, PLSPM_E_ARG, "plspm_assess_intervals: method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no assessment records, so there is no bca");
-    if (!(level > 0.0 && level < 1.0)) return fail(m, PLSPM_E_ARG, "plspm_assess_intervals: level must lie strictly between 0 and 1");
-    int rc;
-    if ((rc = assess_state(m, B, "plspm_assess_intervals"))) return rc;
-    const int A = assess_width(m);
-    return plspm_detail_intervals(m, (const double*)m->assess_rows.p, B, A + 2, A, original, nullptr, method, level, out, n_used);
+    return m ? side_intervals(m, assess_records(m), B, original, method, level, out, n_used, "plspm_assess_intervals") : fail(m, PLSPM_E_ARG, "plspm_assess_intervals: bad arguments (1 <= B <= 2^30)");
 }
 
 }  // extern "C"

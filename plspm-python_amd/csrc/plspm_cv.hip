@@ -9,8 +9,7 @@
 #include "wave_ops.h"
 #include "kernels_cv.h"
 
-int launch_cv_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
-    const CvSpec& cs = *m->cv;
+int launch_cv_counts(plspm_model* m, const CvSpec& cs, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
     const dim3 grid((unsigned)((nb + 7) / 8), (unsigned)((KB * 4 + CV_NT / 8 - 1) / (CV_NT / 8)));
     hipLaunchKernelGGL(cv_counts_kernel, grid, dim3(CV_NT), 0, m->stream, (int)m->N, KB, MT, cs.k, prob0, (int)nb, cs.d_fold, (uint4*)cd);
     HIPCHK(m, hipGetLastError());
@@ -29,8 +28,7 @@ static std::vector<int> cv_targets(const plspm_model* m) {
 static int cv_scope(plspm_model* m, const char* who) {
     if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, std::string(who) + ": no data uploaded");
     if (m->stage1 || m->stage2) return fail(m, PLSPM_E_ARG, std::string(who) + ": plain metric models only (this handle is part of a two-stage pair)");
-    if (m->nonmetric || m->categorical || m->n_ind || m->nmx_K)
-        return fail(m, PLSPM_E_ARG, std::string(who) + ": plain metric models only (no non-metric scales, no missing values)");
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, std::string(who) + ": plain metric models only (no non-metric scales, no missing values)");
     return 0;
 }
 
@@ -88,13 +86,8 @@ int plspm_cv_device(plspm_model_t* m, int64_t reps, int32_t k, uint64_t seed, in
     }
     HIPCHK(m, hipSetDevice(m->device));
     // the int8 route whatever "gram_path" / "i8_min_batch" say, seven planes at least (as plspm_permutation_device: the counts add up to n_train < N)
-    const int keep_path = m->tune.gram_path, keep_slices = m->tune.i8_slices;
-    m->tune.gram_path = 2;
-    if (keep_slices && keep_slices < 7) m->tune.i8_slices = 7;
-    const int route = choose_gram_path(m, reps * k);
-    m->tune.gram_path = keep_path; m->tune.i8_slices = keep_slices;
-    if (route != 2) return fail(m, PLSPM_E_LIMIT, "plspm_cv_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
-    m->cv_reps = 0;
+    if (!gram_counts_route_open(m)) return fail(m, PLSPM_E_LIMIT, "plspm_cv_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
+    void_records(m, REC_CV);
     const int C1 = m->P + 1;
     const long MS = (long)C1 * (C1 + 1) / 2;
     if ((rc = ensure(m, m->cv_fold, (size_t)reps * N))) return rc;
@@ -121,10 +114,9 @@ int plspm_cv_device(plspm_model_t* m, int64_t reps, int32_t k, uint64_t seed, in
     }
     HIPCHK(m, hipGetLastError());
     const CvSpec spec{reps, k, d_fold};
-    m->cv = &spec;
-    rc = plspm_detail_bootstrap(m, reps * k, 0, 0, nullptr, nullptr);       // problem r k + f = the rows of repetition rep_offset + r outside fold f
-    m->cv = nullptr;
-    if (rc) return rc;
+    BatchCall call;
+    call.kind = BatchCall::CROSS_VALIDATION; call.cv = &spec; call.B = reps * k;       // problem r k + f = the rows of repetition rep_offset + r outside fold f
+    if ((rc = plspm_detail_bootstrap(m, call))) return rc;
     {
         ProfScope ps(m, PLSPM_K_REDUCE);
         hipLaunchKernelGGL(cv_fold_moments_kernel, dim3((unsigned)(reps * k)), dim3(CV_NT), 0, m->stream, (const double*)m->d_Xa, m->PA, C1, (int)N, k, (const int*)m->cv_idx.p,
@@ -133,9 +125,7 @@ int plspm_cv_device(plspm_model_t* m, int64_t reps, int32_t k, uint64_t seed, in
     }
     HIPCHK(m, hipGetLastError());
     m->cv_reps = reps; m->cv_k = k;
-    if (d_out) *d_out = m->rows.p;
-    if (d_status) *d_status = m->status.p;
-    if (d_iters) *d_iters = m->iters.p;
+    hand_out(m->rows, m->status, m->iters, d_out, d_status, d_iters);
     return 0;
 }
 

@@ -166,19 +166,19 @@ int launch_nm_wave_solver(plspm_model* m, long nb, const SolverOut& so, double* 
     return rc;
 }
 
-// A dense solver launch that signals the caller's event (plspm_group.cpp: the `computed` event its collective waits for, parked in m->stop_event; a separate
-// hipEventRecord is one more packet the queue drains the device for, ~5 us of every step).  The rows / LDS solvers leave the event to their caller.
+// A dense solver launch that signals the caller's event `stop` (may be null; plspm_group.cpp: the `computed` event its collective waits for, BatchCall's
+// stop_event; a separate hipEventRecord is one more packet the queue drains the device for, ~5 us of every step) and says so in *taken.  The rows / LDS
+// solvers leave the event to their caller.
 template <class K>
-static int launch_signalling(plspm_model* m, K kernel, long nb, int threads, size_t lds, const SolverOut& so) {
+static int launch_signalling(plspm_model* m, K kernel, long nb, int threads, size_t lds, const SolverOut& so, hipEvent_t stop, bool* taken) {
     if (int rc = allow_lds(m, (const void*)kernel, lds)) return rc;
     ProfScope ps(m, PLSPM_K_SOLVER);
-    hipEvent_t stop = m->stop_event;
-    m->stop_event = nullptr;
+    if (stop) *taken = true;
     hipExtLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(threads), lds, m->stream, nullptr, stop, 0, make_desc(m), (const double*)m->gram.p, (long)cov_doubles(m->Pg), so);
     return 0;
 }
 
-int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const SolverOut& so_in) {
+int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const SolverOut& so_in, hipEvent_t stop, bool* stop_taken) {
     SolverOut so = so_in;
     int rc = 0;
     const double* gram_buf = (const double*)m->gram.p;
@@ -189,15 +189,15 @@ int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const Solver
 #endif
     switch (route) {
         case ROUTE_WAVE16_8:      // (round 5: V in LDS, the product stream's second copy w V for the Q sums, a folded into E; Mode-B blocks: a second instantiation)
-            rc = launch_signalling(m, modeb ? solver_wave16_kernel<8, true> : solver_wave16_kernel<8, false>, nb, 64, (size_t)wave16_ws_doubles<8>(m->L, m->kmax, m->n_chol) * sizeof(double), so); break;
+            rc = launch_signalling(m, modeb ? solver_wave16_kernel<8, true> : solver_wave16_kernel<8, false>, nb, 64, (size_t)wave16_ws_doubles<8>(m->L, m->kmax, m->n_chol) * sizeof(double), so, stop, stop_taken); break;
         case ROUTE_WAVE:          // (fixed lane roles, solver_wave.h; Mode-B blocks keep their inverses behind the workspace)
-            rc = launch_signalling(m, modeb ? solver_wave_kernel<8, true> : solver_wave_kernel<8, false>, nb, 64, (size_t)wave_ws_doubles<8>(m->n_chol) * sizeof(double), so); break;
+            rc = launch_signalling(m, modeb ? solver_wave_kernel<8, true> : solver_wave_kernel<8, false>, nb, 64, (size_t)wave_ws_doubles<8>(m->n_chol) * sizeof(double), so, stop, stop_taken); break;
         case ROUTE_WAVE16_16:     // (four matrix entries per pair lane)
-            rc = launch_signalling(m, modeb ? solver_wave16_kernel<16, true> : solver_wave16_kernel<16, false>, nb, 64, (size_t)wave16_ws_doubles<16>(m->L, m->kmax, m->n_chol) * sizeof(double), so); break;
+            rc = launch_signalling(m, modeb ? solver_wave16_kernel<16, true> : solver_wave16_kernel<16, false>, nb, 64, (size_t)wave16_ws_doubles<16>(m->L, m->kmax, m->n_chol) * sizeof(double), so, stop, stop_taken); break;
         case ROUTE_WAVE16_32:     // (sixteen matrix entries per pair lane, three problems per CU)
-            rc = launch_signalling(m, solver_wave16_kernel<32, false>, nb, 64, (size_t)wave16_ws_doubles<32>(m->L, m->kmax, 0) * sizeof(double), so); break;
+            rc = launch_signalling(m, solver_wave16_kernel<32, false>, nb, 64, (size_t)wave16_ws_doubles<32>(m->L, m->kmax, 0) * sizeof(double), so, stop, stop_taken); break;
         case ROUTE_QUAD:
-            rc = launch_signalling(m, solver_quad_kernel<16>, nb, 256, (size_t)quad_ws_doubles<16>(m->L, m->kmax) * sizeof(double), so); break;
+            rc = launch_signalling(m, solver_quad_kernel<16>, nb, 256, (size_t)quad_ws_doubles<16>(m->L, m->kmax) * sizeof(double), so, stop, stop_taken); break;
         case ROUTE_ROWS_SPLIT:    // (two threads per MV on either side of a block boundary, rows_split_block)
         case ROUTE_ROWS: {
             const bool split = route == ROUTE_ROWS_SPLIT;

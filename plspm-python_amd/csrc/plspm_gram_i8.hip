@@ -24,23 +24,26 @@ bool nm_counts8_possible(const plspm_model* m) {
     return m->nonmetric && m->tune.nm_counts8 != 0 && m->tune.resample_aux == 0 && !m->aux && m->tune.i8_shape == 16 && m->nmx_K == 0 &&
            nm_dense_lds(plan_shape(m), m->tune.conv_pass, nullptr) != 0 && (!m->stage2 || nm_dense_lds(plan_shape(m->stage2), m->stage2->tune.conv_pass, nullptr) != 0);
 }
-int choose_gram_path(const plspm_model* m, int64_t B) {
-    if (m->tune.gram_path == 1) return 1;
+// The int8 route is closed for the resident data at `slices` digit planes (0: the automatic count, budgeted as seven) -- whatever the options would prefer.
+bool gram_i8_closed(const plspm_model* m, int slices) {
     // every model's replicates start from the moment matrix of the uploaded columns (metric, mean-imputed, non-metric, categorical
     // indicator columns, incomplete rows zeroed, first stage of a HOC pair).  The LDS histogram bounds N; int32 accumulators need
     // 128 N < 2^31.
     // (int32 accumulators: |sum_i c_bi d_is| <= 128 sum_i c_bi = 128 N < 2^31, i.e. N < 2^24; the resample counts come from an LDS
     // histogram of 65,536 rows per workgroup, larger data sets take several windows per replicate)
-    if (m->stage1 || m->N >= (1 << 24) || m->N < 2) return 1;
+    if (m->stage1 || m->N >= (1 << 24) || m->N < 2) return true;
     // non-metric models beyond one 16-bit histogram window: the int8 route when their stop-rule passes can read the Gram's int8 counts
     // (on-device draws, and -- round 4 -- explicit index lists too: windowed 16-bit histograms, resample_i8_kernel; a chunk that carries a
     // multiplicity above 127 falls back to row lists from the global histogram, the fp64 Gram and the gathering pass, as for metric models);
     // else the fp64 route
-    if (m->nonmetric && m->N > 65535 && !nm_counts8_possible(m)) return 1;
-    const size_t zs_bytes = (size_t)(i8_kblocks(m->N) + I8_SLACK_KB) * (size_t)(((i8_pairs(m) + 31) / 32) * 2 * (m->tune.i8_slices ? m->tune.i8_slices : 7)) * 1024;
-    if (zs_bytes > kZsBudget) return 1;
-    if (m->tune.gram_path == 2) return 2;
-    return B >= m->tune.i8_min_batch ? 2 : 1;
+    if (m->nonmetric && m->N > 65535 && !nm_counts8_possible(m)) return true;
+    const size_t zs_bytes = (size_t)(i8_kblocks(m->N) + I8_SLACK_KB) * (size_t)(((i8_pairs(m) + 31) / 32) * 2 * (slices ? slices : 7)) * 1024;
+    return zs_bytes > kZsBudget;
+}
+// ... and the policy on top: "gram_path" 1 / 2 decides where the route is open, else batches of "i8_min_batch" replicates and more take it.
+int choose_gram_path(const plspm_model* m, int64_t B) {
+    if (m->tune.gram_path == 1 || gram_i8_closed(m, m->tune.i8_slices)) return 1;
+    return (m->tune.gram_path == 2 || B >= m->tune.i8_min_batch) ? 2 : 1;
 }
 
 // Digit planes + pair tables of the resident data (once per upload / digit count).
@@ -247,8 +250,11 @@ static bool i8_mix_plan(long ct, long ntx, int cus, bool mix, int* tall, int* sh
 // flag before the product and reports *fallback so that the caller takes the fp64 Gram for this chunk.
 // out16 (round 5, may be null): where an all-indicator data set's products -- co-occurrence counts -- may leave as uint16 [nb][C][ld16], upper triangle, instead
 // of fp64 slots at `out`; *wrote16 tells whether this call did (the one-plane launch on 0/1 data; any other launch writes `out` as ever).
-int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const int32_t* d_idx, double* out, bool dense, bool* fallback,
+int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, double* out, bool dense, bool* fallback,
                 const void** counts, int* counts_MT, unsigned short* out16, bool* wrote16) {
+    const uint64_t seed = call.seed;
+    const int64_t rep0 = call.rep_offset + b0;
+    const int32_t* const d_idx = call.d_idx ? call.d_idx + b0 * m->N : nullptr;
     *fallback = false;
     if (counts) *counts = nullptr;
     if (wrote16) *wrote16 = false;
@@ -336,7 +342,7 @@ int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const i
     plspm_model::Buf& cd = slot ? m->cd1 : m->cd;
     const size_t cd_bytes = (size_t)MT * 16 * ((size_t)KB + I8_SLACK_KB) * 64;
     if (cd_bytes > cd.cap) { if (m->aux) HIPCHK(m, hipStreamSynchronize(m->aux)); if ((rc = ensure(m, cd, cd_bytes))) return rc; m->cdfree_set[slot] = false; }
-    if (!d_idx && !m->perm && !m->strat && !m->cv && !m->jack && m->aux) {
+    if (!d_idx && !brings_counts(call) && m->aux) {
         // Philox draws: on the low-priority stream, as soon as the Gram that last read this buffer is done -- i.e. beside the Gram and the
         // solver of the PREVIOUS call when the host runs ahead; this call's Gram waits for the counts by event
         if (m->cdfree_set[slot]) HIPCHK(m, hipStreamWaitEvent(m->aux, m->ev_cdfree[slot], 0));
@@ -352,14 +358,18 @@ int run_gram_i8(plspm_model* m, int64_t nb, uint64_t seed, int64_t rep0, const i
         // explicit index lists (test / parity seam) arrive on the main stream: drawn there, and the host looks at the flag
         if (m->aux && m->cdfree_set[slot]) HIPCHK(m, hipStreamWaitEvent(m->stream, m->ev_cdfree[slot], 0));
         ProfScope ps(m, PLSPM_K_RESAMPLE);
-        if (m->perm) { if ((rc = launch_perm_counts(m, nb, rep0, MT, KB, cd.p))) return rc; }      // (two-group permutation test: 0/1 counts of random splits, plspm_permute.hip)
-        else if (m->strat) { if ((rc = launch_strat_counts(m, nb, rep0, MT, KB, cd.p))) return rc; }      // (... its stratified bootstrap: draws inside each group)
-        else if (m->cv) { if ((rc = launch_cv_counts(m, nb, rep0, MT, KB, cd.p))) return rc; }      // (cross-validation: 0/1 counts of the training folds, plspm_cv.hip)
-        else if (m->jack) { if ((rc = launch_jack_counts(m, nb, rep0, MT, KB, cd.p))) return rc; }      // (jackknife: 0/1 counts of the rows a problem keeps, plspm_jackknife.hip)
-        else
-        if (hist_nib) hipLaunchKernelGGL(resample_i8_nib_kernel, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->stream, (int)m->N, KB, MT, seed, rep0, (uint4*)cd.p, (int*)m->err.p, nib_slow);
-        else
-        hipLaunchKernelGGL(resample_k, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->stream, (int)m->N, KB, MT, m->tune.i8_shape, d_idx, seed, rep0, (uint4*)cd.p, (int*)m->err.p);
+        rc = 0;
+        switch (call.kind) {      // (the kinds that bring their own counts: rep_offset is 0, so rep0 is the chunk's first problem)
+            case BatchCall::PERMUTATION: rc = launch_perm_counts(m, *call.perm, nb, rep0, MT, KB, cd.p); break;           // 0/1 counts of random splits, plspm_permute.hip
+            case BatchCall::STRATIFIED: rc = launch_strat_counts(m, *call.strat, nb, rep0, MT, KB, cd.p); break;          // ... its stratified bootstrap: draws inside each group
+            case BatchCall::CROSS_VALIDATION: rc = launch_cv_counts(m, *call.cv, nb, rep0, MT, KB, cd.p); break;         // 0/1 counts of the training folds, plspm_cv.hip
+            case BatchCall::JACKKNIFE: rc = launch_jack_counts(m, *call.jack, nb, rep0, MT, KB, cd.p); break;            // 0/1 counts of the rows a problem keeps, plspm_jackknife.hip
+            case BatchCall::PLAIN:
+                if (hist_nib) hipLaunchKernelGGL(resample_i8_nib_kernel, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->stream, (int)m->N, KB, MT, seed, rep0, (uint4*)cd.p, (int*)m->err.p, nib_slow);
+                else hipLaunchKernelGGL(resample_k, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->stream, (int)m->N, KB, MT, m->tune.i8_shape, d_idx, seed, rep0, (uint4*)cd.p, (int*)m->err.p);
+                break;
+        }
+        if (rc) return rc;
     }
     if (d_idx) {
         int* h_err = (int*)m->h_flag + 9;

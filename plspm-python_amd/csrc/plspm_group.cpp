@@ -652,11 +652,11 @@ int plspm_group_bootstrap(plspm_group_t* g, int64_t B, uint64_t seed, int64_t re
             double* send = (double*)l.send[s].p + sub_off[k] * RS;
             // (a full shard: its last kernel signals `computed` itself; a ragged one records the event behind the padding below)
             const bool fused = g->opt_lean_events && count == sub_cap[k] && count > 0;
-            m->stop_event = fused ? l.computed[s][k] : nullptr;
-            if (count > 0 && (shard_rc[i] = plspm_detail_bootstrap(m, count, seed, rep_offset + sub_first[k] + first, nullptr, send))) { m->stop_event = nullptr; return; }
-            const bool signalled = fused && m->stop_event == nullptr;      // (taken by the solver launch; left in place by routes that do not end in it)
-            m->stop_event = nullptr;
-            if (signalled) { shard_done[i] = k + 1; continue; }
+            BatchCall call;
+            call.B = count; call.seed = seed; call.rep_offset = rep_offset + sub_first[k] + first; call.rows_out = send;
+            call.stop_event = fused ? l.computed[s][k] : nullptr;
+            if (count > 0 && (shard_rc[i] = plspm_detail_bootstrap(m, call))) return;
+            if (call.stop_taken) { shard_done[i] = k + 1; continue; }      // (taken by the solver launch; left alone by routes that do not end in it)
             if (count < sub_cap[k] && hipMemsetAsync(send + count * RS, 0xFF, (size_t)(sub_cap[k] - count) * RS * sizeof(double), m->stream) != hipSuccess) {   // NaN status: not a replicate
                 shard_rc[i] = fail(m, PLSPM_E_STATE, "hipMemsetAsync failed"); return;
             }
@@ -888,7 +888,7 @@ int plspm_group_adopt(plspm_group_t* g) {
     plspm_model* m = l.m;
     const int RS = plspm_row_stride(m);
     GHIP(g, hipSetDevice(m->device));
-    m->rows_B = 0;
+    void_records(m, REC_ROWS);
     int rc = check_peer_shards(g);             // (no extra round trip in the Plspm flow: plspm_group_summary ran -- and waited -- before)
     if (rc) return rc;
     rc = ensure(m, m->rows, (size_t)g->last_B * RS * sizeof(double));

@@ -7,8 +7,7 @@
 #include "wave_ops.h"
 #include "kernels_jack.h"
 
-int launch_jack_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
-    const JackSpec& js = *m->jack;
+int launch_jack_counts(plspm_model* m, const JackSpec& js, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
     const dim3 grid((unsigned)((nb + 7) / 8), (unsigned)((KB * 4 + JACK_NT / 8 - 1) / (JACK_NT / 8)));
     hipLaunchKernelGGL(jack_counts_kernel, grid, dim3(JACK_NT), 0, m->stream, (int)m->N, KB, MT, (int)js.G, prob0, (int)nb, (uint4*)cd);
     HIPCHK(m, hipGetLastError());
@@ -28,8 +27,7 @@ int plspm_jackknife_device(plspm_model_t* m, int64_t G, void** d_out, void** d_s
     if (!m) return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: no handle");
     if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_jackknife_device: no data uploaded");
     if (m->stage1 || m->stage2) return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: plain metric models only (this handle is part of a two-stage pair)");
-    if (m->nonmetric || m->categorical || m->n_ind || m->nmx_K)
-        return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: plain metric models only (no non-metric scales, no missing values)");
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: plain metric models only (no non-metric scales, no missing values)");
     const int64_t N = m->N;
     if (G < 2 || G > N || N - (N + G - 1) / G < 4)
         return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: bad G (2 <= G <= N, and every problem keeps at least four rows)");
@@ -37,24 +35,17 @@ int plspm_jackknife_device(plspm_model_t* m, int64_t G, void** d_out, void** d_s
     HIPCHK(m, hipSetDevice(m->device));
     // the int8 route whatever "gram_path" / "i8_min_batch" say, seven planes at least (as plspm_permutation_device: the counts add up to less than N, and
     // the statistic is a difference of nearly equal estimates)
-    const int keep_path = m->tune.gram_path, keep_slices = m->tune.i8_slices;
-    m->tune.gram_path = 2;
-    if (keep_slices && keep_slices < 7) m->tune.i8_slices = 7;
-    const int route = choose_gram_path(m, G);
-    m->tune.gram_path = keep_path; m->tune.i8_slices = keep_slices;
-    if (route != 2) return fail(m, PLSPM_E_LIMIT, "plspm_jackknife_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
-    m->jack_G = 0;
+    if (!gram_counts_route_open(m)) return fail(m, PLSPM_E_LIMIT, "plspm_jackknife_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
+    void_records(m, REC_JACK);
     int rc;
     if ((rc = ensure(m, m->jack_rows, (size_t)G * plspm_row_stride(m) * sizeof(double)))) return rc;
     const JackSpec spec{G};
-    m->jack = &spec;
-    rc = plspm_detail_bootstrap(m, G, 0, 0, nullptr, (double*)m->jack_rows.p);       // problem g = the rows i with i % G != g
-    m->jack = nullptr;
-    if (rc) return rc;
+    BatchCall call;
+    call.kind = BatchCall::JACKKNIFE; call.jack = &spec; call.B = G;       // problem g = the rows i with i % G != g
+    call.rows_out = (double*)m->jack_rows.p; call.status_out = &m->jack_status; call.iters_out = &m->jack_iters;
+    if ((rc = plspm_detail_bootstrap(m, call))) return rc;
     m->jack_G = G;
-    if (d_out) *d_out = m->jack_rows.p;
-    if (d_status) *d_status = m->jack_status.p;
-    if (d_iters) *d_iters = m->jack_iters.p;
+    hand_out(m->jack_rows, m->jack_status, m->jack_iters, d_out, d_status, d_iters);
     return 0;
 }
 

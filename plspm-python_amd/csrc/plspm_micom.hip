@@ -64,17 +64,19 @@ int launch_micom(plspm_model* m, long nperm, bool dense, const double* gram, con
     return 0;
 }
 
-static int micom_state(plspm_model* m, int64_t B, const char* who) {
-    if (!m->micom_B || !m->micom_rows.p) return fail(m, PLSPM_E_STATE, std::string(who) + ": no MICOM records on this handle (plspm_micom_enable, then plspm_permutation_device; an upload or a later call replaced them)");
-    if (B != m->micom_B) return fail(m, PLSPM_E_ARG, std::string(who) + ": B differs from the last MICOM permutation call on this handle");
-    return 0;
+// the handle's MICOM records as the entry points below share them with the assessment's (host_internal.h SideRecords)
+static SideRecords micom_records(const plspm_model* m) {
+    return {m->micom_rows, m->micom_B, micom_width(m), true,
+            ": no MICOM records on this handle (plspm_micom_enable, then plspm_permutation_device; an upload or a later call replaced them)",
+            ": B differs from the last MICOM permutation call on this handle", ": range exceeds the last MICOM permutation call's permutations",
+            ": method must be 0 (percentile), 1 (basic) or 2 (bc)"};
 }
 
 extern "C" {
 
 int plspm_micom_enable(plspm_model_t* m, int32_t on) {
     if (!m) return fail(m, PLSPM_E_ARG, "plspm_micom_enable: no handle");
-    if (on && !micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (on && !plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
     m->micom_on = on != 0;
     return 0;
 }
@@ -82,40 +84,22 @@ int plspm_micom_enable(plspm_model_t* m, int32_t on) {
 int32_t plspm_micom_width(const plspm_model_t* m) { return m ? micom_width(m) : 0; }
 
 int plspm_micom_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    if (!m || first < 0 || count < 1) return fail(m, PLSPM_E_ARG, "plspm_micom_fetch: bad arguments");
-    if (!micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_fetch: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (!m->micom_B || !m->micom_rows.p) return fail(m, PLSPM_E_STATE, "plspm_micom_fetch: no MICOM records on this handle (plspm_micom_enable, then plspm_permutation_device; an upload or a later call replaced them)");
-    if (first + count > m->micom_B) return fail(m, PLSPM_E_ARG, "plspm_micom_fetch: range exceeds the last MICOM permutation call's permutations");
-    HIPCHK(m, hipSetDevice(m->device));
-    const int MS = micom_width(m) + 2;
-    return plspm_detail_fetch_records(m, (const double*)m->micom_rows.p + first * MS, count, MS, out, status, nullptr);
+    return m ? side_fetch(m, micom_records(m), first, count, out, status, "plspm_micom_fetch") : fail(m, PLSPM_E_ARG, "plspm_micom_fetch: bad arguments");
 }
 
 int plspm_micom_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    if (!m || !original || !summary || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_micom_summary: bad arguments (1 <= B <= 2^30)");
-    if (!micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_summary: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    int rc;
-    if ((rc = micom_state(m, B, "plspm_micom_summary"))) return rc;
-    const int W = micom_width(m);
-    return plspm_detail_summary(m, (const double*)m->micom_rows.p, B, W + 2, W, original, summary, n_used);
+    return m ? side_summary(m, micom_records(m), B, original, summary, n_used, "plspm_micom_summary") : fail(m, PLSPM_E_ARG, "plspm_micom_summary: bad arguments (1 <= B <= 2^30)");
 }
 
 int plspm_micom_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    if (!m || !original || !out || B < 1 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_micom_intervals: bad arguments (1 <= B <= 2^30)");
-    if (!micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_intervals: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (method < 0 || method > 2) return fail(m, PLSPM_E_ARG, "plspm_micom_intervals: method must be 0 (percentile), 1 (basic) or 2 (bc)");
-    if (!(level > 0.0 && level < 1.0)) return fail(m, PLSPM_E_ARG, "plspm_micom_intervals: level must lie strictly between 0 and 1");
-    int rc;
-    if ((rc = micom_state(m, B, "plspm_micom_intervals"))) return rc;
-    const int W = micom_width(m);
-    return plspm_detail_intervals(m, (const double*)m->micom_rows.p, B, W + 2, W, original, nullptr, method, level, out, n_used);
+    return m ? side_intervals(m, micom_records(m), B, original, method, level, out, n_used, "plspm_micom_intervals") : fail(m, PLSPM_E_ARG, "plspm_micom_intervals: bad arguments (1 <= B <= 2^30)");
 }
 
 int plspm_micom_counts(plspm_model_t* m, int64_t B, const double* observed, int64_t* below, int64_t* exceed, int64_t* n_used) {
     if (!m || B < 1 || !observed || !below || !exceed) return fail(m, PLSPM_E_ARG, "plspm_micom_counts: bad arguments");
-    if (!micom_covers(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_counts: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_micom_counts: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
     int rc;
-    if ((rc = micom_state(m, B, "plspm_micom_counts"))) return rc;
+    if ((rc = side_state(m, micom_records(m), B, "plspm_micom_counts"))) return rc;
     HIPCHK(m, hipSetDevice(m->device));
     const int W = micom_width(m);
     // [observed W | below W | exceed W | valid records]

@@ -12,8 +12,7 @@
 #include "kernels_permute.h"
 #include "kernels_strat.h"
 
-int launch_perm_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
-    const PermSpec& ps = *m->perm;
+int launch_perm_counts(plspm_model* m, const PermSpec& ps, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
     const int64_t np = nb / 2, p0 = prob0 / 2;               // (plspm_detail_bootstrap cuts a batch into whole 256-problem tiles: pairs stay together)
     const int N = (int)m->N;
     int rc;
@@ -35,8 +34,7 @@ int launch_perm_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB
     return 0;
 }
 
-int launch_strat_counts(plspm_model* m, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
-    const StratSpec& ss = *m->strat;
+int launch_strat_counts(plspm_model* m, const StratSpec& ss, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
     const int N = (int)m->N, n_a = (int)ss.n_a;
     const int ng_max = std::max(n_a, N - n_a);
     const size_t hist_bytes = (size_t)std::min(KB, STRAT_HIST_KB) * 32 * sizeof(unsigned);
@@ -94,7 +92,7 @@ int plspm_stratified_bootstrap_device(plspm_model_t* m, int64_t B, uint64_t seed
     if (!m || B < 1 || B > ((int64_t)1 << 29) || rep_offset < 0 || rep_offset > ((int64_t)1 << 61) || !member)
         return fail(m, PLSPM_E_ARG, "plspm_stratified_bootstrap_device: bad arguments (1 <= B <= 2^29, rep_offset >= 0, member required)");
     if (!m->d_Xa || m->N < 4) return fail(m, PLSPM_E_STATE, "plspm_stratified_bootstrap_device: no data uploaded");
-    if (m->nonmetric || m->categorical || m->n_ind || m->nmx_K || m->stage1 || m->stage2)
+    if (!plain_metric(m))
         return fail(m, PLSPM_E_ARG, "plspm_stratified_bootstrap_device: plain metric models only (no non-metric scales, no missing values, no two-stage pair)");
     if (m->tune.i8_shape != 16) return fail(m, PLSPM_E_ARG, "plspm_stratified_bootstrap_device: needs the 16x16x64 layout of the int8 Gram (i8_shape 16)");
     const int64_t N = m->N;
@@ -104,12 +102,7 @@ int plspm_stratified_bootstrap_device(plspm_model_t* m, int64_t B, uint64_t seed
     if (n_a < 2 || N - n_a < 2) return fail(m, PLSPM_E_ARG, "plspm_stratified_bootstrap_device: each group needs at least two rows");
     HIPCHK(m, hipSetDevice(m->device));
     // the int8 route whatever "gram_path" / "i8_min_batch" say, seven planes at least (as plspm_permutation_device)
-    const int keep_path = m->tune.gram_path, keep_slices = m->tune.i8_slices;
-    m->tune.gram_path = 2;
-    if (keep_slices && keep_slices < 7) m->tune.i8_slices = 7;
-    const int route = choose_gram_path(m, 2 * B);
-    m->tune.gram_path = keep_path; m->tune.i8_slices = keep_slices;
-    if (route != 2) return fail(m, PLSPM_E_LIMIT, "plspm_stratified_bootstrap_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
+    if (!gram_counts_route_open(m)) return fail(m, PLSPM_E_LIMIT, "plspm_stratified_bootstrap_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
     int rc;
     const size_t row_bytes = (size_t)N * sizeof(int32_t);
     if (!m->strat_rows.p || m->strat_member.size() != (size_t)N || !std::equal(member, member + N, m->strat_member.begin())) {
@@ -137,19 +130,16 @@ int plspm_stratified_bootstrap_device(plspm_model_t* m, int64_t B, uint64_t seed
         d_draws = (const int32_t*)m->strat_draws.p;
     }
     const StratSpec spec{seed, rep_offset, n_a, (const int32_t*)m->strat_rows.p, d_draws};
-    m->strat = &spec;
-    rc = plspm_detail_bootstrap(m, 2 * B, 0, 0, nullptr, nullptr);       // problems 2p / 2p + 1 = the groups of resample rep_offset + p
-    m->strat = nullptr;
-    if (rc) return rc;
+    BatchCall call;
+    call.kind = BatchCall::STRATIFIED; call.strat = &spec; call.B = 2 * B;       // problems 2p / 2p + 1 = the groups of resample rep_offset + p
+    if ((rc = plspm_detail_bootstrap(m, call))) return rc;
     // the error word (cleared by the driver in front of the counts): a multiplicity above 127 never wraps silently
     int* h_err = (int*)m->h_flag + 9;
     HIPCHK(m, hipMemcpyAsync(h_err, m->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));
-    if (*h_err & 2) { m->rows_B = 0; return fail(m, PLSPM_E_LIMIT, "plspm_stratified_bootstrap_device: a multiplicity exceeded 127 on the int8 Gram path"); }
-    if (*h_err) { m->rows_B = 0; return fail(m, PLSPM_E_STATE, "plspm_stratified_bootstrap_device: the device reported error bits " + std::to_string(*h_err)); }
-    if (d_out) *d_out = m->rows.p;
-    if (d_status) *d_status = m->status.p;
-    if (d_iters) *d_iters = m->iters.p;
+    if (*h_err & 2) { void_records(m, REC_ROWS); return fail(m, PLSPM_E_LIMIT, "plspm_stratified_bootstrap_device: a multiplicity exceeded 127 on the int8 Gram path"); }
+    if (*h_err) { void_records(m, REC_ROWS); return fail(m, PLSPM_E_STATE, "plspm_stratified_bootstrap_device: the device reported error bits " + std::to_string(*h_err)); }
+    hand_out(m->rows, m->status, m->iters, d_out, d_status, d_iters);
     return 0;
 }
 
@@ -205,17 +195,13 @@ int plspm_permutation_device(plspm_model_t* m, int64_t B, uint64_t seed, int64_t
     if (!m || B < 1 || B > ((int64_t)1 << 29) || rep_offset < 0) return fail(m, PLSPM_E_ARG, "plspm_permutation_device: bad arguments (1 <= B <= 2^29, rep_offset >= 0)");
     if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_permutation_device: no data uploaded");
     if (n1 < 1 || n1 >= m->N) return fail(m, PLSPM_E_ARG, "plspm_permutation_device: the group size must satisfy 1 <= n1 < N");
-    if (m->nonmetric || m->categorical || m->n_ind || m->nmx_K || m->stage1 || m->stage2)
+    if (!plain_metric(m))
         return fail(m, PLSPM_E_ARG, "plspm_permutation_device: plain metric models only (no non-metric scales, no missing values, no two-stage pair)");
     if (m->tune.i8_shape != 16) return fail(m, PLSPM_E_ARG, "plspm_permutation_device: needs the 16x16x64 layout of the int8 Gram (i8_shape 16)");
     HIPCHK(m, hipSetDevice(m->device));
-    // the int8 route whatever "gram_path" / "i8_min_batch" say (the dense 0/1 counts are what it reads), unless the route itself is closed
-    const int keep_path = m->tune.gram_path, keep_slices = m->tune.i8_slices;
-    m->tune.gram_path = 2;
-    if (keep_slices && keep_slices < 7) m->tune.i8_slices = 7;           // (the budget of the seven planes this call cuts)
-    const int route = choose_gram_path(m, 2 * B);
-    m->tune.gram_path = keep_path; m->tune.i8_slices = keep_slices;
-    if (route != 2) return fail(m, PLSPM_E_LIMIT, "plspm_permutation_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
+    // the int8 route whatever "gram_path" / "i8_min_batch" say (the dense 0/1 counts are what it reads), unless the route itself is closed at the seven
+    // planes this call cuts
+    if (!gram_counts_route_open(m)) return fail(m, PLSPM_E_LIMIT, "plspm_permutation_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
     const uint8_t* d_member = nullptr;
     int rc;
     if (member) {
@@ -233,13 +219,10 @@ int plspm_permutation_device(plspm_model_t* m, int64_t B, uint64_t seed, int64_t
     }
     if (m->micom_on && (rc = micom_prepare(m))) return rc;               // (the pooled inputs of the MICOM records: once per upload, in front of the batch that overwrites m->gram)
     const PermSpec spec{seed, rep_offset, n1, d_member};
-    m->perm = &spec;
-    rc = plspm_detail_bootstrap(m, 2 * B, 0, 0, nullptr, nullptr);       // problems 2p / 2p + 1 = the groups of permutation rep_offset + p
-    m->perm = nullptr;
-    if (rc) return rc;
-    if (d_out) *d_out = m->rows.p;
-    if (d_status) *d_status = m->status.p;
-    if (d_iters) *d_iters = m->iters.p;
+    BatchCall call;
+    call.kind = BatchCall::PERMUTATION; call.perm = &spec; call.B = 2 * B;       // problems 2p / 2p + 1 = the groups of permutation rep_offset + p
+    if ((rc = plspm_detail_bootstrap(m, call))) return rc;
+    hand_out(m->rows, m->status, m->iters, d_out, d_status, d_iters);
     return 0;
 }
 
