@@ -164,31 +164,16 @@ PLSPM_HD void solve_problem_quad(Ex& ex, const ModelDesc& md, const QuadWs<LMAX>
     const double corr2 = ex.uniform_d(n / (n - 1.0));
     ex.mark(2);                                                  // (the loader's last barrier stands behind its last tile read: the staging area is free)
 
-    // LV role: normal equations M[f, f] x = M[f, t] over my predecessors f -- up to four in registers (wave_ldl4), more by Cholesky in LDS
-    // scratch; a rank-deficient system takes the minimum-norm answer of the reference's pinv / gelsd (solver_core.h pinv_solve).  Scratch and
-    // x live in an area of their own (ws.scr): V stays in LDS through the trip, and the outer step, the sign rule and the loadings read it there --
-    // sixteen register pairs per thread that the regressions' straight-line code would otherwise send to scratch.
+    // LV role: the regressions over my predecessors (solver_wave_parts.h wave_regress).  Scratch and x live in an area of their own (ws.scr): V stays
+    // in LDS through the trip, and the outer step, the sign rule and the loadings read it there -- sixteen register pairs per thread that the
+    // regressions' straight-line code would otherwise send to scratch.
     const int* fglob = md.pred_idx + (lvlane ? md.pred_off[t] : 0);
     const long rscr = regression_scratch_doubles(md.kmax);
     const int km = md.kmax;
-    auto pred = [&](int r) { return r < 4 ? (int)((fpack >> (8 * r)) & 255u) : fglob[r]; };
     auto regress = [&](const double* M) {
         double* scratch = ws.scr + t * rscr;
         double* x = scratch + 2 * km * km;
-        bool ok;
-        if (nk <= 4) {
-            unsigned fp = fpack;
-            ex.opaque(fp);
-            ok = wave_ldl4(M, LMAX, fp, nk, t, x);
-        } else {
-            for (int r = 0; r < nk; ++r) {
-                for (int c = 0; c < nk; ++c) scratch[r * nk + c] = M[fglob[r] * LMAX + fglob[c]];
-                x[r] = M[fglob[r] * LMAX + t];
-            }
-            ok = chol_factor(scratch, nk);
-            if (ok) chol_solve(scratch, nk, x);
-        }
-        if (!ok && !(nk > 1 && pinv_solve(M, LMAX, fglob, nk, t, x, scratch))) singular = true;
+        wave_regress(ex, M, LMAX, nk, fpack, fglob, t, scratch, x, singular);
         return x;
     };
 
@@ -255,8 +240,8 @@ PLSPM_HD void solve_problem_quad(Ex& ex, const ModelDesc& md, const QuadWs<LMAX>
             if (lvlane && nk > 0) {                              // regression of Yhat_t on its predecessors, no intercept (scheme.py:48-50)
                 const double* x = regress(ws.Gm);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) if (r < nk) ws.Em[pred(r) * LMAX + tl] = ws.a[pred(r)] * x[r];
-                for (int r = 4; r < nk; ++r) ws.Em[pred(r) * LMAX + tl] = ws.a[pred(r)] * x[r];
+                for (int r = 0; r < 4; ++r) if (r < nk) ws.Em[wave_pred(fpack, fglob, r) * LMAX + tl] = ws.a[wave_pred(fpack, fglob, r)] * x[r];
+                for (int r = 4; r < nk; ++r) ws.Em[wave_pred(fpack, fglob, r) * LMAX + tl] = ws.a[wave_pred(fpack, fglob, r)] * x[r];
             }
             ex.sync();
         }
@@ -308,15 +293,7 @@ PLSPM_HD void solve_problem_quad(Ex& ex, const ModelDesc& md, const QuadWs<LMAX>
     // inner model (inner_model.py:58-75): OLS with intercept == centred normal equations on the score covariance
     double r2p = 0.0;
     if (lvlane) {
-        if (nk > 0) {
-            const double* x = regress(ws.Cs);
-            double expl = 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (r < nk) { const int fr = pred(r); ws.Bm[t * LMAX + fr] = x[r]; expl += x[r] * ws.Cs[fr * LMAX + t]; }
-            for (int r = 4; r < nk; ++r) { const int fr = pred(r); ws.Bm[t * LMAX + fr] = x[r]; expl += x[r] * ws.Cs[fr * LMAX + t]; }
-            r2p = expl / ws.Cs[t * LMAX + t];
-        }
+        if (nk > 0) r2p = wave_inner_model(regress(ws.Cs), ws.Cs, ws.Bm, LMAX, t, nk, fpack, fglob);
     }
     ex.sync();
     ex.mark(6);
@@ -357,9 +334,7 @@ PLSPM_HD void solve_problem_quad(Ex& ex, const ModelDesc& md, const QuadWs<LMAX>
     if ((t & 63) == 0) ws.red[wave] = (double)nbad;
     ex.sync();
     if (t == 0) {
-        const bool bad = (ws.red[0] + ws.red[1]) + (ws.red[2] + ws.red[3]) > 0.0;
-        int st = sing ? ST_SINGULAR : (not_converged ? ST_NOT_CONVERGED : ST_OK);
-        if (st == ST_OK && bad) st = ST_NONFINITE;
+        const int st = wave_status(sing, not_converged, (ws.red[0] + ws.red[1]) + (ws.red[2] + ws.red[3]) > 0.0);
         if (out.status) *out.status = st;
         if (out.iters) *out.iters = iteration;
         if (out.row) { out.row[2 * P + L + 2 * ne] = (double)st; out.row[2 * P + L + 2 * ne + 1] = (double)iteration; }

@@ -30,8 +30,7 @@
 // passed, LDS writes visible; ex.allsum(v) = butterfly sum, bitwise identical on every lane; ex.vote_count / ex.vote_any = ballots;
 // ex.load_cov = the column loader; ex.seg_products = the segmented multiply-add stream of solve_problem_rows.
 #pragma once
-#include "solver_core.h"
-#include <type_traits>
+#include "solver_wave_parts.h"
 
 namespace plspm {
 
@@ -65,99 +64,6 @@ template <int LMAX> PLSPM_HD void wave_carve(WaveWs<LMAX>& ws, double* base) {
 // What the wave solver covers (the host asks before it launches; everything else takes solve_problem_rows / solve_problem).
 // Mode-B blocks: their inverses are formed by an out-of-place Gauss-Jordan sweep that ping-pongs between ws.inv and the staging area.
 template <int LMAX> PLSPM_HD bool wave_solver_covers(int P, int L, int n_chol) { return P >= 1 && P <= 64 && L >= 1 && L <= LMAX && n_chol / 2 <= 16 * 66; }
-
-// 1 / sqrt(x) and 1 / x to the last bit or two (not correctly rounded): v_rsq_f64 / v_rcp_f64 seeds + Newton steps on the device -- a
-// fraction of the dependent instructions of the IEEE sqrt + divide sequences, which sit on the critical path of every small phase.
-// The CPU emulation runs the SAME refinement on a seed of the hardware's accuracy (the exact value rounded to fp32's 24 bits, exponent kept
-// apart so that any double is in range): what the emulation tests then hold against the oracle is this arithmetic, not the IEEE divide.
-PLSPM_HD double wave_rsqrt(double x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    double r = __builtin_amdgcn_rsq(x);                           // ~2^-26 relative
-#else
-    double r;
-    if (!(x > 0.0) || x > 1.7976931348623157e308) r = 1.0 / sqrt(x);      // 0, negative, inf, NaN: what the instruction returns
-    else {
-        int e;
-        double m = frexp(x, &e);                                  // x = m 2^e, m in [1/2, 1)
-        if (e & 1) { m *= 2.0; --e; }                             // even exponent: sqrt(2^e) is a power of two
-        r = ldexp((double)(float)(1.0 / sqrt(m)), -e / 2);
-    }
-#endif
-    const double hx = 0.5 * x;
-    r = fma(r, fma(-hx * r, r, 0.5), r);                          // r (1 + (1/2 - x r^2 / 2))
-    r = fma(r, fma(-hx * r, r, 0.5), r);
-    return r;
-}
-PLSPM_HD double wave_rcp(double x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    double r = __builtin_amdgcn_rcp(x);
-#else
-    double r;
-    if (!(fabs(x) > 0.0) || fabs(x) > 1.7976931348623157e308) r = 1.0 / x;
-    else {
-        int e;
-        const double m = frexp(x, &e);
-        r = ldexp((double)(float)(1.0 / m), -e);
-    }
-#endif
-    r = fma(r, fma(-x, r, 1.0), r);
-    r = fma(r, fma(-x, r, 1.0), r);
-    return r;
-}
-// Normal equations M[f, f] x = M[f, col], f = the k <= 4 indices packed one per byte in `fpack`, M an L x L matrix with pitch ld in the
-// workspace: square-root-free factorisation A = U' D U in registers (as solver_core.h spd_solve_fixed; identity padding beyond k),
-// reciprocals by wave_rcp.  Returns false at a pivot that is not safely positive (the caller takes the minimum-norm route).
-PLSPM_HD bool wave_ldl4(const double* M, int ld, unsigned fpack, int k, int col, double* x) {
-    constexpr int K = 4;
-    double A[K][K], b[K];
-    int f[K];
-#pragma unroll
-    for (int r = 0; r < K; ++r) f[r] = (r < k) ? (int)((fpack >> (8 * r)) & 255u) : 0;
-#pragma unroll
-    for (int r = 0; r < K; ++r) {
-#pragma unroll
-        for (int c = r; c < K; ++c) A[r][c] = (r < k && c < k) ? M[f[r] * ld + f[c]] : ((r == c) ? 1.0 : 0.0);
-        b[r] = (r < k) ? M[f[r] * ld + col] : 0.0;
-    }
-    bool ok = true;
-    double T[K][K], invd[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const double ajj = A[j][j];
-        double d = ajj;
-#pragma unroll
-        for (int r = 0; r < j; ++r) d -= A[r][j] * T[r][j];
-        ok = ok && (d > PLSPM_PIVOT_RTOL * ajj);
-        invd[j] = wave_rcp(d);
-#pragma unroll
-        for (int c = j + 1; c < K; ++c) {
-            double t = A[j][c];
-#pragma unroll
-            for (int r = 0; r < j; ++r) t -= A[r][j] * T[r][c];
-            T[j][c] = t;
-            A[j][c] = t * invd[j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        double t = b[i];
-#pragma unroll
-        for (int r = 0; r < i; ++r) t -= A[r][i] * b[r];
-        b[i] = t;
-    }
-#pragma unroll
-    for (int i = 0; i < K; ++i) b[i] *= invd[i];
-#pragma unroll
-    for (int i = K - 1; i >= 0; --i) {
-        double t = b[i];
-#pragma unroll
-        for (int c = i + 1; c < K; ++c) t -= A[i][c] * b[c];
-        b[i] = t;
-    }
-#pragma unroll
-    for (int r = 0; r < K; ++r) if (r < k) x[r] = b[r];
-    return ok;
-}
 
 // Md: the DENSE moment matrix [(P+1) x cov_ld(P)] of the mean-shifted columns + ones, upper triangle (entry (r, c >= r) at r * PS + c),
 // as the int8 digit-plane Gram writes it.  Outputs: out.row / out.status / out.iters (a bootstrap record).
@@ -247,162 +153,19 @@ PLSPM_HD void solve_problem_wave(Ex& ex, const ModelDesc& md, const WaveWs<LMAX>
     ex.mark(2);
 
 
-    // Mode-B blocks (mode.py:50-52: w_b = argmin |X_b w - z| = S_bb^-1 (X_b' z / N)): S_bb does not change over the iterations, so its
-    // inverse is formed once.  Gauss-Jordan sweep without pivoting (S_bb is positive definite; pivot j is the same Schur complement the
-    // Cholesky factorisation of solver_core.h tests, so a rank-deficient block is recognised by the same rule), every MV lane of a Mode-B
-    // block owning ROW i of its k x k matrix, all blocks at once, out of place: step j reads A, writes A' -- no lane reads what another
-    // rewrites in the same step, ONE exchange per step -- ping-ponging between ws.inv and the staging area (free until the first S W).
-    //     i == j:  A'[j][c] = A[j][c] / piv  (c != j),  A'[j][j] = 1 / piv
-    //     i != j:  A'[i][c] = A[i][c] - A[i][j] A[j][c] / piv  (c != j),  A'[i][j] = -A[i][j] / piv
-    // A block whose sweep meets a pivot that is not safely positive takes the minimum-norm route of the reference's gelsd (jacobi_pinv, on
-    // its LV lane, one such block at a time in the staging area) -- the outer step multiplies with the full symmetric matrix either way.
+    // Mode-B blocks: (S_bb)^-1 of every block formed ONCE per problem, in ws.inv (solver_wave_parts.h wave_modeb_inverses)
     const bool modeb = MODEB && mine && md.mode[lp] == MODE_B;
     const int bb0 = md.boff[lp], bk = md.boff[lp + 1] - bb0, bi = p - bb0;
     const long boffB = modeb ? md.chol_off[lp] / 2 : 0;
-    if constexpr (MODEB) {
-        ex.sync();                                              // (every lane is done with the column sums ws.mu held)
-        ws.mu[p] = (sdp > 0.0) ? sdp * sdp : 1e300;             // the treated diagonal S_pp: the scale a pivot is measured against (a zero-variance column: no pivot passes -- the block takes the minimum-norm route, weight 0 for it)
-        double* A = (kbB & 1) ? ws.stage : ws.inv;              // an odd number of steps ends in ws.inv
-        double* An = (kbB & 1) ? ws.inv : ws.stage;
-        auto fill_block = [&](double* dst) {                    // row bi of S_bb out of the column registers (S is symmetric)
-#pragma unroll
-            for (int q = 0; q < PMAX; ++q)
-                if (modeb && q >= bb0 && q < bb0 + bk) dst[boffB + bi * bk + (q - bb0)] = s[q];
-        };
-        // the same with every lane storing every column -- the ones outside its block into a slot of its own behind the pivot rows of the
-        // sweep below (an address select instead of an exec-masked branch per column: 7 k -> 2 k clocks)
-        auto fill_block_all = [&](double* dst) {
-            double* mine_row = dst + boffB + bi * bk - bb0;      // column q of my block lands at mine_row[q]
-            double* junk = ws.stage + 2 * LMAX * 16 + p;
-            const unsigned bkm = modeb ? (unsigned)bk : 0u;
-#pragma unroll
-            for (int q = 0; q < PMAX; ++q) {
-                double* d = ((unsigned)(q - bb0) < bkm) ? mine_row + q : junk;
-                *d = s[q];
-            }
-        };
-        bool okrow = true;
-        ex.mark(20);
-        // blocks of at most 16 MVs (round 4): every lane keeps ITS row of the block in registers; step j = the pivot lane publishes its row
-        // (double-buffered at the head of the staging area), one exchange, every lane updates its row with straight-line code (compile-time
-        // column index, `c == j` a scalar test) -- where the loop over LDS-resident matrices below pays two dependent LDS round trips per
-        // column and step (5 k clocks per step at k = 10 against ~1 k).  Same formulas, same pivot test.  KR = registers of a row: 8 / 12 / 16.
-        auto sweep_rows = [&](auto krc) {
-            constexpr int KR = decltype(krc)::value;
-            fill_block_all(ws.inv);
-            ex.sync();
-            ex.mark(21);
-            double row[KR];
-            {
-                const double* Ib0 = ws.inv + boffB + bi * bk;
-#pragma unroll
-                for (int c = 0; c < KR; ++c) row[c] = (modeb && c < bk) ? Ib0[c] : 0.0;
-            }
-            ex.mark(22);
-            for (int j = 0; j < kbB; ++j) {
-                double* Pj = ws.stage + ((j & 1) * LMAX + lp) * 16;
-                if (modeb && bi == j) {
-#pragma unroll
-                    for (int c = 0; c < KR; ++c) Pj[c] = row[c];
-                }
-                ex.sync();
-                if (modeb && j < bk) {
-                    double f = 0.0;
-#pragma unroll
-                    for (int c = 0; c < KR; ++c) f = (c == j) ? row[c] : f;
-                    const double piv = Pj[j];
-                    okrow = okrow && (piv > PLSPM_PIVOT_RTOL * ws.mu[bb0 + j]);
-                    const double ip = wave_rcp(piv);
-                    const bool pivlane = bi == j;
-                    const double fip = f * ip;
-#pragma unroll
-                    for (int c = 0; c < KR; ++c) {
-                        const double rjc = Pj[c] * ip;
-                        const double off = pivlane ? rjc : row[c] - f * rjc;
-                        const double dia = pivlane ? ip : -fip;
-                        row[c] = (c == j) ? dia : off;
-                    }
-                }
-            }
-            ex.mark(23);
-#pragma unroll
-            for (int c = 0; c < KR; ++c) if (modeb && c < bk) ws.inv[boffB + bi * bk + c] = row[c];
-            ex.sync();
-            ex.mark(24);
-        };
-        if (kbB <= 8) sweep_rows(std::integral_constant<int, 8>{});
-        else if (kbB <= 12) sweep_rows(std::integral_constant<int, 12>{});
-        else if (kbB <= 16) sweep_rows(std::integral_constant<int, 16>{});
-        else {
-        fill_block(A);
-        ex.sync();
-        for (int j = 0; j < kbB; ++j) {
-            if (modeb) {
-                const double* Ab = A + boffB;
-                double* Ob = An + boffB;
-                if (j < bk) {
-                    const double piv = Ab[j * bk + j];
-                    okrow = okrow && (piv > PLSPM_PIVOT_RTOL * ws.mu[bb0 + j]);
-                    const double ip = 1.0 / piv;
-                    const double f = Ab[bi * bk + j];
-                    for (int c = 0; c < bk; ++c) {
-                        const double rjc = Ab[j * bk + c] * ip;
-                        double v;
-                        if (bi == j) v = (c == j) ? ip : rjc;
-                        else v = (c == j) ? -f * ip : Ab[bi * bk + c] - f * rjc;
-                        Ob[bi * bk + c] = v;
-                    }
-                } else {
-                    for (int c = 0; c < bk; ++c) Ob[bi * bk + c] = Ab[bi * bk + c];      // a smaller block waits out the larger ones' steps
-                }
-            }
-            ex.sync();
-            double* t = A; A = An; An = t;
-        }
-        }
-        // rank-deficient blocks, one at a time: S_bb once more from the registers, pseudo-inverse on the block's LV lane (scratch: the staging area)
-        const bool any_bad = ex.vote_any(modeb && !okrow);      // (one ballot instead of a descriptor walk when every sweep went through)
-        for (int l = 0; any_bad && l < L; ++l) {
-            if (md.mode[l] != MODE_B) continue;
-            const int k = md.boff[l + 1] - md.boff[l];
-            const bool bad_here = ex.vote_any(modeb && lp == l && !okrow);
-            if (!bad_here) continue;
-            if (lp == l) fill_block(ws.inv);
-            ex.sync();
-            if (p == l) {
-                double* F = ws.inv + md.chol_off[l] / 2;
-                bool ok = k > 1 && jacobi_pinv(F, k, ws.stage);
-                if (!ok) singular = true;
-                for (int r = 0; r < k; ++r) for (int c = 0; c < r; ++c) F[r * k + c] = F[c * k + r];      // jacobi_pinv leaves the upper triangle
-            }
-            ex.sync();
-        }
-        ex.mark(25);
-    }
+    if constexpr (MODEB) wave_modeb_inverses<LMAX>(ex, md, ws, s, p, lp, L, sdp, kbB, modeb, bb0, bk, bi, boffB, singular);
 
-    // LV role: normal equations M[f, f] x = M[f, p] over my predecessors f -- up to four in registers (wave_ldl4: every LV lane runs the
-    // same straight-line code, identity-padded), five to LMAX - 1 by Cholesky in LDS scratch; a rank-deficient system takes the
-    // minimum-norm answer of the reference's pinv / gelsd (solver_core.h pinv_solve).  Scratch and x live in the staging area: V and T
+    // LV role: the regressions over my predecessors (solver_wave_parts.h wave_regress).  Scratch and x live in the staging area: V and T
     // are dead between the Q exchange and the next S W.
     const int* fglob = md.pred_idx + (lvlane ? md.pred_off[p] : 0);
-    auto pred = [&](int r) { return r < 4 ? (int)((fpack >> (8 * r)) & 255u) : fglob[r]; };
     auto regress = [&](const double* M) {
         double* scratch = ws.stage + p * WAVE_REG_SCRATCH;
         double* x = scratch + 2 * (LMAX - 1) * (LMAX - 1);
-        bool ok;
-        if (nk <= 4) {
-            unsigned fp = fpack;
-            ex.opaque(fp);            // the 14 gather addresses are recomputed here (a few integer operations) instead of living -- spilled -- across the loop
-            ok = wave_ldl4(M, LMAX, fp, nk, p, x);
-        } else {
-            for (int r = 0; r < nk; ++r) {
-                for (int c = 0; c < nk; ++c) scratch[r * nk + c] = M[fglob[r] * LMAX + fglob[c]];
-                x[r] = M[fglob[r] * LMAX + p];
-            }
-            ok = chol_factor(scratch, nk);
-            if (ok) chol_solve(scratch, nk, x);
-        }
-        if (!ok && !(nk > 1 && pinv_solve(M, LMAX, fglob, nk, p, x, scratch))) singular = true;
+        wave_regress(ex, M, LMAX, nk, fpack, fglob, p, scratch, x, singular);
         return x;
     };
 
@@ -479,8 +242,8 @@ PLSPM_HD void solve_problem_wave(Ex& ex, const ModelDesc& md, const WaveWs<LMAX>
             if (lvlane && nk > 0) {                              // regression of Yhat_p on its predecessors, no intercept (scheme.py:48-50)
                 const double* x = regress(ws.Gm);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) if (r < nk) ws.Em[pred(r) * LMAX + pl] = x[r];
-                for (int r = 4; r < nk; ++r) ws.Em[pred(r) * LMAX + pl] = x[r];
+                for (int r = 0; r < 4; ++r) if (r < nk) ws.Em[wave_pred(fpack, fglob, r) * LMAX + pl] = x[r];
+                for (int r = 4; r < nk; ++r) ws.Em[wave_pred(fpack, fglob, r) * LMAX + pl] = x[r];
             }
             ex.sync();
         }
@@ -498,13 +261,7 @@ PLSPM_HD void solve_problem_wave(Ex& ex, const ModelDesc& md, const WaveWs<LMAX>
             ws.mu[pl] = wn;
             ex.sync();
             if (modeb) {
-                const double* Ib = ws.inv + boffB + bi * bk;
-                const double* cb = ws.mu + bb0;
-                double a0 = 0.0, a1 = 0.0;
-                int q = 0;
-                for (; q + 1 < bk; q += 2) { a0 += Ib[q] * cb[q]; a1 += Ib[q + 1] * cb[q + 1]; }
-                if (q < bk) a0 += Ib[q] * cb[q];
-                wn = a0 + a1;
+                wn = wave_modeb_dot(ws.inv + boffB + bi * bk, ws.mu + bb0, bk);
             }
         }
         const double dd = fabs(wp) - fabs(wn);
@@ -533,7 +290,8 @@ PLSPM_HD void solve_problem_wave(Ex& ex, const ModelDesc& md, const WaveWs<LMAX>
     }
     ex.sync();
     ex.mark(5);
-    // inner model (inner_model.py:58-75): OLS with intercept == centred normal equations on the score covariance
+    // inner model (inner_model.py:58-75): OLS with intercept == centred normal equations on the score covariance.  Spelled out here, not a call of
+    // wave_inner_model (same text): through the call, ~500 of the 8.3 k instructions of the Mode-A kernel come out differently
     double r2p = 0.0;
     if (lvlane) {
 #pragma unroll
@@ -543,8 +301,8 @@ PLSPM_HD void solve_problem_wave(Ex& ex, const ModelDesc& md, const WaveWs<LMAX>
             double expl = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (r < nk) { const int fr = pred(r); ws.Bm[p * LMAX + fr] = x[r]; expl += x[r] * ws.Cs[fr * LMAX + p]; }
-            for (int r = 4; r < nk; ++r) { const int fr = pred(r); ws.Bm[p * LMAX + fr] = x[r]; expl += x[r] * ws.Cs[fr * LMAX + p]; }
+                if (r < nk) { const int fr = wave_pred(fpack, fglob, r); ws.Bm[p * LMAX + fr] = x[r]; expl += x[r] * ws.Cs[fr * LMAX + p]; }
+            for (int r = 4; r < nk; ++r) { const int fr = wave_pred(fpack, fglob, r); ws.Bm[p * LMAX + fr] = x[r]; expl += x[r] * ws.Cs[fr * LMAX + p]; }
             r2p = expl / ws.Cs[p * LMAX + p];
         }
     }
@@ -585,8 +343,7 @@ PLSPM_HD void solve_problem_wave(Ex& ex, const ModelDesc& md, const WaveWs<LMAX>
     const bool bad = ex.vote_any((mine && !(isfinite(wp) && isfinite(sdp) && sdp >= 0.0)) || (lvlane && !isfinite(r2p)));
     const bool sing = ex.vote_any(singular);
     if (p == 0) {
-        int st = sing ? ST_SINGULAR : (not_converged ? ST_NOT_CONVERGED : ST_OK);
-        if (st == ST_OK && bad) st = ST_NONFINITE;
+        const int st = wave_status(sing, not_converged, bad);
         if (out.status) *out.status = st;
         if (out.iters) *out.iters = iteration;
         if (out.row) { out.row[2 * P + L + 2 * ne] = (double)st; out.row[2 * P + L + 2 * ne + 1] = (double)iteration; }

@@ -180,162 +180,20 @@ PLSPM_HD void solve_problem_wave16(Ex& ex, const ModelDesc& md, const Wave16Ws<L
     const double corr2 = ex.uniform_d(n / (n - 1.0));
     ex.mark(2);                                                  // (the loader's last barrier stands behind its last tile read: V takes the tile's place)
 
-    // Mode-B blocks (solver_wave.h, round 4: the same code on this workspace -- the staging area is the V area, free until the first S W) (mode.py:50-52: w_b = argmin |X_b w - z| = S_bb^-1 (X_b' z / N)): S_bb does not change over the iterations, so its
-    // inverse is formed once.  Gauss-Jordan sweep without pivoting (S_bb is positive definite; pivot j is the same Schur complement the
-    // Cholesky factorisation of solver_core.h tests, so a rank-deficient block is recognised by the same rule), every MV lane of a Mode-B
-    // block owning ROW i of its k x k matrix, all blocks at once, out of place: step j reads A, writes A' -- no lane reads what another
-    // rewrites in the same step, ONE exchange per step -- ping-ponging between ws.inv and the staging area (free until the first S W).
-    //     i == j:  A'[j][c] = A[j][c] / piv  (c != j),  A'[j][j] = 1 / piv
-    //     i != j:  A'[i][c] = A[i][c] - A[i][j] A[j][c] / piv  (c != j),  A'[i][j] = -A[i][j] / piv
-    // A block whose sweep meets a pivot that is not safely positive takes the minimum-norm route of the reference's gelsd (jacobi_pinv, on
-    // its LV lane, one such block at a time in the staging area) -- the outer step multiplies with the full symmetric matrix either way.
+    // Mode-B blocks: (S_bb)^-1 of every block formed ONCE per problem, in ws.inv (solver_wave_parts.h wave_modeb_inverses; the staging area is the V area, free until the first S W)
     const bool modeb = MODEB && valid && md.mode[lp] == MODE_B;
     const int bb0 = md.boff[lp], bk = md.boff[lp + 1] - bb0, bi = p - bb0;
     const long boffB = modeb ? md.chol_off[lp] / 2 : 0;
-    if constexpr (MODEB) {
-        ex.sync();                                              // (every lane is done with the column sums ws.mu held)
-        ws.mu[p] = (sdp > 0.0) ? sdp * sdp : 1e300;             // the treated diagonal S_pp: the scale a pivot is measured against (a zero-variance column: no pivot passes -- the block takes the minimum-norm route, weight 0 for it)
-        double* A = (kbB & 1) ? ws.stage : ws.inv;              // an odd number of steps ends in ws.inv
-        double* An = (kbB & 1) ? ws.inv : ws.stage;
-        auto fill_block = [&](double* dst) {                    // row bi of S_bb out of the column registers (S is symmetric)
-#pragma unroll
-            for (int q = 0; q < PMAX; ++q)
-                if (modeb && q >= bb0 && q < bb0 + bk) dst[boffB + bi * bk + (q - bb0)] = s[q];
-        };
-        // the same with every lane storing every column -- the ones outside its block into a slot of its own behind the pivot rows of the
-        // sweep below (an address select instead of an exec-masked branch per column: 7 k -> 2 k clocks)
-        auto fill_block_all = [&](double* dst) {
-            double* mine_row = dst + boffB + bi * bk - bb0;      // column q of my block lands at mine_row[q]
-            double* junk = ws.stage + 2 * LMAX * 16 + p;
-            const unsigned bkm = modeb ? (unsigned)bk : 0u;
-#pragma unroll
-            for (int q = 0; q < PMAX; ++q) {
-                double* d = ((unsigned)(q - bb0) < bkm) ? mine_row + q : junk;
-                *d = s[q];
-            }
-        };
-        bool okrow = true;
-        ex.mark(20);
-        // blocks of at most 16 MVs (round 4): every lane keeps ITS row of the block in registers; step j = the pivot lane publishes its row
-        // (double-buffered at the head of the staging area), one exchange, every lane updates its row with straight-line code (compile-time
-        // column index, `c == j` a scalar test) -- where the loop over LDS-resident matrices below pays two dependent LDS round trips per
-        // column and step (5 k clocks per step at k = 10 against ~1 k).  Same formulas, same pivot test.  KR = registers of a row: 8 / 12 / 16.
-        auto sweep_rows = [&](auto krc) {
-            constexpr int KR = decltype(krc)::value;
-            fill_block_all(ws.inv);
-            ex.sync();
-            ex.mark(21);
-            double row[KR];
-            {
-                const double* Ib0 = ws.inv + boffB + bi * bk;
-#pragma unroll
-                for (int c = 0; c < KR; ++c) row[c] = (modeb && c < bk) ? Ib0[c] : 0.0;
-            }
-            ex.mark(22);
-            for (int j = 0; j < kbB; ++j) {
-                double* Pj = ws.stage + ((j & 1) * LMAX + lp) * 16;
-                if (modeb && bi == j) {
-#pragma unroll
-                    for (int c = 0; c < KR; ++c) Pj[c] = row[c];
-                }
-                ex.sync();
-                if (modeb && j < bk) {
-                    double f = 0.0;
-#pragma unroll
-                    for (int c = 0; c < KR; ++c) f = (c == j) ? row[c] : f;
-                    const double piv = Pj[j];
-                    okrow = okrow && (piv > PLSPM_PIVOT_RTOL * ws.mu[bb0 + j]);
-                    const double ip = wave_rcp(piv);
-                    const bool pivlane = bi == j;
-                    const double fip = f * ip;
-#pragma unroll
-                    for (int c = 0; c < KR; ++c) {
-                        const double rjc = Pj[c] * ip;
-                        const double off = pivlane ? rjc : row[c] - f * rjc;
-                        const double dia = pivlane ? ip : -fip;
-                        row[c] = (c == j) ? dia : off;
-                    }
-                }
-            }
-            ex.mark(23);
-#pragma unroll
-            for (int c = 0; c < KR; ++c) if (modeb && c < bk) ws.inv[boffB + bi * bk + c] = row[c];
-            ex.sync();
-            ex.mark(24);
-        };
-        if (kbB <= 8) sweep_rows(std::integral_constant<int, 8>{});
-        else if (kbB <= 12) sweep_rows(std::integral_constant<int, 12>{});
-        else if (kbB <= 16) sweep_rows(std::integral_constant<int, 16>{});
-        else {
-        fill_block(A);
-        ex.sync();
-        for (int j = 0; j < kbB; ++j) {
-            if (modeb) {
-                const double* Ab = A + boffB;
-                double* Ob = An + boffB;
-                if (j < bk) {
-                    const double piv = Ab[j * bk + j];
-                    okrow = okrow && (piv > PLSPM_PIVOT_RTOL * ws.mu[bb0 + j]);
-                    const double ip = 1.0 / piv;
-                    const double f = Ab[bi * bk + j];
-                    for (int c = 0; c < bk; ++c) {
-                        const double rjc = Ab[j * bk + c] * ip;
-                        double v;
-                        if (bi == j) v = (c == j) ? ip : rjc;
-                        else v = (c == j) ? -f * ip : Ab[bi * bk + c] - f * rjc;
-                        Ob[bi * bk + c] = v;
-                    }
-                } else {
-                    for (int c = 0; c < bk; ++c) Ob[bi * bk + c] = Ab[bi * bk + c];      // a smaller block waits out the larger ones' steps
-                }
-            }
-            ex.sync();
-            double* t = A; A = An; An = t;
-        }
-        }
-        // rank-deficient blocks, one at a time: S_bb once more from the registers, pseudo-inverse on the block's LV lane (scratch: the staging area)
-        const bool any_bad = ex.vote_any(modeb && !okrow);      // (one ballot instead of a descriptor walk when every sweep went through)
-        for (int l = 0; any_bad && l < L; ++l) {
-            if (md.mode[l] != MODE_B) continue;
-            const int k = md.boff[l + 1] - md.boff[l];
-            const bool bad_here = ex.vote_any(modeb && lp == l && !okrow);
-            if (!bad_here) continue;
-            if (lp == l) fill_block(ws.inv);
-            ex.sync();
-            if (p == l) {
-                double* F = ws.inv + md.chol_off[l] / 2;
-                bool ok = k > 1 && jacobi_pinv(F, k, ws.stage);
-                if (!ok) singular = true;
-                for (int r = 0; r < k; ++r) for (int c = 0; c < r; ++c) F[r * k + c] = F[c * k + r];      // jacobi_pinv leaves the upper triangle
-            }
-            ex.sync();
-        }
-        ex.mark(25);
-    }
+    if constexpr (MODEB) wave_modeb_inverses<LMAX>(ex, md, ws, s, p, lp, L, sdp, kbB, modeb, bb0, bk, bi, boffB, singular);
 
-
-    // LV role: normal equations M[f, f] x = M[f, t] over my predecessors f (solver_quad.h: the same lambda)
+    // LV role: the regressions over my predecessors (solver_wave_parts.h wave_regress), scratch and x in an area of their own (ws.scr)
     const int* fglob = md.pred_idx + (lvlane ? md.pred_off[t] : 0);
     const long rscr = regression_scratch_doubles(md.kmax);
     const int km = md.kmax;
-    auto pred = [&](int r) { return r < 4 ? (int)((fpack >> (8 * r)) & 255u) : fglob[r]; };
     auto regress = [&](const double* M) {
         double* scratch = ws.scr + t * rscr;
         double* x = scratch + 2 * km * km;
-        bool ok;
-        if (nk <= 4) {
-            unsigned fp = fpack;
-            ex.opaque(fp);
-            ok = wave_ldl4(M, LMAX, fp, nk, t, x);
-        } else {
-            for (int r = 0; r < nk; ++r) {
-                for (int c = 0; c < nk; ++c) scratch[r * nk + c] = M[fglob[r] * LMAX + fglob[c]];
-                x[r] = M[fglob[r] * LMAX + t];
-            }
-            ok = chol_factor(scratch, nk);
-            if (ok) chol_solve(scratch, nk, x);
-        }
-        if (!ok && !(nk > 1 && pinv_solve(M, LMAX, fglob, nk, t, x, scratch))) singular = true;
+        wave_regress(ex, M, LMAX, nk, fpack, fglob, t, scratch, x, singular);
         return x;
     };
 
@@ -508,8 +366,8 @@ PLSPM_HD void solve_problem_wave16(Ex& ex, const ModelDesc& md, const Wave16Ws<L
             if (lvlane && nk > 0) {                              // regression of Yhat_t on its predecessors, no intercept (scheme.py:48-50)
                 const double* x = regress(ws.Gm);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) if (r < nk) ws.Em[pred(r) * LMAX + pl] = ws.a[pred(r)] * x[r];
-                for (int r = 4; r < nk; ++r) ws.Em[pred(r) * LMAX + pl] = ws.a[pred(r)] * x[r];
+                for (int r = 0; r < 4; ++r) if (r < nk) ws.Em[wave_pred(fpack, fglob, r) * LMAX + pl] = ws.a[wave_pred(fpack, fglob, r)] * x[r];
+                for (int r = 4; r < nk; ++r) ws.Em[wave_pred(fpack, fglob, r) * LMAX + pl] = ws.a[wave_pred(fpack, fglob, r)] * x[r];
             }
             ex.sync();
         }
@@ -526,13 +384,7 @@ PLSPM_HD void solve_problem_wave16(Ex& ex, const ModelDesc& md, const Wave16Ws<L
             ws.mu[pl] = wn;
             ex.sync();
             if (modeb) {
-                const double* Ib = ws.inv + boffB + bi * bk;
-                const double* cb = ws.mu + bb0;
-                double a0 = 0.0, a1 = 0.0;
-                int q = 0;
-                for (; q + 1 < bk; q += 2) { a0 += Ib[q] * cb[q]; a1 += Ib[q + 1] * cb[q + 1]; }
-                if (q < bk) a0 += Ib[q] * cb[q];
-                wn = a0 + a1;
+                wn = wave_modeb_dot(ws.inv + boffB + bi * bk, ws.mu + bb0, bk);
             }
         }
         if constexpr (NM) {
@@ -591,15 +443,7 @@ PLSPM_HD void solve_problem_wave16(Ex& ex, const ModelDesc& md, const Wave16Ws<L
     // inner model (inner_model.py:58-75): OLS with intercept == centred normal equations on the score covariance
     double r2p = 0.0;
     if (lvlane) {
-        if (nk > 0) {
-            const double* x = regress(Cs);
-            double expl = 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (r < nk) { const int fr = pred(r); Bm[t * LMAX + fr] = x[r]; expl += x[r] * Cs[fr * LMAX + t]; }
-            for (int r = 4; r < nk; ++r) { const int fr = pred(r); Bm[t * LMAX + fr] = x[r]; expl += x[r] * Cs[fr * LMAX + t]; }
-            r2p = expl / Cs[t * LMAX + t];
-        }
+        if (nk > 0) r2p = wave_inner_model(regress(Cs), Cs, Bm, LMAX, t, nk, fpack, fglob);
     }
     ex.sync();
     ex.mark(6);
@@ -636,8 +480,7 @@ PLSPM_HD void solve_problem_wave16(Ex& ex, const ModelDesc& md, const Wave16Ws<L
     const bool bad = ex.vote_any((valid && !(isfinite(wp) && isfinite(sdp) && sdp >= 0.0)) || (lvlane && !isfinite(r2p)));
     const bool sing = ex.vote_any(singular);
     if (t == 0) {
-        int st = sing ? ST_SINGULAR : (not_converged ? ST_NOT_CONVERGED : ST_OK);
-        if (st == ST_OK && bad) st = ST_NONFINITE;
+        const int st = wave_status(sing, not_converged, bad);
         if (out.status) *out.status = st;
         if (out.iters) *out.iters = iteration;
         if (out.row) { out.row[2 * P + L + 2 * ne] = (double)st; out.row[2 * P + L + 2 * ne + 1] = (double)iteration; }

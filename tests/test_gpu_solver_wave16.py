@@ -151,6 +151,40 @@ def test_wave16_solver_mode_b_blocks(sizes, modes, scheme):
     assert_close(rows[r], mine, RTOL, ATOL)
 
 
+@pytest.mark.parametrize("sizes,modes", [([8, 2, 2, 2, 2, 2, 2, 2, 2], "BAAAAAAAB"), ([9, 1, 2, 2, 2, 2, 2, 2, 2], "BAAAAAAAB"), ([12, 3, 1, 2, 2, 2, 2, 2, 2], "BBAAAAAAA"),
+                                         ([13, 2, 2, 2, 2, 2, 2, 2, 2], "BAAAAAAAB"), ([16, 16, 16, 2, 2, 2, 2, 2, 2], "BBBAAAAAA"), ([17, 8, 5, 2, 2, 2, 2, 2, 2], "BBAAAAAAB")])
+def test_wave16_solver_mode_b_block_widths(sizes, modes):
+    """Mode-B blocks on the 9 ... 16 LV form at the widths where the inverse phase changes form (rows of 8 | 9 .. 12 | 13 .. 16 registers per lane; from 17 MVs
+    the sweep over LDS-resident matrices), smaller blocks waiting out a wider one: against the rows and LDS solvers on the same moment matrices and against the
+    oracle; the 12-wide block once more with its last column a copy of its first (rank deficient: the minimum-norm route) against the LDS solver."""
+    from plspm import _native
+    C = _dag(9, 2)
+    X, blocks = _shaped(C, sizes, seed=14, N=300)
+    for scheme in ("centroid", "path"):
+        model = orc.Model(blocks, C, modes, scheme, True)
+        nm = native_model(model)
+        nm.upload(X); nm.set_option("gram_path", 2)
+        out = _three_solvers(nm, 64, 5)
+        rows, status, iters = out["wave16"]
+        assert np.all(status == 0), (sizes, modes, scheme)
+        for other in ("rows", "lds"):
+            assert np.array_equal(out[other][1], status) and np.array_equal(out[other][2], iters), other
+            assert_close(out[other][0], rows, 1e-10, 1e-12, what="%s %s %s" % (sizes, modes, other))
+        corr = orc.correction(300)
+        for r in (0, 63):
+            mine, its = orc.bootstrap_replicate(X, model, _native.bootstrap_indices(5, r, 300), corr)
+            assert its == iters[r]
+            assert_close(rows[r], mine, RTOL, ATOL)
+        if sizes[0] == 12:
+            Xd = X.copy()
+            Xd[:, blocks[0][-1]] = Xd[:, blocks[0][0]]
+            nm = native_model(model)
+            nm.upload(Xd); nm.set_option("gram_path", 2)
+            out = _three_solvers(nm, 64, 5)
+            assert np.array_equal(out["wave16"][1], out["lds"][1]) and np.array_equal(out["wave16"][2], out["lds"][2])
+            assert_close(out["wave16"][0], out["lds"][0], 1e-8, 1e-10)
+
+
 @pytest.mark.parametrize("scheme", ["centroid", "path"])
 @pytest.mark.parametrize("sizes,fan", [([3] * 20, 2), ([2] * 32, 1), ([1] * 10 + [4] * 7, 5), ([5, 1, 2, 3, 1, 4, 2, 1, 3, 2, 1, 1, 6, 2, 3, 1, 2, 4, 1, 2, 3, 1, 1, 2], 3)])
 def test_wave16_solver_for_17_to_32_lvs(sizes, fan, scheme):
