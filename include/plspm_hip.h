@@ -44,7 +44,8 @@ enum {
     PLSPM_OK = 0,
     PLSPM_NOT_CONVERGED = 1, /* reference raises Exception("Could not converge ...") weights.py:185-186 */
     PLSPM_SINGULAR = 2,      /* a regression the reference cannot solve either (e.g. Mode B on a block with missing cells, mode.py:55-56) */
-    PLSPM_NONFINITE = 3      /* zero-variance MV or NaN input                                            */
+    PLSPM_NONFINITE = 3,     /* zero-variance MV or NaN input                                            */
+    PLSPM_INADMISSIBLE = 4   /* PLSc records only (plspm_plsc_*): a factor's rho_A is not positive and finite, or a corrected construct correlation is not below 1 in magnitude */
 };
 /* Argument errors returned by the API functions themselves. */
 enum { PLSPM_E_ARG = 100, PLSPM_E_STATE = 101, PLSPM_E_LIMIT = 102 };
@@ -535,6 +536,45 @@ int plspm_assess_summary(plspm_model_t* m, int64_t B, const double* original, do
 int plspm_assess_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
 
 /*
+ * ---- Consistent PLS (PLSc) of the bootstrap -------------------------------------------------------------------------------------
+ * Dijkstra and Henseler's (2015) correction for attenuation, for every replicate: one more kernel behind the assessment kernel.  From the
+ * assessment's quantities of a data set -- the normalised standardised weights v (v_l' R_ll v_l = 1), the fit's sign sigma_l, rho_a[l] and the signed construct
+ * correlations lv_cor_ij -- and a factor mask (which LVs are common factors; default: every Mode-A block of two items or more):
+ *     Q_l       rho_a[l] for a factor, 1 otherwise
+ *     rc_ij     lv_cor_ij / sqrt(Q_i Q_j) for i != j, rc_ii = 1                      the corrected construct correlations
+ *     inner model: the solver's own, on rc in place of the score covariance -- per endogenous LV the normal equations on its predecessors (the same pivot
+ *               rule, the same minimum-norm fallback), R2_j = beta' rc_pj, indirect effects by forward substitution, total = direct + indirect on the
+ *               pairs of plspm_effect_pairs.  With an all-zero mask this is the bootstrap record up to rounding.
+ *     loadings  factor l: sigma_l v_p sqrt(Q_l) / (v_l' v_l); any other LV: the record's.  Weights: the record's.
+ * PLSc record, width W = R + npairs (R = plspm_row_width, npairs = L (L - 1) / 2):  weights[P] | r2[L] | total[n_eff] | direct[n_eff] | loadings[P] |
+ * lv_cor_c[npairs] (i < j, i-major);  device records carry a status and the replicate's iteration count behind it as doubles (pitch W + 2).  A replicate whose
+ * bootstrap status is not PLSPM_OK keeps that status and has NaN in all W values.  PLSPM_INADMISSIBLE (NaN in all W values, not counted in n_used): a factor's
+ * rho_a is not finite or <= 0, or some |rc_ij| is not below 1 (a NaN included).  PLSPM_SINGULAR: a regression the shared routine reports as failed (the
+ * values stand, as in the solver).  Plain metric handles only (no non-metric scales, no missing values, not part of a two-stage pair): PLSPM_E_ARG otherwise.
+ *
+ * plspm_plsc_enable: on != 0: every later plspm_bootstrap / plspm_bootstrap_device call on this handle also writes the PLSc records of its replicates into a
+ *   buffer of their own, indexed like the bootstrap's records -- and the assessment records as well (the PLSc kernel reads them), whether or not
+ *   plspm_assess_enable was called; the bootstrap's records, status and iteration counts, and the assessment records, are bit for bit what they are without
+ *   it.  factor [L] of 0 / 1, or NULL for the default mask; naming a Mode-B or single-item LV as a factor is PLSPM_E_ARG.  Off (the default): no launch, no
+ *   allocation.  Permutation, stratified, cross-validation, jackknife and group calls write none.
+ * plspm_plsc_width: W.
+ * plspm_plsc_fit: the full-sample record, out [W]: the same two kernels on the moments of all uploaded rows and one solver problem (plspm_fit's), with the mask
+ *   of the last plspm_plsc_enable (the default mask if there was none); *status (may be NULL): the record's status.
+ * plspm_plsc_fetch: host copy of the PLSc records [first, first + count) of the last PLSc bootstrap: out [count*W], status [count] (may be NULL).
+ * plspm_plsc_summary / plspm_plsc_intervals: plspm_bootstrap_summary / plspm_bootstrap_intervals on the PLSc records (B: that bootstrap's, else PLSPM_E_ARG):
+ *   original [W] host, summary / out [W*6] host, *n_used (may be NULL).  Methods 0 (percentile), 1 (basic), 2 (bc); 3 (bca) is PLSPM_E_ARG: the jackknife
+ *   writes no PLSc records.
+ * PLSPM_E_STATE from the last three without PLSc records on the handle (none written yet; an upload, or a later call that replaced the bootstrap's records,
+ * voids them; a jackknife leaves them alone).
+ */
+int plspm_plsc_enable(plspm_model_t* m, int32_t on, const uint8_t* factor /*[L] or NULL = default mask*/);
+int32_t plspm_plsc_width(const plspm_model_t* m);
+int plspm_plsc_fit(plspm_model_t* m, double* out, int32_t* status);
+int plspm_plsc_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
+int plspm_plsc_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
+int plspm_plsc_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
+
+/*
  * ---- MICOM: permutation test of measurement invariance --------------------------------------------------------------------------
  * Measurement invariance of composite models (Henseler, Ringle and Sarstedt 2016), steps 2 and 3, for every permutation of plspm_permutation_device: one more
  * kernel behind the solver reads both halves' moment matrices and records.  Per group g of a permutation (problem 2r: a, 2r + 1: b), from its
@@ -698,7 +738,7 @@ int plspm_op_outer_weights_nonmetric(int32_t device_id, int32_t mode, const doub
                                      double correction, double* w, double* Y);
 
 /* Kernel timing with HIP events on the handle's own stream (for the roofline figures in bench.py).
- * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM kernel). */
+ * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM and PLSc kernels). */
 enum { PLSPM_K_RESAMPLE = 0, PLSPM_K_GRAM = 1, PLSPM_K_SOLVER = 2, PLSPM_K_SCORES = 3, PLSPM_K_PACK = 4, PLSPM_K_REDUCE = 5, PLSPM_K_ASSESS = 6, PLSPM_K_COUNT = 7 };
 /* on: 0 off, 1 every kernel, 2 + id only kernel `id` (an event pair costs dispatch latency on both sides: bracketing one kernel of a
  * step perturbs the step less than bracketing all of them). */

@@ -22,6 +22,7 @@ struct AssessArgs {
     const int* boff; const int* lvof; const int* mode;
     const double* rows; long row_stride;
     double* out; long nb;                          // record b at out + b * (A + 2), A = 4 L + 3 L (L - 1) / 2
+    double* side;                                  // optional [nb x 3 L]: per LV the fit's sign | v'Rv | v'v as pass 1 ends with them (kernels_plsc.h reads them); null: no store
     long long* marks;                              // phase clocks of problem 0 (`make marks`; null in the release library)
 };
 #ifdef PLSPM_DEBUG_MARKS
@@ -128,6 +129,7 @@ __global__ void __launch_bounds__(64 * ASSESS_WAVES) assess_kernel(const AssessA
             }
             out[l] = alpha; out[L + l] = rho_a; out[2 * L + l] = rho_c; out[3 * L + l] = ave;
             bm[l] = m; bg[l] = g; bt[l] = sT; bs[l] = (sU < 0.0) ? -1.0 : 1.0;
+            if (a.side) { double* sd = a.side + b * 3L * L; sd[l] = (sU < 0.0) ? -1.0 : 1.0; sd[L + l] = sT; sd[2 * L + l] = s2; }
         }
     }
     assess_wave_sync();

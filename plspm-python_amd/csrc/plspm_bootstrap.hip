@@ -1,6 +1,6 @@
 // plspm_bootstrap.hip -- host side, part 4: the bootstrap driver (resample -> Gram -> solver per chunk of replicates), its C-ABI entry points,
-// the record download, the device summaries and the confidence intervals, and the measurement-model assessment of the replicates (plspm_assess_*).
-// Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h, kernels_assess.h.
+// the record download, the device summaries and the confidence intervals, the measurement-model assessment of the replicates (plspm_assess_*) and their
+// consistent-PLS records (plspm_plsc_*).  Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h, kernels_assess.h, kernels_plsc.h.
 #include "host_internal.h"
 
 #include "philox.h"
@@ -9,6 +9,7 @@
 #include "kernels_summary.h"
 #include "kernels_intervals.h"
 #include "kernels_assess.h"
+#include "kernels_plsc.h"
 
 // dense [C x C] symmetric moment matrix of every replicate out of the tile-packed one (plspm_bootstrap_moments)
 __global__ void __launch_bounds__(256) moments_unpack_kernel(const double* __restrict__ gram, long psize, int T, int C, double* __restrict__ out) {
@@ -21,7 +22,7 @@ static inline int assess_width(const plspm_model* m) { return 4 * m->L + 3 * (m-
 
 // Assessment records of `nb` problems: their moment matrices at `gram` (dense: [(P+1) x cov_ld(P)] upper triangles; else tile-packed), their records at `rows`
 // (row_stride 0: one problem) -> out [nb x (A + 2)].  One wave per problem, four per workgroup (kernels_assess.h).
-static int launch_assess(plspm_model* m, long nb, bool dense, const double* gram, const double* rows, long row_stride, double* out) {
+static int launch_assess(plspm_model* m, long nb, bool dense, const double* gram, const double* rows, long row_stride, double* out, double* side = nullptr) {
     const size_t lds = (size_t)ASSESS_WAVES * assess_wave_doubles(m->P, m->L) * sizeof(double);
     auto k = dense ? assess_kernel<true> : assess_kernel<false>;
     if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
@@ -29,7 +30,7 @@ static int launch_assess(plspm_model* m, long nb, bool dense, const double* gram
     a.gram = gram; a.gstride = dense ? cov_doubles(m->P) : packed_size(m->T); a.ld = dense ? cov_ld(m->P) : m->T;
     a.P = m->P; a.L = m->L; a.R = plspm_row_width(m);
     a.boff = m->d_boff; a.lvof = m->d_lvof; a.mode = m->d_mode;
-    a.rows = rows; a.row_stride = row_stride; a.out = out; a.nb = nb;
+    a.rows = rows; a.row_stride = row_stride; a.out = out; a.nb = nb; a.side = side;
 #ifdef PLSPM_DEBUG_MARKS      // phase clocks of one problem (make marks); never in the release library
     HIPCHK(m, plspm_dmalloc((void**)&a.marks, 4 * sizeof(long long)));
 #endif
@@ -43,6 +44,40 @@ static int launch_assess(plspm_model* m, long nb, bool dense, const double* gram
         HIPCHK(m, hipStreamSynchronize(m->stream));
         HIPCHK(m, hipMemcpy(h, a.marks, sizeof(h), hipMemcpyDeviceToHost));
         fprintf(stderr, "[plspm assess clocks] per-MV values %lld  diagonal blocks %lld  block pairs %lld  total %lld\n", h[1] - h[0], h[2] - h[1], h[3] - h[2], h[3] - h[0]);
+        plspm_dfree(a.marks);
+    }
+#endif
+    return 0;
+}
+
+static inline int plsc_width(const plspm_model* m) { return plspm_row_width(m) + m->L * (m->L - 1) / 2; }
+
+// PLSc records of `nb` problems (kernels_plsc.h): their moment matrices and bootstrap records as launch_assess takes them, the assessment records `assess`
+// [nb x (A + 2)] and the side output `side` [nb x 3 L] that launch wrote -> out [nb x (W + 2)].  One wave per problem, four per workgroup.
+static int launch_plsc(plspm_model* m, long nb, bool dense, const double* gram, const double* rows, long row_stride, const double* assess, const double* side, double* out) {
+    const size_t lds = (size_t)PLSC_WAVES * plsc_ws_doubles(m->P, m->L, m->kmax) * sizeof(double);
+    auto k = dense ? plsc_kernel<true> : plsc_kernel<false>;
+    if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
+    PlscArgs a{};
+    a.gram = gram; a.gstride = dense ? cov_doubles(m->P) : packed_size(m->T); a.ld = dense ? cov_ld(m->P) : m->T;
+    a.R = plspm_row_width(m); a.A = assess_width(m);
+    a.md = make_desc(m);
+    a.factor = (const unsigned char*)m->plsc_mask.p;
+    a.rows = rows; a.row_stride = row_stride; a.assess = assess; a.side = side; a.out = out; a.nb = nb;
+#ifdef PLSPM_DEBUG_MARKS      // phase clocks of one problem (make marks); never in the release library
+    HIPCHK(m, plspm_dmalloc((void**)&a.marks, 16 * sizeof(long long)));
+#endif
+    {
+        ProfScope ps(m, PLSPM_K_ASSESS);
+        hipLaunchKernelGGL(k, dim3((unsigned)((nb + PLSC_WAVES - 1) / PLSC_WAVES)), dim3(64 * PLSC_WAVES), lds, m->stream, a);
+    }
+#ifdef PLSPM_DEBUG_MARKS
+    {
+        long long h[16];
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        HIPCHK(m, hipMemcpy(h, a.marks, sizeof(h), hipMemcpyDeviceToHost));
+        fprintf(stderr, "[plspm plsc clocks] per-MV values %lld  rc %lld  regressions and effects %lld  stores %lld  total %lld\n", h[9] - h[8], h[10] - h[9], h[11] - h[10], h[12] - h[11],
+                h[12] - h[8]);
         plspm_dfree(a.marks);
     }
 #endif
@@ -121,6 +156,11 @@ int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
     const int64_t assess_base = assess_own ? 0 : call.assess_off;
     const int AS = assess_width(m) + 2;
     if (assess && assess_own && (rc = ensure(m, m->assess_rows, (size_t)B * AS * sizeof(double)))) return rc;
+    // PLSc records (plspm_plsc_enable): the assessment's offsets and owners; assess_kernel's side output lasts for one pass
+    const bool plsc = assess && plsc_applies(m, call);
+    const int WS = plsc_width(m) + 2;
+    if (plsc && assess_own && (rc = ensure(m, m->plsc_rows, (size_t)B * WS * sizeof(double)))) return rc;
+    if (plsc && (rc = ensure(m, m->plsc_side, (size_t)chunk * 3 * m->L * sizeof(double)))) return rc;
     // MICOM records (plspm_micom_enable) of a permutation call: one per pair of problems, from position 0 of the call.
     const bool micom = m->micom_on && pairs_problems(call) && plain_metric(m) && !call.rows_out;
     const int MS = 3 * m->L + 2;
@@ -216,13 +256,17 @@ int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
         // (only the last chunk's solver launch may signal the caller's event)
         if ((rc = launch_batch_solver(m, nb, (rows_solver && !f64_gram) ? route : ROUTE_LDS, so, b0 + nb >= B ? call.stop_event : nullptr, &call.stop_taken))) return rc;
         // the chunk's moment matrices are still in m->gram: dense where a dense solver read them, tile-packed for the LDS solver (fp64 Gram, int8 chunks that fell back)
-        if (assess && (rc = launch_assess(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, (double*)m->assess_rows.p + (assess_base + b0) * AS))) return rc;
+        double* const assess_out = assess ? (double*)m->assess_rows.p + (assess_base + b0) * AS : nullptr;
+        if (assess && (rc = launch_assess(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, assess_out, plsc ? (double*)m->plsc_side.p : nullptr))) return rc;
+        if (plsc && (rc = launch_plsc(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, assess_out, (const double*)m->plsc_side.p,
+                                      (double*)m->plsc_rows.p + (assess_base + b0) * WS))) return rc;
         // (a chunk holds whole 256-problem tiles: the pairs stay together, and the chunk that starts at problem b0 starts at permutation b0 / 2)
         if (micom && (rc = launch_micom(m, nb / 2, rows_solver && !f64_gram, gram_buf, so.row, (double*)m->micom_rows.p + (b0 / 2) * MS))) return rc;
     }
     HIPCHK(m, hipGetLastError());
     if (rows_out == (double*)m->rows.p) m->rows_B = B;
     if (assess && assess_own) m->assess_B = B;
+    if (plsc && assess_own) m->plsc_B = B;
     if (micom) m->micom_B = B / 2;
     return 0;
 }
@@ -277,12 +321,14 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
         for (int k = 0; k < nparts; ++k)
             if (!m->ev_part[k]) HIPCHK(m, hipEventCreateWithFlags(&m->ev_part[k], hipEventDisableTiming));
     }
-    void_records(m, REC_ROWS | REC_ASSESS);
+    void_records(m, REC_ROWS | REC_ASSESS | REC_PLSC);
     if ((rc = ensure(m, m->rows, (size_t)B * RS * sizeof(double)))) return rc;
     double* const rows = (double*)m->rows.p;
     // assessment records follow the sub-batches: one buffer for the whole call, every part writes from its first replicate's position (call.assess_off)
     const bool assess = assessable(m, call);
     if (assess && (rc = ensure(m, m->assess_rows, (size_t)B * (assess_width(m) + 2) * sizeof(double)))) return rc;
+    const bool plsc = plsc_applies(m, call);      // ... and so do the PLSc records
+    if (plsc && (rc = ensure(m, m->plsc_rows, (size_t)B * (plsc_width(m) + 2) * sizeof(double)))) return rc;
     int* h_err = (int*)m->h_flag + 10;                   // (+8: plspm_bootstrap_fetch, +9: run_gram_i8's look at the multiplicity flag of an explicit index list)
     h_err[0] = h_err[1] = 0;
     FetchSeg segs[kBootChunksMax];
@@ -305,6 +351,7 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     if (rc) return rc;
     m->rows_B = B;
     if (assess) m->assess_B = B;
+    if (plsc) m->plsc_B = B;
     if (h_err[0] & 4) return fail(m, PLSPM_E_STATE, "plspm_bootstrap: the persistent Gram gave up waiting for a partial tile (device shared with a long-running kernel?); set_option i8_sched 0");
     if (h_err[0] & 1) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: resample index outside [0, N)");
     if ((h_err[0] & 2) || h_err[1]) return fail(m, PLSPM_E_LIMIT, "plspm_bootstrap: a resample multiplicity exceeded 127 on the int8 Gram path (set_option gram_path 1)");
@@ -715,6 +762,99 @@ int plspm_assess_summary(plspm_model_t* m, int64_t B, const double* original, do
 
 int plspm_assess_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
     return m ? side_intervals(m, assess_records(m), B, original, method, level, out, n_used, "plspm_assess_intervals") : fail(m, PLSPM_E_ARG, "plspm_assess_intervals: bad arguments (1 <= B <= 2^30)");
+}
+
+}  // extern "C"
+
+// ---- consistent PLS: per-replicate records [weights | r2 | total | direct | loadings | lv_cor_c | status | iterations]
+static SideRecords plsc_records(const plspm_model* m) {
+    return {m->plsc_rows, m->plsc_B, plsc_width(m), false,
+            ": no PLSc records on this handle (plspm_plsc_enable, then a plain bootstrap; an upload or a later call replaced them)",
+            ": B differs from the last PLSc bootstrap on this handle", ": range exceeds the last PLSc bootstrap's replicates",
+            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no PLSc records, so there is no bca"};
+}
+
+// the default factor mask: every Mode-A block of two items or more
+static std::vector<uint8_t> plsc_default_mask(const plspm_model* m) {
+    std::vector<uint8_t> f((size_t)m->L);
+    for (int l = 0; l < m->L; ++l) f[l] = (m->mode[l] == PLSPM_MODE_A && m->boff[l + 1] - m->boff[l] >= 2) ? 1 : 0;
+    return f;
+}
+
+// the mask the PLSc kernel reads: on the device, behind whatever the stream still runs with the mask before it
+static int plsc_set_mask(plspm_model* m, const std::vector<uint8_t>& f) {
+    HIPCHK(m, hipSetDevice(m->device));
+    if (int rc = ensure(m, m->plsc_mask, (size_t)m->L)) return rc;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(m->plsc_mask.p, f.data(), (size_t)m->L, hipMemcpyHostToDevice));
+    m->plsc_factor = f;
+    return 0;
+}
+
+extern "C" {
+
+int plspm_plsc_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) {
+    if (!m) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: no handle");
+    if (!on) { m->plsc_on = false; return 0; }
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    std::vector<uint8_t> f = plsc_default_mask(m);
+    if (factor) {
+        for (int l = 0; l < m->L; ++l) {
+            if (factor[l] > 1) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: the factor mask holds 0 or 1 per latent variable");
+            if (factor[l] && !f[l]) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: latent variable " + std::to_string(l) + " cannot be a common factor (Mode B, or a single item)");
+            f[l] = factor[l];
+        }
+    }
+    if (int rc = plsc_set_mask(m, f)) return rc;
+    m->plsc_on = true;
+    return 0;
+}
+
+int32_t plspm_plsc_width(const plspm_model_t* m) { return m ? plsc_width(m) : 0; }
+
+int plspm_plsc_fit(plspm_model_t* m, double* out, int32_t* status) {
+    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_plsc_fit: bad arguments");
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_plsc_fit: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_plsc_fit: no data uploaded");
+    HIPCHK(m, hipSetDevice(m->device));
+    int rc;
+    if (m->plsc_factor.empty() && (rc = plsc_set_mask(m, plsc_default_mask(m)))) return rc;      // (never enabled: the default mask)
+    const int RS = plspm_row_stride(m), A = assess_width(m), W = plsc_width(m), L = m->L;
+    // [record RS | assessment A + 2 | side 3 L | PLSc W + 2 | status, iterations (int)]
+    if ((rc = ensure(m, m->plsc_fit, (size_t)(RS + A + 2 + 3 * L + W + 2) * sizeof(double) + 2 * sizeof(int)))) return rc;
+    double* d = (double*)m->plsc_fit.p;
+    double *d_as = d + RS, *d_side = d_as + A + 2, *d_out = d_side + 3 * L;
+    int* d_int = (int*)(d_out + W + 2);
+    if ((rc = dense_moments(m))) return rc;                       // the full sample's moments, tile-packed, in m->gram
+    SolverOut so{};
+    so.row = d; so.row_stride = 0; so.status = d_int; so.iters = d_int + 1;
+    {
+        const double* Mp; long mp_stride;
+        if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;
+        ProfScope ps(m, PLSPM_K_SOLVER);
+        if ((rc = launch_solver(m, 1, Mp, mp_stride, so, 256))) return rc;      // (the problem plspm_fit and plspm_assess_fit solve)
+    }
+    if ((rc = launch_assess(m, 1, false, (const double*)m->gram.p, d, 0, d_as, d_side))) return rc;
+    if ((rc = launch_plsc(m, 1, false, (const double*)m->gram.p, d, 0, d_as, d_side, d_out))) return rc;
+    HIPCHK(m, hipGetLastError());
+    std::vector<double> h((size_t)W + 2);
+    HIPCHK(m, hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    std::copy(h.begin(), h.begin() + W, out);
+    if (status) *status = (h[W] == h[W]) ? (int32_t)h[W] : -1;
+    return 0;
+}
+
+int plspm_plsc_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
+    return m ? side_fetch(m, plsc_records(m), first, count, out, status, "plspm_plsc_fetch") : fail(m, PLSPM_E_ARG, "plspm_plsc_fetch: bad arguments");
+}
+
+int plspm_plsc_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
+    return m ? side_summary(m, plsc_records(m), B, original, summary, n_used, "plspm_plsc_summary") : fail(m, PLSPM_E_ARG, "plspm_plsc_summary: bad arguments (1 <= B <= 2^30)");
+}
+
+int plspm_plsc_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
+    return m ? side_intervals(m, plsc_records(m), B, original, method, level, out, n_used, "plspm_plsc_intervals") : fail(m, PLSPM_E_ARG, "plspm_plsc_intervals: bad arguments (1 <= B <= 2^30)");
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("PLSPM_HIP_LIB", os.path.join(_HERE, "_lib", "libplspm
 ABI_VERSION = 4
 
 STATUS_OK, STATUS_NOT_CONVERGED, STATUS_SINGULAR, STATUS_NONFINITE = 0, 1, 2, 3
+STATUS_INADMISSIBLE = 4      # PLSc records only (plspm_plsc_*)
 KERNELS = {"resample": 0, "gram": 1, "solver": 2, "scores": 3, "pack": 4, "reduce": 5, "assess": 6}
 EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm_model_create", "plspm_model_destroy", "plspm_model_set_nonmetric", "plspm_model_set_categorical", "plspm_model_set_missing", "plspm_model_attach_second_stage", "plspm_model_set_incomplete_rows",
            "plspm_upload", "plspm_effect_pairs", "plspm_row_width", "plspm_row_stride", "plspm_fit", "plspm_bootstrap", "plspm_bootstrap_device", "plspm_bootstrap_summary",
@@ -32,6 +33,7 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_cv_folds", "plspm_cv_device", "plspm_cv_fold_ids", "plspm_cv_moments", "plspm_cv_targets", "plspm_cv_predict",
            "plspm_jackknife_device", "plspm_jackknife_fetch", "plspm_jackknife_stats", "plspm_bootstrap_intervals",
            "plspm_assess_enable", "plspm_assess_width", "plspm_assess_fit", "plspm_assess_fetch", "plspm_assess_summary", "plspm_assess_intervals",
+           "plspm_plsc_enable", "plspm_plsc_width", "plspm_plsc_fit", "plspm_plsc_fetch", "plspm_plsc_summary", "plspm_plsc_intervals",
            "plspm_micom_enable", "plspm_micom_width", "plspm_micom_fetch", "plspm_micom_summary", "plspm_micom_intervals", "plspm_micom_counts"]
 CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
 CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
@@ -131,6 +133,13 @@ def load():
     lib.plspm_assess_fetch.argtypes = [vp, i64, i64, vp, vp]
     lib.plspm_assess_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_assess_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
+    lib.plspm_plsc_enable.argtypes = [vp, i32, vp]
+    lib.plspm_plsc_width.restype = i32
+    lib.plspm_plsc_width.argtypes = [vp]
+    lib.plspm_plsc_fit.argtypes = [vp, vp, ctypes.POINTER(i32)]
+    lib.plspm_plsc_fetch.argtypes = [vp, i64, i64, vp, vp]
+    lib.plspm_plsc_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
+    lib.plspm_plsc_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
     lib.plspm_micom_enable.argtypes = [vp, i32]
     lib.plspm_micom_width.restype = i32
     lib.plspm_micom_width.argtypes = [vp]
@@ -597,6 +606,58 @@ class NativeModel:
         out = np.empty((self.assess_width, 6))
         used = ctypes.c_int64(0)
         self._check(self._lib.plspm_assess_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_assess_intervals")
+        return out, used.value
+
+    def plsc_enable(self, on=True, factor=None):
+        """Consistent PLS (plspm_plsc_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the PLSc record weights | r2 | total | direct |
+        loadings | lv_cor_c of every replicate -- and the assessment records, which the PLSc kernel reads; the bootstrap's own records do not change.
+        ``factor``: 0 / 1 per LV (None: every Mode-A block of two items or more)."""
+        mask = None
+        if factor is not None:
+            mask = np.ascontiguousarray(factor, dtype=np.uint8)
+            if mask.shape != (self.L,):
+                raise ValueError("factor must have one entry per latent variable")
+        self._check(self._lib.plspm_plsc_enable(self._h, int(bool(on)), _ptr(mask) if mask is not None else None), "plspm_plsc_enable")
+
+    @property
+    def plsc_width(self):
+        return int(self._lib.plspm_plsc_width(self._h))
+
+    def plsc_fit(self):
+        """The full-sample PLSc record (plspm_plsc_fit): ([W] values, the record's status)."""
+        out = np.empty(self.plsc_width)
+        status = ctypes.c_int32(-1)
+        self._check(self._lib.plspm_plsc_fit(self._h, _ptr(out), ctypes.byref(status)), "plspm_plsc_fit")
+        return out, status.value
+
+    def plsc_fetch(self, first=0, count=None):
+        """Host copy of the PLSc records [first, first + count) of the last PLSc bootstrap: (records [count, W], status [count])."""
+        if count is None:
+            count = self.last_B - first
+        out = np.empty((max(count, 0), self.plsc_width))
+        status = np.empty(max(count, 0), dtype=np.int32)
+        self._check(self._lib.plspm_plsc_fetch(self._h, first, count, _ptr(out), _ptr(status)), "plspm_plsc_fetch")
+        return out, status
+
+    def plsc_summary(self, B, original):
+        """``summary`` on the PLSc records (plspm_plsc_summary): ([W, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (self.plsc_width,):
+            raise ValueError("original must have plsc_width entries")
+        out = np.empty((self.plsc_width, 6))
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_plsc_summary(self._h, B, _ptr(original), _ptr(out), ctypes.byref(used)), "plspm_plsc_summary")
+        return out, used.value
+
+    def plsc_intervals(self, B, original, method="percentile", level=0.95):
+        """``intervals`` on the PLSc records (plspm_plsc_intervals; no bca): ([W, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (self.plsc_width,):
+            raise ValueError("original must have plsc_width entries")
+        mid = CI_METHODS.index(method) if isinstance(method, str) else int(method)
+        out = np.empty((self.plsc_width, 6))
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_plsc_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_plsc_intervals")
         return out, used.value
 
     def micom_enable(self, on=True):
