@@ -45,7 +45,7 @@ enum {
     PLSPM_NOT_CONVERGED = 1, /* reference raises Exception("Could not converge ...") weights.py:185-186 */
     PLSPM_SINGULAR = 2,      /* a regression the reference cannot solve either (e.g. Mode B on a block with missing cells, mode.py:55-56) */
     PLSPM_NONFINITE = 3,     /* zero-variance MV or NaN input                                            */
-    PLSPM_INADMISSIBLE = 4   /* PLSc records only (plspm_plsc_*): a factor's rho_A is not positive and finite, or a corrected construct correlation is not below 1 in magnitude */
+    PLSPM_INADMISSIBLE = 4   /* PLSc and model-fit records only (plspm_plsc_*, plspm_modelfit_*): a factor's rho_A is not positive and finite, or a corrected construct correlation is not below 1 in magnitude */
 };
 /* Argument errors returned by the API functions themselves. */
 enum { PLSPM_E_ARG = 100, PLSPM_E_STATE = 101, PLSPM_E_LIMIT = 102 };
@@ -575,6 +575,44 @@ int plspm_plsc_summary(plspm_model_t* m, int64_t B, const double* original, doub
 int plspm_plsc_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
 
 /*
+ * ---- Model fit of the bootstrap: SRMR and d_ULS ----------------------------------------------------------------------------------
+ * The discrepancy between a data set's indicator correlations r_pq and the correlations its own model implies, for every replicate: one more kernel behind
+ * the PLSc kernel.  From the replicate's PLSc record -- lambda*_p its loadings (a factor's corrected, any other LV's the fit's), rc_ij its
+ * construct correlations, beta_jm its direct effects -- and the handle's factor mask (the one plspm_plsc_enable sets):
+ *     Phi       saturated model: rc.  Estimated model, LVs in path order:  Phi_jj = 1;  j, k both without predecessors: rc_jk;  j with predecessors, every
+ *               k < j: sum_{m in pred(j)} beta_jm Phi_mk in ascending j (the structural residual of j is uncorrelated with everything before it);  j without,
+ *               an earlier k with predecessors: sum_{m in pred(k)} beta_km Phi_jm in ascending k
+ *     sigma_pq  p, q in blocks i != j: lambda*_p Phi_ij lambda*_q;  p != q in one block: lambda*_p lambda*_q for a factor, r_pq itself for a composite (Mode A
+ *               outside the mask, every Mode-B block: a composite reproduces its own block);  sigma_pp = 1
+ *     d_uls     sum_{p<q} (r_pq - sigma_pq)^2 = 1/2 ||R - Sigma||_F^2            srmr   sqrt(2 d_uls / (P (P + 1)))
+ * Model-fit record, width 4:  srmr_sat | d_uls_sat | srmr_est | d_uls_est;  device records carry a status and the replicate's iteration count behind it as
+ * doubles (pitch 6).  A replicate whose bootstrap status is not PLSPM_OK keeps that status and has NaN in all four.  Otherwise the status is the PLSc
+ * record's; PLSPM_INADMISSIBLE (NaN in all four, not counted in n_used) where that record is inadmissible, where a column is constant in the replicate, and
+ * where a value is not finite.  Plain metric handles only: PLSPM_E_ARG otherwise.
+ *
+ * plspm_modelfit_enable: on != 0: every later plspm_bootstrap / plspm_bootstrap_device call on this handle also writes the model-fit records of its replicates
+ *   into a buffer of their own, indexed like the bootstrap's records -- and the assessment and PLSc records as well, whether or not their own switches are on;
+ *   all of those, and the bootstrap's records, status and iteration counts, are bit for bit what they are without it.  factor [L] of 0 / 1 sets the handle's
+ *   factor mask as plspm_plsc_enable does (the same argument errors); NULL keeps the mask the handle has (the default mask if none was ever set); an all-zero
+ *   mask is the plain composite model.  Off (the default): no launch, no allocation.  Permutation, stratified, cross-validation, jackknife and group calls
+ *   write none.
+ * plspm_modelfit_width: 4.
+ * plspm_modelfit_fit: the full-sample record, out [4]: the same three kernels on the moments of all uploaded rows and one solver problem (plspm_fit's);
+ *   *status (may be NULL): the record's status.
+ * plspm_modelfit_fetch: host copy of the records [first, first + count) of the last model-fit bootstrap: out [count*4], status [count] (may be NULL).
+ * plspm_modelfit_summary / plspm_modelfit_intervals: plspm_bootstrap_summary / plspm_bootstrap_intervals on the model-fit records (B: that bootstrap's, else
+ *   PLSPM_E_ARG): original [4] host, summary / out [4*6] host, *n_used (may be NULL).  Methods 0 (percentile), 1 (basic), 2 (bc); 3 (bca) is PLSPM_E_ARG.
+ * PLSPM_E_STATE from the last three without model-fit records on the handle (none written yet; whatever voids the PLSc records voids these; a jackknife leaves
+ * them alone).
+ */
+int plspm_modelfit_enable(plspm_model_t* m, int32_t on, const uint8_t* factor /*[L] or NULL = keep the handle's mask*/);
+int32_t plspm_modelfit_width(const plspm_model_t* m);
+int plspm_modelfit_fit(plspm_model_t* m, double* out, int32_t* status);
+int plspm_modelfit_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
+int plspm_modelfit_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
+int plspm_modelfit_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
+
+/*
  * ---- MICOM: permutation test of measurement invariance --------------------------------------------------------------------------
  * Measurement invariance of composite models (Henseler, Ringle and Sarstedt 2016), steps 2 and 3, for every permutation of plspm_permutation_device: one more
  * kernel behind the solver reads both halves' moment matrices and records.  Per group g of a permutation (problem 2r: a, 2r + 1: b), from its
@@ -738,7 +776,7 @@ int plspm_op_outer_weights_nonmetric(int32_t device_id, int32_t mode, const doub
                                      double correction, double* w, double* Y);
 
 /* Kernel timing with HIP events on the handle's own stream (for the roofline figures in bench.py).
- * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM and PLSc kernels). */
+ * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM, PLSc and model-fit kernels). */
 enum { PLSPM_K_RESAMPLE = 0, PLSPM_K_GRAM = 1, PLSPM_K_SOLVER = 2, PLSPM_K_SCORES = 3, PLSPM_K_PACK = 4, PLSPM_K_REDUCE = 5, PLSPM_K_ASSESS = 6, PLSPM_K_COUNT = 7 };
 /* on: 0 off, 1 every kernel, 2 + id only kernel `id` (an event pair costs dispatch latency on both sides: bracketing one kernel of a
  * step perturbs the step less than bracketing all of them). */

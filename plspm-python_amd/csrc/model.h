@@ -151,6 +151,11 @@ struct plspm_model {
     std::vector<uint8_t> plsc_factor;        // ... the factor mask [L] it was enabled with (the default mask until then)
     Buf plsc_rows, plsc_side, plsc_mask, plsc_fit;      // ... the replicates' records; a pass's side output of assess_kernel [nb x 3 L]; the mask on the device; plspm_plsc_fit's problem
     int64_t plsc_B = 0;                      // ... the last plain bootstrap whose PLSc records are on the handle (0: none)
+    // model fit of a plain bootstrap's replicates (kernels_modelfit.h; plspm_modelfit_*): records [modelfit_B x 6] in a buffer of their own, indexed like the PLSc
+    // records, which are written whenever these are (the model-fit kernel reads them); the factor mask is PLSc's
+    bool modelfit_on = false;                // plspm_modelfit_enable
+    Buf modelfit_rows;                       // ... the replicates' records
+    int64_t modelfit_B = 0;                  // ... the last plain bootstrap whose model-fit records are on the handle (0: none)
     // MICOM records of a permutation call's splits (kernels_micom.h; plspm_micom_*): records [micom_B x (3 L + 2)] in a buffer of their own, indexed by the
     // permutation's position in the call; the pooled inputs (u, the diagonal blocks of R_0; plspm_micom.hip micom_prepare) once per upload
     bool micom_on = false;                   // plspm_micom_enable
@@ -224,10 +229,12 @@ inline bool pairs_problems(const BatchCall& c) { return c.kind == BatchCall::PER
 inline bool plain_metric(const plspm_model* m) { return !m->nonmetric && !m->categorical && !m->n_ind && !m->nmx_K && !m->stage1 && !m->stage2; }
 // A plain bootstrap whose replicates get assessment records (plspm_assess_enable) if the owner of the bootstrap records takes them: a call into the handle's
 // own `rows` does, plspm_bootstrap() does for its sub-batches (assess_off), a group's shard does not.
-// (with PLSc on the assessment records are written as well: the PLSc kernel reads them)
-inline bool assessable(const plspm_model* m, const BatchCall& c) { return (m->assess_on || m->plsc_on) && plain_metric(m) && c.kind == BatchCall::PLAIN && !c.moments_out; }
+// (with PLSc or model fit on the assessment records are written as well: the PLSc kernel reads them, and the model-fit kernel reads the PLSc records)
+inline bool assessable(const plspm_model* m, const BatchCall& c) { return (m->assess_on || m->plsc_on || m->modelfit_on) && plain_metric(m) && c.kind == BatchCall::PLAIN && !c.moments_out; }
 // ... and PLSc records (plspm_plsc_enable) under the same conditions, at the same positions.
-inline bool plsc_applies(const plspm_model* m, const BatchCall& c) { return m->plsc_on && assessable(m, c); }
+inline bool plsc_applies(const plspm_model* m, const BatchCall& c) { return (m->plsc_on || m->modelfit_on) && assessable(m, c); }
+// ... and model-fit records (plspm_modelfit_enable).
+inline bool modelfit_applies(const plspm_model* m, const BatchCall& c) { return m->modelfit_on && assessable(m, c); }
 
 // The records on a handle, and the one place that voids them.  A batch call voids whatever went with the bootstrap records it replaces (REC_ROWS itself only
 // when it writes the handle's own `rows`); plspm_bootstrap_store replaces the bootstrap records from the host; an upload voids everything.
@@ -238,7 +245,7 @@ inline void void_records(plspm_model* m, unsigned which) {
     if (which & REC_ASSESS) m->assess_B = 0;
     if (which & REC_MICOM) m->micom_B = 0;
     if (which & REC_JACK) m->jack_G = 0;
-    if (which & REC_PLSC) m->plsc_B = 0;
+    if (which & REC_PLSC) m->plsc_B = m->modelfit_B = 0;      // (the model-fit records go with the PLSc records they were computed from)
 }
 // (an entry point voids its own kind's records before it prepares the call -- plspm_cv_device REC_CV, plspm_jackknife_device REC_JACK -- and sets the count
 //  again behind the driver; so does plspm_bootstrap() with REC_ASSESS, which every one of its sub-batches voids here once more)

@@ -1,6 +1,7 @@
 // plspm_bootstrap.hip -- host side, part 4: the bootstrap driver (resample -> Gram -> solver per chunk of replicates), its C-ABI entry points,
-// the record download, the device summaries and the confidence intervals, the measurement-model assessment of the replicates (plspm_assess_*) and their
-// consistent-PLS records (plspm_plsc_*).  Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h, kernels_assess.h, kernels_plsc.h.
+// the record download, the device summaries and the confidence intervals, the measurement-model assessment of the replicates (plspm_assess_*), their
+// consistent-PLS records (plspm_plsc_*) and their model-fit records (plspm_modelfit_*).
+// Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h, kernels_assess.h, kernels_plsc.h, kernels_modelfit.h.
 #include "host_internal.h"
 
 #include "philox.h"
@@ -10,6 +11,7 @@
 #include "kernels_intervals.h"
 #include "kernels_assess.h"
 #include "kernels_plsc.h"
+#include "kernels_modelfit.h"
 
 // dense [C x C] symmetric moment matrix of every replicate out of the tile-packed one (plspm_bootstrap_moments)
 __global__ void __launch_bounds__(256) moments_unpack_kernel(const double* __restrict__ gram, long psize, int T, int C, double* __restrict__ out) {
@@ -78,6 +80,38 @@ static int launch_plsc(plspm_model* m, long nb, bool dense, const double* gram, 
         HIPCHK(m, hipMemcpy(h, a.marks, sizeof(h), hipMemcpyDeviceToHost));
         fprintf(stderr, "[plspm plsc clocks] per-MV values %lld  rc %lld  regressions and effects %lld  stores %lld  total %lld\n", h[9] - h[8], h[10] - h[9], h[11] - h[10], h[12] - h[11],
                 h[12] - h[8]);
+        plspm_dfree(a.marks);
+    }
+#endif
+    return 0;
+}
+
+// Model-fit records of `nb` problems (kernels_modelfit.h): their moment matrices and bootstrap records as launch_assess takes them and the PLSc records `plsc`
+// [nb x (W + 2)] that launch_plsc wrote -> out [nb x 6].  One wave per problem, four per workgroup.
+static int launch_modelfit(plspm_model* m, long nb, bool dense, const double* gram, const double* rows, long row_stride, const double* plsc, double* out) {
+    const size_t lds = (size_t)MODELFIT_WAVES * modelfit_ws_doubles(m->P, m->L) * sizeof(double);
+    auto k = dense ? modelfit_kernel<true> : modelfit_kernel<false>;
+    if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
+    ModelfitArgs a{};
+    a.gram = gram; a.gstride = dense ? cov_doubles(m->P) : packed_size(m->T); a.ld = dense ? cov_ld(m->P) : m->T;
+    a.R = plspm_row_width(m);
+    a.md = make_desc(m);
+    a.factor = (const unsigned char*)m->plsc_mask.p;
+    a.rows = rows; a.row_stride = row_stride; a.plsc = plsc; a.out = out; a.nb = nb;
+#ifdef PLSPM_DEBUG_MARKS      // phase clocks of one problem (make marks); never in the release library
+    HIPCHK(m, plspm_dmalloc((void**)&a.marks, 8 * sizeof(long long)));
+#endif
+    {
+        ProfScope ps(m, PLSPM_K_ASSESS);
+        hipLaunchKernelGGL(k, dim3((unsigned)((nb + MODELFIT_WAVES - 1) / MODELFIT_WAVES)), dim3(64 * MODELFIT_WAVES), lds, m->stream, a);
+    }
+#ifdef PLSPM_DEBUG_MARKS
+    {
+        long long h[8];
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        HIPCHK(m, hipMemcpy(h, a.marks, sizeof(h), hipMemcpyDeviceToHost));
+        fprintf(stderr, "[plspm modelfit clocks] per-MV values %lld  implied construct correlations %lld  residual sweep %lld  stores %lld  total %lld\n", h[1] - h[0], h[2] - h[1],
+                h[3] - h[2], h[4] - h[3], h[4] - h[0]);
         plspm_dfree(a.marks);
     }
 #endif
@@ -161,6 +195,10 @@ int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
     const int WS = plsc_width(m) + 2;
     if (plsc && assess_own && (rc = ensure(m, m->plsc_rows, (size_t)B * WS * sizeof(double)))) return rc;
     if (plsc && (rc = ensure(m, m->plsc_side, (size_t)chunk * 3 * m->L * sizeof(double)))) return rc;
+    // model-fit records (plspm_modelfit_enable): the same offsets and owners
+    const bool modelfit = plsc && modelfit_applies(m, call);
+    const int FS = MODELFIT_WIDTH + 2;
+    if (modelfit && assess_own && (rc = ensure(m, m->modelfit_rows, (size_t)B * FS * sizeof(double)))) return rc;
     // MICOM records (plspm_micom_enable) of a permutation call: one per pair of problems, from position 0 of the call.
     const bool micom = m->micom_on && pairs_problems(call) && plain_metric(m) && !call.rows_out;
     const int MS = 3 * m->L + 2;
@@ -258,8 +296,9 @@ int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
         // the chunk's moment matrices are still in m->gram: dense where a dense solver read them, tile-packed for the LDS solver (fp64 Gram, int8 chunks that fell back)
         double* const assess_out = assess ? (double*)m->assess_rows.p + (assess_base + b0) * AS : nullptr;
         if (assess && (rc = launch_assess(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, assess_out, plsc ? (double*)m->plsc_side.p : nullptr))) return rc;
-        if (plsc && (rc = launch_plsc(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, assess_out, (const double*)m->plsc_side.p,
-                                      (double*)m->plsc_rows.p + (assess_base + b0) * WS))) return rc;
+        double* const plsc_out = plsc ? (double*)m->plsc_rows.p + (assess_base + b0) * WS : nullptr;
+        if (plsc && (rc = launch_plsc(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, assess_out, (const double*)m->plsc_side.p, plsc_out))) return rc;
+        if (modelfit && (rc = launch_modelfit(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, plsc_out, (double*)m->modelfit_rows.p + (assess_base + b0) * FS))) return rc;
         // (a chunk holds whole 256-problem tiles: the pairs stay together, and the chunk that starts at problem b0 starts at permutation b0 / 2)
         if (micom && (rc = launch_micom(m, nb / 2, rows_solver && !f64_gram, gram_buf, so.row, (double*)m->micom_rows.p + (b0 / 2) * MS))) return rc;
     }
@@ -267,6 +306,7 @@ int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
     if (rows_out == (double*)m->rows.p) m->rows_B = B;
     if (assess && assess_own) m->assess_B = B;
     if (plsc && assess_own) m->plsc_B = B;
+    if (modelfit && assess_own) m->modelfit_B = B;
     if (micom) m->micom_B = B / 2;
     return 0;
 }
@@ -329,6 +369,8 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     if (assess && (rc = ensure(m, m->assess_rows, (size_t)B * (assess_width(m) + 2) * sizeof(double)))) return rc;
     const bool plsc = plsc_applies(m, call);      // ... and so do the PLSc records
     if (plsc && (rc = ensure(m, m->plsc_rows, (size_t)B * (plsc_width(m) + 2) * sizeof(double)))) return rc;
+    const bool modelfit = modelfit_applies(m, call);      // ... and the model-fit records
+    if (modelfit && (rc = ensure(m, m->modelfit_rows, (size_t)B * (MODELFIT_WIDTH + 2) * sizeof(double)))) return rc;
     int* h_err = (int*)m->h_flag + 10;                   // (+8: plspm_bootstrap_fetch, +9: run_gram_i8's look at the multiplicity flag of an explicit index list)
     h_err[0] = h_err[1] = 0;
     FetchSeg segs[kBootChunksMax];
@@ -352,6 +394,7 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     m->rows_B = B;
     if (assess) m->assess_B = B;
     if (plsc) m->plsc_B = B;
+    if (modelfit) m->modelfit_B = B;
     if (h_err[0] & 4) return fail(m, PLSPM_E_STATE, "plspm_bootstrap: the persistent Gram gave up waiting for a partial tile (device shared with a long-running kernel?); set_option i8_sched 0");
     if (h_err[0] & 1) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: resample index outside [0, N)");
     if ((h_err[0] & 2) || h_err[1]) return fail(m, PLSPM_E_LIMIT, "plspm_bootstrap: a resample multiplicity exceeded 127 on the int8 Gram path (set_option gram_path 1)");
@@ -791,40 +834,31 @@ static int plsc_set_mask(plspm_model* m, const std::vector<uint8_t>& f) {
     return 0;
 }
 
-extern "C" {
-
-int plspm_plsc_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) {
-    if (!m) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: no handle");
-    if (!on) { m->plsc_on = false; return 0; }
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+// the handle's one factor mask from an entry point's argument (plspm_plsc_enable, plspm_modelfit_enable): checked against what can be a factor, then set
+static int plsc_take_mask(plspm_model* m, const uint8_t* factor, const std::string& who) {
     std::vector<uint8_t> f = plsc_default_mask(m);
-    if (factor) {
-        for (int l = 0; l < m->L; ++l) {
-            if (factor[l] > 1) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: the factor mask holds 0 or 1 per latent variable");
-            if (factor[l] && !f[l]) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: latent variable " + std::to_string(l) + " cannot be a common factor (Mode B, or a single item)");
-            f[l] = factor[l];
-        }
+    for (int l = 0; l < m->L; ++l) {
+        if (factor[l] > 1) return fail(m, PLSPM_E_ARG, who + ": the factor mask holds 0 or 1 per latent variable");
+        if (factor[l] && !f[l]) return fail(m, PLSPM_E_ARG, who + ": latent variable " + std::to_string(l) + " cannot be a common factor (Mode B, or a single item)");
+        f[l] = factor[l];
     }
-    if (int rc = plsc_set_mask(m, f)) return rc;
-    m->plsc_on = true;
-    return 0;
+    return plsc_set_mask(m, f);
 }
 
-int32_t plspm_plsc_width(const plspm_model_t* m) { return m ? plsc_width(m) : 0; }
-
-int plspm_plsc_fit(plspm_model_t* m, double* out, int32_t* status) {
-    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_plsc_fit: bad arguments");
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_plsc_fit: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_plsc_fit: no data uploaded");
+// The full-sample records (plspm_plsc_fit, plspm_modelfit_fit): the kernels of a replicate on the moments of all uploaded rows and plspm_fit's solver problem,
+// with the handle's mask (the default mask if none was ever set).  h: the PLSc record [W + 2], or with `modelfit` the model-fit record [6].
+static int plsc_full_sample(plspm_model* m, bool modelfit, std::vector<double>& h, const std::string& who) {
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, who + ": plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, who + ": no data uploaded");
     HIPCHK(m, hipSetDevice(m->device));
     int rc;
-    if (m->plsc_factor.empty() && (rc = plsc_set_mask(m, plsc_default_mask(m)))) return rc;      // (never enabled: the default mask)
-    const int RS = plspm_row_stride(m), A = assess_width(m), W = plsc_width(m), L = m->L;
-    // [record RS | assessment A + 2 | side 3 L | PLSc W + 2 | status, iterations (int)]
-    if ((rc = ensure(m, m->plsc_fit, (size_t)(RS + A + 2 + 3 * L + W + 2) * sizeof(double) + 2 * sizeof(int)))) return rc;
+    if (m->plsc_factor.empty() && (rc = plsc_set_mask(m, plsc_default_mask(m)))) return rc;
+    const int RS = plspm_row_stride(m), A = assess_width(m), W = plsc_width(m), L = m->L, FS = MODELFIT_WIDTH + 2;
+    // [record RS | assessment A + 2 | side 3 L | PLSc W + 2 | model fit 6 | status, iterations (int)]
+    if ((rc = ensure(m, m->plsc_fit, (size_t)(RS + A + 2 + 3 * L + W + 2 + FS) * sizeof(double) + 2 * sizeof(int)))) return rc;
     double* d = (double*)m->plsc_fit.p;
-    double *d_as = d + RS, *d_side = d_as + A + 2, *d_out = d_side + 3 * L;
-    int* d_int = (int*)(d_out + W + 2);
+    double *d_as = d + RS, *d_side = d_as + A + 2, *d_out = d_side + 3 * L, *d_fit = d_out + W + 2;
+    int* d_int = (int*)(d_fit + FS);
     if ((rc = dense_moments(m))) return rc;                       // the full sample's moments, tile-packed, in m->gram
     SolverOut so{};
     so.row = d; so.row_stride = 0; so.status = d_int; so.iters = d_int + 1;
@@ -836,10 +870,32 @@ int plspm_plsc_fit(plspm_model_t* m, double* out, int32_t* status) {
     }
     if ((rc = launch_assess(m, 1, false, (const double*)m->gram.p, d, 0, d_as, d_side))) return rc;
     if ((rc = launch_plsc(m, 1, false, (const double*)m->gram.p, d, 0, d_as, d_side, d_out))) return rc;
+    if (modelfit && (rc = launch_modelfit(m, 1, false, (const double*)m->gram.p, d, 0, d_out, d_fit))) return rc;
     HIPCHK(m, hipGetLastError());
-    std::vector<double> h((size_t)W + 2);
-    HIPCHK(m, hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    h.resize(modelfit ? (size_t)FS : (size_t)W + 2);
+    HIPCHK(m, hipMemcpyAsync(h.data(), modelfit ? d_fit : d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));
+    return 0;
+}
+
+extern "C" {
+
+int plspm_plsc_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) {
+    if (!m) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: no handle");
+    if (!on) { m->plsc_on = false; return 0; }
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (int rc = factor ? plsc_take_mask(m, factor, "plspm_plsc_enable") : plsc_set_mask(m, plsc_default_mask(m))) return rc;
+    m->plsc_on = true;
+    return 0;
+}
+
+int32_t plspm_plsc_width(const plspm_model_t* m) { return m ? plsc_width(m) : 0; }
+
+int plspm_plsc_fit(plspm_model_t* m, double* out, int32_t* status) {
+    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_plsc_fit: bad arguments");
+    std::vector<double> h;
+    if (int rc = plsc_full_sample(m, false, h, "plspm_plsc_fit")) return rc;
+    const int W = plsc_width(m);
     std::copy(h.begin(), h.begin() + W, out);
     if (status) *status = (h[W] == h[W]) ? (int32_t)h[W] : -1;
     return 0;
@@ -855,6 +911,51 @@ int plspm_plsc_summary(plspm_model_t* m, int64_t B, const double* original, doub
 
 int plspm_plsc_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
     return m ? side_intervals(m, plsc_records(m), B, original, method, level, out, n_used, "plspm_plsc_intervals") : fail(m, PLSPM_E_ARG, "plspm_plsc_intervals: bad arguments (1 <= B <= 2^30)");
+}
+
+}  // extern "C"
+
+// ---- model fit: per-replicate records [srmr_sat | d_uls_sat | srmr_est | d_uls_est | status | iterations]
+static SideRecords modelfit_records(const plspm_model* m) {
+    return {m->modelfit_rows, m->modelfit_B, MODELFIT_WIDTH, true,
+            ": no model-fit records on this handle (plspm_modelfit_enable, then a plain bootstrap; an upload or a later call replaced them)",
+            ": B differs from the last model-fit bootstrap on this handle", ": range exceeds the last model-fit bootstrap's replicates",
+            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no model-fit records, so there is no bca"};
+}
+
+extern "C" {
+
+int plspm_modelfit_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) {
+    if (!m) return fail(m, PLSPM_E_ARG, "plspm_modelfit_enable: no handle");
+    if (!on) { m->modelfit_on = false; return 0; }
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_modelfit_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (factor) { if (int rc = plsc_take_mask(m, factor, "plspm_modelfit_enable")) return rc; }
+    else if (m->plsc_factor.empty()) { if (int rc = plsc_set_mask(m, plsc_default_mask(m))) return rc; }      // (NULL keeps the handle's mask)
+    m->modelfit_on = true;
+    return 0;
+}
+
+int32_t plspm_modelfit_width(const plspm_model_t* m) { return m ? MODELFIT_WIDTH : 0; }
+
+int plspm_modelfit_fit(plspm_model_t* m, double* out, int32_t* status) {
+    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_modelfit_fit: bad arguments");
+    std::vector<double> h;
+    if (int rc = plsc_full_sample(m, true, h, "plspm_modelfit_fit")) return rc;
+    std::copy(h.begin(), h.begin() + MODELFIT_WIDTH, out);
+    if (status) *status = (int32_t)h[MODELFIT_WIDTH];
+    return 0;
+}
+
+int plspm_modelfit_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
+    return m ? side_fetch(m, modelfit_records(m), first, count, out, status, "plspm_modelfit_fetch") : fail(m, PLSPM_E_ARG, "plspm_modelfit_fetch: bad arguments");
+}
+
+int plspm_modelfit_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
+    return m ? side_summary(m, modelfit_records(m), B, original, summary, n_used, "plspm_modelfit_summary") : fail(m, PLSPM_E_ARG, "plspm_modelfit_summary: bad arguments (1 <= B <= 2^30)");
+}
+
+int plspm_modelfit_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
+    return m ? side_intervals(m, modelfit_records(m), B, original, method, level, out, n_used, "plspm_modelfit_intervals") : fail(m, PLSPM_E_ARG, "plspm_modelfit_intervals: bad arguments (1 <= B <= 2^30)");
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PLSPM_HIP_LIB", os.path.join(_HERE, "_lib", "libplspm
 ABI_VERSION = 4
 
 STATUS_OK, STATUS_NOT_CONVERGED, STATUS_SINGULAR, STATUS_NONFINITE = 0, 1, 2, 3
-STATUS_INADMISSIBLE = 4      # PLSc records only (plspm_plsc_*)
+STATUS_INADMISSIBLE = 4      # PLSc and model-fit records only (plspm_plsc_*, plspm_modelfit_*)
 KERNELS = {"resample": 0, "gram": 1, "solver": 2, "scores": 3, "pack": 4, "reduce": 5, "assess": 6}
 EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm_model_create", "plspm_model_destroy", "plspm_model_set_nonmetric", "plspm_model_set_categorical", "plspm_model_set_missing", "plspm_model_attach_second_stage", "plspm_model_set_incomplete_rows",
            "plspm_upload", "plspm_effect_pairs", "plspm_row_width", "plspm_row_stride", "plspm_fit", "plspm_bootstrap", "plspm_bootstrap_device", "plspm_bootstrap_summary",
@@ -34,6 +34,7 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_jackknife_device", "plspm_jackknife_fetch", "plspm_jackknife_stats", "plspm_bootstrap_intervals",
            "plspm_assess_enable", "plspm_assess_width", "plspm_assess_fit", "plspm_assess_fetch", "plspm_assess_summary", "plspm_assess_intervals",
            "plspm_plsc_enable", "plspm_plsc_width", "plspm_plsc_fit", "plspm_plsc_fetch", "plspm_plsc_summary", "plspm_plsc_intervals",
+           "plspm_modelfit_enable", "plspm_modelfit_width", "plspm_modelfit_fit", "plspm_modelfit_fetch", "plspm_modelfit_summary", "plspm_modelfit_intervals",
            "plspm_micom_enable", "plspm_micom_width", "plspm_micom_fetch", "plspm_micom_summary", "plspm_micom_intervals", "plspm_micom_counts"]
 CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
 CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
@@ -140,6 +141,13 @@ def load():
     lib.plspm_plsc_fetch.argtypes = [vp, i64, i64, vp, vp]
     lib.plspm_plsc_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_plsc_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
+    lib.plspm_modelfit_enable.argtypes = [vp, i32, vp]
+    lib.plspm_modelfit_width.restype = i32
+    lib.plspm_modelfit_width.argtypes = [vp]
+    lib.plspm_modelfit_fit.argtypes = [vp, vp, ctypes.POINTER(i32)]
+    lib.plspm_modelfit_fetch.argtypes = [vp, i64, i64, vp, vp]
+    lib.plspm_modelfit_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
+    lib.plspm_modelfit_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
     lib.plspm_micom_enable.argtypes = [vp, i32]
     lib.plspm_micom_width.restype = i32
     lib.plspm_micom_width.argtypes = [vp]
@@ -658,6 +666,58 @@ class NativeModel:
         out = np.empty((self.plsc_width, 6))
         used = ctypes.c_int64(0)
         self._check(self._lib.plspm_plsc_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_plsc_intervals")
+        return out, used.value
+
+    def modelfit_enable(self, on=True, factor=None):
+        """Model fit (plspm_modelfit_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the record srmr_sat | d_uls_sat | srmr_est |
+        d_uls_est of every replicate -- and the assessment and PLSc records, which the model-fit kernel builds on; the bootstrap's own records do not change.
+        ``factor``: 0 / 1 per LV, the handle's one factor mask (None: the mask the handle has, PLSc's default if none was ever set)."""
+        mask = None
+        if factor is not None:
+            mask = np.ascontiguousarray(factor, dtype=np.uint8)
+            if mask.shape != (self.L,):
+                raise ValueError("factor must have one entry per latent variable")
+        self._check(self._lib.plspm_modelfit_enable(self._h, int(bool(on)), _ptr(mask) if mask is not None else None), "plspm_modelfit_enable")
+
+    @property
+    def modelfit_width(self):
+        return int(self._lib.plspm_modelfit_width(self._h))
+
+    def modelfit_fit(self):
+        """The full-sample model-fit record (plspm_modelfit_fit): ([4] values, the record's status)."""
+        out = np.empty(self.modelfit_width)
+        status = ctypes.c_int32(-1)
+        self._check(self._lib.plspm_modelfit_fit(self._h, _ptr(out), ctypes.byref(status)), "plspm_modelfit_fit")
+        return out, status.value
+
+    def modelfit_fetch(self, first=0, count=None):
+        """Host copy of the model-fit records [first, first + count) of the last model-fit bootstrap: (records [count, 4], status [count])."""
+        if count is None:
+            count = self.last_B - first
+        out = np.empty((max(count, 0), self.modelfit_width))
+        status = np.empty(max(count, 0), dtype=np.int32)
+        self._check(self._lib.plspm_modelfit_fetch(self._h, first, count, _ptr(out), _ptr(status)), "plspm_modelfit_fetch")
+        return out, status
+
+    def modelfit_summary(self, B, original):
+        """``summary`` on the model-fit records (plspm_modelfit_summary): ([4, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (self.modelfit_width,):
+            raise ValueError("original must have modelfit_width entries")
+        out = np.empty((self.modelfit_width, 6))
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_modelfit_summary(self._h, B, _ptr(original), _ptr(out), ctypes.byref(used)), "plspm_modelfit_summary")
+        return out, used.value
+
+    def modelfit_intervals(self, B, original, method="percentile", level=0.95):
+        """``intervals`` on the model-fit records (plspm_modelfit_intervals; no bca): ([4, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (self.modelfit_width,):
+            raise ValueError("original must have modelfit_width entries")
+        mid = CI_METHODS.index(method) if isinstance(method, str) else int(method)
+        out = np.empty((self.modelfit_width, 6))
+        used = ctypes.c_int64(0)
+        self._check(self._lib.plspm_modelfit_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_modelfit_intervals")
         return out, used.value
 
     def micom_enable(self, on=True):
