@@ -1,7 +1,8 @@
 // host_internal.h -- what the translation units of libplspm_hip.so share on the HOST side (round 4: the former one-file host is split by
 // concern so that the units compile side by side): plspm_hip.hip (allocator, handles, options, upload, staging), plspm_fit.hip (fp64 Gram,
 // solvers, non-metric iteration, single fit, operator seam), plspm_gram_i8.hip (digit planes + the int8 Gram of bootstrap batches),
-// plspm_bootstrap.hip (bootstrap driver, record download, summaries), plspm_group.cpp (multi-GPU groups).  Every device kernel lives in
+// plspm_bootstrap.hip (bootstrap driver, record download, summaries), plspm_derived.hip (the records derived from a plain bootstrap's replicates),
+// plspm_group.cpp (multi-GPU groups).  Every device kernel lives in
 // exactly one unit's headers; the functions below are the seams between them.  Nothing here is part of the C-ABI (include/plspm_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -108,6 +109,9 @@ int dense_moments(plspm_model* m);
 int launch_gram_lists(plspm_model* m, long nproblems, const int2* ent, const int* nent, long ent_stride, double* out);
 int run_impute(plspm_model* m, long nproblems, const double* Min, const double** Mp, long* mp_stride);
 int launch_solver(plspm_model* m, long nproblems, const double* Mp, long mp_stride, const SolverOut& so, int threads);
+// the full sample as ONE solver problem (the one plspm_fit solves): the moments of all uploaded rows, tile-packed, into m->gram; its record at `record`, its status and
+// iteration count at status_iters[0] and [1]
+int solve_full_sample(plspm_model* m, double* record, int* status_iters);
 // the metric solver of a bootstrap batch: `route` as metric_batch_route chose it when the int8 Gram wrote dense matrices, else ROUTE_LDS
 // stop: an event the launch may signal on completion (the dense solvers do, and set *stop_taken; plspm_fit.hip launch_signalling), or null
 int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const SolverOut& so, hipEvent_t stop, bool* stop_taken);
@@ -137,8 +141,19 @@ int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, d
 // plspm_nonmetric.hip: a Scale.NUM / RAW batch as one solver launch + verification (pl.num_one)
 int run_nonmetric_wave(plspm_model* m, const NmPlan& pl, const SolverOut& so, const void* cd8, int cd8_MT);
 
+// ---- plspm_derived.hip: the chain assessment -> PLSc -> model fit behind a plain metric bootstrap's solver, as the batch driver sees it
+// Once per call: *depth = the deepest stage that applies (0 none, 1 assessment, 2 + PLSc, 3 + model fit) -- a plain call on a plain metric handle, no moments seam,
+// whose owner takes the records: a call into the handle's own `rows` does (and its record buffers are reserved here for call.B replicates), a sub-batch of
+// plspm_bootstrap() does (call.chain_off; that function reserved them for the whole call with this same function), a group's shard does not.
+int derived_begin(plspm_model* m, const BatchCall& call, int* depth);
+// Once per chunk, behind its solver: the chain's launches on `nb` problems whose records start at position `pos` of the record buffers.  gram: their moment matrices
+// (dense: [(P+1) x cov_ld(P)] upper triangles; else tile-packed); rows: their bootstrap records, status included (pitch row_stride).
+int derived_launch(plspm_model* m, int depth, long nb, int64_t pos, bool dense, const double* gram, const double* rows, long row_stride);
+// The owner of the record buffers, behind the last chunk: B records of every stage that ran are valid.
+void derived_commit(plspm_model* m, int depth, int64_t B);
+
 // ---- plspm_bootstrap.hip: side records -- a buffer of records [count x (width + 2)] (values | status | iterations) beside the bootstrap records, valid while
-// `count` is non-zero: the assessment records of a plain bootstrap, the MICOM records of a permutation call.  One description, and the entry points both share.
+// `count` is non-zero: the records of every stage of plspm_derived.hip, the MICOM records of a permutation call.  One description, and the entry points all share.
 // plain_only: the entry points refuse any other handle kind behind their argument check (MICOM; the assessment answers "no records" there).  none / differs /
 // range / method: the kind's whole messages behind "<who>" -- no records, B is not the count, a fetch past the count, a method the intervals do not take
 struct SideRecords { const plspm_model::Buf& buf; int64_t count; int width; bool plain_only; const char *none, *differs, *range, *method; };

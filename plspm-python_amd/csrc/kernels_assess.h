@@ -13,12 +13,13 @@
 // headline's 5,000 replicates, a third of the step).  Row p is read along the lanes: in the dense layout (upper triangle, entry (r, c >= r) at r * ld + c) contiguously wherever q >= p, which is all of pass 2;
 // the entries of a diagonal block below its diagonal (pass 1, q < p) are read down their column.  The tile-packed layout is read through packed_index.
 #pragma once
+#include "kernels_moments.h"
 
 constexpr int ASSESS_WAVES = 4;
 
 struct AssessArgs {
-    const double* gram; long gstride; int ld;      // DENSE: ld = cov_ld(P); else the tile count T of the packed layout
-    int P, L, R;                                   // MVs, LVs, record width (weights at 0, loadings at R - P, status at R, iterations at R + 1)
+    MomentLayout mom;
+    int L, R;                                      // LVs, record width (weights at 0, loadings at R - P, status at R, iterations at R + 1)
     const int* boff; const int* lvof; const int* mode;
     const double* rows; long row_stride;
     double* out; long nb;                          // record b at out + b * (A + 2), A = 4 L + 3 L (L - 1) / 2
@@ -36,11 +37,6 @@ constexpr int ASSESS_ROWS = 16;                    // rows of a block whose load
 // doubles of one wave's LDS slice: 1 / s, mu, v, lambda [P] | m, g, v'Rv, sign [L] | the three pair sums of the current block [L] | one window of three columns [64]
 __host__ __device__ inline long assess_wave_doubles(int P, int L) { return 4L * P + 7L * L + 3 * 64; }
 
-template <bool DENSE> __device__ __forceinline__ double assess_moment(const double* __restrict__ M, int ld, int p, int q) {
-    if (DENSE) { const int r = min(p, q), c = max(p, q); return M[(long)r * ld + c]; }
-    return M[packed_index(ld, p, q)];
-}
-
 // sum of log |r| over a column as ONE logarithm: the factors are multiplied up, and after every fourth the product's exponent moves into an integer (|r| <= 1
 // up to rounding and >= 1e-19 or so unless it is exactly 0, so four factors neither overflow nor underflow; a zero stays a zero: log 0 = -inf, exp(-inf) = 0)
 __device__ __forceinline__ double assess_log_of(double prod, int ex) {
@@ -49,38 +45,29 @@ __device__ __forceinline__ double assess_log_of(double prod, int ex) {
     return fma((double)(ex + e), 0.693147180559945309417, log(prod));
 }
 
-// the lanes of a wave hand values to each other through its LDS slice: the wave's own LDS order, no workgroup barrier
-__device__ __forceinline__ void assess_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 template <bool DENSE>
 __global__ void __launch_bounds__(64 * ASSESS_WAVES) assess_kernel(const AssessArgs a) {
     extern __shared__ double assess_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long b = (long)blockIdx.x * ASSESS_WAVES + wave;
     if (b >= a.nb) return;
-    const int P = a.P, L = a.L, ld = a.ld;
+    const int P = a.mom.P, L = a.L, ld = a.mom.ld;
     const int npairs = L * (L - 1) / 2, A = 4 * L + 3 * npairs;
     const double* __restrict__ rec = a.rows + b * a.row_stride;
     double* __restrict__ out = a.out + b * (long)(A + 2);
     const double st = rec[a.R];
+    if (!(st == 0.0)) { wave_void_record(out, A, st, rec[a.R + 1], lane); return; }
     if (lane == 0) { out[A] = st; out[A + 1] = rec[a.R + 1]; }
-    if (!(st == 0.0)) {                            // a failed replicate: NaN everywhere
-        for (int c = lane; c < A; c += 64) out[c] = __builtin_nan("");
-        return;
-    }
     double* isd = assess_lds + (long)wave * assess_wave_doubles(P, L);
     double *mu = isd + P, *v = mu + P, *lam = v + P, *bm = lam + P, *bg = bm + L, *bt = bg + L, *bs = bt + L, *pa = bs + L, *pg = pa + L, *pt = pg + L, *win = pt + L;
-    const double* __restrict__ M = a.gram + b * a.gstride;
+    const double* __restrict__ M = a.mom.gram + b * a.mom.gstride;
     ASSESS_MARK(0);
     const double inv_n = 1.0 / assess_moment<DENSE>(M, ld, P, P);
     for (int p = lane; p < P; p += 64) {
-        const double m = assess_moment<DENSE>(M, ld, p, P) * inv_n, m2 = assess_moment<DENSE>(M, ld, p, p) * inv_n, var = fma(-m, m, m2);
-        // (a column that is constant in this replicate: its variance is rounding residue of either sign -- zero by solver_core.h treated_sd's threshold, so that
-        //  what divides by it is inf or NaN by IEEE's rules and not a number made of noise; the solver gives such an item weight and loading 0 and status OK)
-        const double s = (var > 1e-9 * m2) ? sqrt(var) : ((var == var) ? 0.0 : var);
-        isd[p] = 1.0 / s; mu[p] = m; v[p] = rec[p] * s; lam[p] = rec[a.R - P + p];
+        const MvStats mv = mv_stats<DENSE>(M, ld, p, P, inv_n);
+        isd[p] = 1.0 / mv.sd; mu[p] = mv.mean; v[p] = rec[p] * mv.sd; lam[p] = rec[a.R - P + p];
     }
-    assess_wave_sync();
+    wave_sync();
     ASSESS_MARK(1);
 
     // ---- pass 1: the diagonal blocks
@@ -132,7 +119,7 @@ __global__ void __launch_bounds__(64 * ASSESS_WAVES) assess_kernel(const AssessA
             if (a.side) { double* sd = a.side + b * 3L * L; sd[l] = (sU < 0.0) ? -1.0 : 1.0; sd[L + l] = sT; sd[2 * L + l] = s2; }
         }
     }
-    assess_wave_sync();
+    wave_sync();
     ASSESS_MARK(2);
 
     // ---- pass 2: block i against every block behind it
@@ -140,7 +127,7 @@ __global__ void __launch_bounds__(64 * ASSESS_WAVES) assess_kernel(const AssessA
     for (int i = 0; i + 1 < L; ++i) {
         const int b0 = a.boff[i], b1 = a.boff[i + 1];
         for (int j = i + 1 + lane; j < L; j += 64) { pa[j] = 0.0; pg[j] = 0.0; pt[j] = 0.0; }
-        assess_wave_sync();
+        wave_sync();
         for (int c0 = b1; c0 < P; c0 += 64) {
             const bool on = c0 + lane < P;
             const int q = on ? c0 + lane : P - 1;
@@ -164,7 +151,7 @@ __global__ void __launch_bounds__(64 * ASSESS_WAVES) assess_kernel(const AssessA
             }
             const double gq = assess_log_of(prod, ex);
             win[lane] = on ? aq : 0.0; win[64 + lane] = on ? gq : 0.0; win[128 + lane] = on ? tq * v[q] : 0.0;
-            assess_wave_sync();
+            wave_sync();
             const int cl = min(c0 + 63, P - 1), jf = a.lvof[c0], jl = a.lvof[cl];      // the blocks this window touches: at most 64
             const int j = jf + lane;
             if (j <= jl) {
@@ -173,7 +160,7 @@ __global__ void __launch_bounds__(64 * ASSESS_WAVES) assess_kernel(const AssessA
                 for (int s = s0; s < s1; ++s) { xa += win[s]; xg += win[64 + s]; xt += win[128 + s]; }
                 pa[j] += xa; pg[j] += xg; pt[j] += xt;
             }
-            assess_wave_sync();
+            wave_sync();
         }
         const double ki = b1 - b0, mi = bm[i], gi = bg[i], ti = bt[i], si = bs[i];
         for (int j = i + 1 + lane; j < L; j += 64) {
@@ -183,7 +170,7 @@ __global__ void __launch_bounds__(64 * ASSESS_WAVES) assess_kernel(const AssessA
             out[e + npairs] = exp(pg[j] / cnt) / sqrt(gi * bg[j]);
             out[e + 2L * npairs] = si * bs[j] * pt[j] / sqrt(ti * bt[j]);
         }
-        assess_wave_sync();
+        wave_sync();
         pbase += L - 1 - i;
     }
     ASSESS_MARK(3);

@@ -13,14 +13,15 @@
 // depends on the largest block and not on P: 4 k_max doubles.  The loads of eight rows -- three matrices each -- are issued together (one memory round trip per
 // batch of rows, not per row: kernels_assess.h).  Only the diagonal blocks of the three matrices are read.
 #pragma once
+#include "kernels_moments.h"
 
 constexpr int MICOM_WAVES = 4;
 constexpr int MICOM_ROWS = 8;                      // rows of a block whose loads (M_a, M_b, R_0) are in flight together
 constexpr int MICOM_COUNT_NT = 256;
 
 struct MicomArgs {
-    const double* gram; long gstride; int ld;      // DENSE: ld = cov_ld(P); else the tile count T of the packed layout; problem j at gram + j * gstride
-    int P, L, R, kb;                               // MVs, LVs, record width (weights at 0, status at R, iterations at R + 1), largest block
+    MomentLayout mom;
+    int L, R, kb;                                  // LVs, record width (weights at 0, status at R, iterations at R + 1), largest block
     const int* boff;
     const double* rows; long row_stride;           // record of problem j at rows + j * row_stride
     const double* u; const double* r0;             // pooled: u [P]; R_0's diagonal blocks, block l row-major [k_l x k_l] behind those before it
@@ -36,35 +37,28 @@ __global__ void __launch_bounds__(64 * MICOM_WAVES) micom_kernel(const MicomArgs
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long r = (long)blockIdx.x * MICOM_WAVES + wave;
     if (r >= a.np) return;
-    const int P = a.P, L = a.L, ld = a.ld, W = 3 * L;
+    const int P = a.mom.P, L = a.L, ld = a.mom.ld, W = 3 * L;
     const double* __restrict__ recA = a.rows + 2 * r * a.row_stride;
     const double* __restrict__ recB = recA + a.row_stride;
     double* __restrict__ out = a.out + r * (long)(W + 2);
     const double sa = recA[a.R], sb = recB[a.R];
     const double st = (sa == 0.0) ? sb : sa;       // 0 iff both are PLSPM_OK, else the first problem's status, or else the second's
+    if (!(st == 0.0)) { wave_void_record(out, W, st, fmax(recA[a.R + 1], recB[a.R + 1]), lane); return; }      // a failed half
     if (lane == 0) { out[W] = st; out[W + 1] = fmax(recA[a.R + 1], recB[a.R + 1]); }
-    if (!(st == 0.0)) {                            // a failed half: NaN everywhere
-        for (int c = lane; c < W; c += 64) out[c] = __builtin_nan("");
-        return;
-    }
     double* va = micom_lds + (long)wave * micom_wave_doubles(a.kb);
     double *vb = va + a.kb, *mua = vb + a.kb, *mub = mua + a.kb;
-    const double* __restrict__ Ma = a.gram + 2 * r * a.gstride;
-    const double* __restrict__ Mb = Ma + a.gstride;
+    const double* __restrict__ Ma = a.mom.gram + 2 * r * a.mom.gstride;
+    const double* __restrict__ Mb = Ma + a.mom.gstride;
     const double na = assess_moment<DENSE>(Ma, ld, P, P), nb = assess_moment<DENSE>(Mb, ld, P, P);
     const double inv_na = 1.0 / na, inv_nb = 1.0 / nb;
     long roff = 0;
     for (int l = 0; l < L; ++l) {
         const int b0 = a.boff[l], b1 = a.boff[l + 1], k = b1 - b0;
         for (int p = b0 + lane; p < b1; p += 64) {
-            // (a column that is constant in this group: zero by treated_sd's threshold, exactly as assess_kernel takes it)
-            const double ma = assess_moment<DENSE>(Ma, ld, p, P) * inv_na, ma2 = assess_moment<DENSE>(Ma, ld, p, p) * inv_na, vara = fma(-ma, ma, ma2);
-            const double mb = assess_moment<DENSE>(Mb, ld, p, P) * inv_nb, mb2 = assess_moment<DENSE>(Mb, ld, p, p) * inv_nb, varb = fma(-mb, mb, mb2);
-            const double ssa = (vara > 1e-9 * ma2) ? sqrt(vara) : ((vara == vara) ? 0.0 : vara);
-            const double ssb = (varb > 1e-9 * mb2) ? sqrt(varb) : ((varb == varb) ? 0.0 : varb);
-            va[p - b0] = recA[p] * ssa; vb[p - b0] = recB[p] * ssb; mua[p - b0] = ma; mub[p - b0] = mb;
+            const MvStats sa_p = mv_stats<DENSE>(Ma, ld, p, P, inv_na), sb_p = mv_stats<DENSE>(Mb, ld, p, P, inv_nb);      // (a column that is constant in its group: sd 0)
+            va[p - b0] = recA[p] * sa_p.sd; vb[p - b0] = recB[p] * sb_p.sd; mua[p - b0] = sa_p.mean; mub[p - b0] = sb_p.mean;
         }
-        assess_wave_sync();
+        wave_sync();
         const double* __restrict__ R0 = a.r0 + roff;
         double qaa = 0.0, qbb = 0.0, qab = 0.0, qba = 0.0, qua = 0.0, qub = 0.0, dm = 0.0;
         for (int c0 = b0; c0 < b1; c0 += 64) {
@@ -100,7 +94,7 @@ __global__ void __launch_bounds__(64 * MICOM_WAVES) micom_kernel(const MicomArgs
             out[L + l] = dm;
             out[2 * L + l] = log(na / (na - 1.0) * qua) - log(nb / (nb - 1.0) * qub);
         }
-        assess_wave_sync();                        // (the next block's staging overwrites the slice)
+        wave_sync();                        // (the next block's staging overwrites the slice)
         roff += (long)k * k;
     }
 }
@@ -113,10 +107,7 @@ __global__ void __launch_bounds__(64) micom_pooled_kernel(const double* __restri
     const int lane = threadIdx.x;
     const double inv_n = 1.0 / M[packed_index(T, P, P)];
     const bool ok = rec[R] == 0.0;
-    for (int p = lane; p < P; p += 64) {
-        const double m = M[packed_index(T, p, P)] * inv_n, m2 = M[packed_index(T, p, p)] * inv_n, var = fma(-m, m, m2);
-        s0[p] = (var > 1e-9 * m2) ? sqrt(var) : ((var == var) ? 0.0 : var);
-    }
+    for (int p = lane; p < P; p += 64) s0[p] = mv_stats<false>(M, T, p, P, inv_n).sd;
     __syncthreads();
     long roff = 0;
     for (int l = 0; l < L; ++l) {

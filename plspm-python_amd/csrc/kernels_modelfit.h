@@ -10,13 +10,14 @@
 //   residual sweep: rows p ascending, sixteen rows' loads in flight together; lane q serves column q of a window of 64 behind the rows (dense layout: row p is
 //                   contiguous along the lanes); every lane keeps the two running sums over all its entries, one butterfly sum of each at the end
 #pragma once
+#include "kernels_moments.h"
 #include "modelfit_core.h"
 
 constexpr int MODELFIT_WAVES = 4;
 constexpr int MODELFIT_ROWS = 16;                  // rows whose loads are in flight together (kernels_assess.h ASSESS_ROWS)
 
 struct ModelfitArgs {
-    const double* gram; long gstride; int ld;      // as AssessArgs: DENSE ld = cov_ld(P), else the tile count T
+    MomentLayout mom;
     int R;                                         // bootstrap record width (status at R)
     plspm::ModelDesc md;
     const unsigned char* factor;                   // [L]
@@ -33,30 +34,27 @@ __global__ void __launch_bounds__(64 * MODELFIT_WAVES) modelfit_kernel(const Mod
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long b = (long)blockIdx.x * MODELFIT_WAVES + wave;
     if (b >= a.nb) return;
-    const int P = a.md.P, L = a.md.L, R = a.R, ld = a.ld;
+    const int P = a.md.P, L = a.md.L, R = a.R, ld = a.mom.ld;
     const int W = R + L * (L - 1) / 2;
     const double* __restrict__ rec = a.rows + b * a.row_stride;
     const double* __restrict__ pc = a.plsc + b * (long)(W + 2);
     double* __restrict__ out = a.out + b * (long)(F + 2);
     const double st = rec[R], pst = pc[W];
     if (!(st == 0.0) || pst == (double)plspm::ST_INADMISSIBLE) {      // a failed replicate keeps its status, an inadmissible one the PLSc record's: NaN everywhere
-        if (lane < F) out[lane] = __builtin_nan("");
-        if (lane == 0) { out[F] = (st == 0.0) ? pst : st; out[F + 1] = rec[R + 1]; }
+        wave_void_record(out, F, (st == 0.0) ? pst : st, rec[R + 1], lane);
         return;
     }
     plspm::ModelfitWs w;
     plspm::modelfit_carve(w, modelfit_lds + (long)wave * plspm::modelfit_ws_doubles(P, L), P, L);
     PlscWaveExec ex{lane, (b == 0) ? a.marks : nullptr};
-    const double* __restrict__ M = a.gram + b * a.gstride;
+    const double* __restrict__ M = a.mom.gram + b * a.mom.gstride;
     ex.mark(0);
     const double inv_n = 1.0 / assess_moment<DENSE>(M, ld, P, P);
     bool constant = false;
     for (int p = lane; p < P; p += 64) {
-        const double m = assess_moment<DENSE>(M, ld, p, P) * inv_n, m2 = assess_moment<DENSE>(M, ld, p, p) * inv_n, var = fma(-m, m, m2);
-        const bool varies = var > 1e-9 * m2;                                               // (kernels_assess.h: the rule for a constant column)
-        const double s = varies ? sqrt(var) : ((var == var) ? 0.0 : var);
-        constant = constant || !varies;
-        w.isd[p] = 1.0 / s; w.mu[p] = m; w.lam[p] = pc[R - P + p];
+        const MvStats mv = mv_stats<DENSE>(M, ld, p, P, inv_n);
+        constant = constant || !mv.varies;
+        w.isd[p] = 1.0 / mv.sd; w.mu[p] = mv.mean; w.lam[p] = pc[R - P + p];
     }
     constant = __ballot(constant) != 0ull;
     ex.sync();

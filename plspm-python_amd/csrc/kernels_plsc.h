@@ -9,12 +9,13 @@
 //                for its regression (<= 8 predecessors in registers, more through the LDS scratch), one lane per column for the effects, lanes over the stores
 // Nothing of pass 1 of the assessment is computed again: the block sums arrive through AssessArgs::side.
 #pragma once
+#include "kernels_moments.h"
 #include "plsc_core.h"
 
 constexpr int PLSC_WAVES = 4;
 
 struct PlscArgs {
-    const double* gram; long gstride; int ld;      // as AssessArgs: DENSE ld = cov_ld(P), else the tile count T
+    MomentLayout mom;
     int R, A;                                      // bootstrap record width (status at R), assessment record width (rho_a at L, lv_cor at 4 L + 2 npairs)
     plspm::ModelDesc md;
     const unsigned char* factor;                   // [L]
@@ -35,7 +36,7 @@ struct PlscWaveExec {
 #else
     __device__ __forceinline__ void mark(int) {}
 #endif
-    __device__ __forceinline__ void sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+    __device__ __forceinline__ void sync() { wave_sync(); }
     template <class F> __device__ __forceinline__ void par(int n, F f) { for (int i = lane; i < n; i += 64) f(i); sync(); }
     template <class F> __device__ __forceinline__ void one(F f) { if (lane == 0) f(); sync(); }
     template <class F> __device__ __forceinline__ bool any(int n, F f) {
@@ -51,27 +52,19 @@ __global__ void __launch_bounds__(64 * PLSC_WAVES) plsc_kernel(const PlscArgs a)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long b = (long)blockIdx.x * PLSC_WAVES + wave;
     if (b >= a.nb) return;
-    const int P = a.md.P, L = a.md.L, R = a.R, ld = a.ld;
+    const int P = a.md.P, L = a.md.L, R = a.R, ld = a.mom.ld;
     const int npairs = L * (L - 1) / 2, W = R + npairs;
     const double* __restrict__ rec = a.rows + b * a.row_stride;
     double* __restrict__ out = a.out + b * (long)(W + 2);
     const double st = rec[R];
-    if (!(st == 0.0)) {                            // a failed replicate keeps its status: NaN everywhere
-        if (lane == 0) { out[W] = st; out[W + 1] = rec[R + 1]; }
-        for (int c = lane; c < W; c += 64) out[c] = __builtin_nan("");
-        return;
-    }
+    if (!(st == 0.0)) { wave_void_record(out, W, st, rec[R + 1], lane); return; }
     plspm::PlscWs w;
     plspm::plsc_carve(w, plsc_lds + (long)wave * plspm::plsc_ws_doubles(P, L, a.md.kmax), P, L, a.md.kmax);
     PlscWaveExec ex{lane, (b == 0) ? a.marks : nullptr};
-    const double* __restrict__ M = a.gram + b * a.gstride;
+    const double* __restrict__ M = a.mom.gram + b * a.mom.gstride;
     ex.mark(8);
     const double inv_n = 1.0 / assess_moment<DENSE>(M, ld, P, P);
-    for (int p = lane; p < P; p += 64) {
-        const double m = assess_moment<DENSE>(M, ld, p, P) * inv_n, m2 = assess_moment<DENSE>(M, ld, p, p) * inv_n, var = fma(-m, m, m2);
-        const double s = (var > 1e-9 * m2) ? sqrt(var) : ((var == var) ? 0.0 : var);      // (kernels_assess.h: the rule for a constant column)
-        w.v[p] = rec[p] * s;
-    }
+    for (int p = lane; p < P; p += 64) w.v[p] = rec[p] * mv_stats<DENSE>(M, ld, p, P, inv_n).sd;
     ex.sync();
     ex.mark(9);
     const double* __restrict__ as = a.assess + b * (long)(a.A + 2);

@@ -143,13 +143,13 @@ struct plspm_model {
     // measurement-model assessment of a plain bootstrap's replicates (kernels_assess.h; plspm_assess_*): records [assess_B x (A + 2)] in a buffer of their own,
     // indexed by the replicate's position in the whole call
     bool assess_on = false;                  // plspm_assess_enable
-    Buf assess_rows, assess_fit;             // ... the replicates' records; the full-sample record + its solver problem (plspm_assess_fit)
+    Buf assess_rows, derived_fit;            // ... the replicates' records; the full-sample problem and its records of every stage (plspm_assess_fit, plspm_plsc_fit, plspm_modelfit_fit)
     int64_t assess_B = 0;                    // ... the last plain bootstrap whose assessment records are on the handle (0: none)
     // consistent PLS of a plain bootstrap's replicates (kernels_plsc.h; plspm_plsc_*): records [plsc_B x (R + npairs + 2)] in a buffer of their own, indexed like
     // the assessment records, which are written whenever these are (the PLSc kernel reads them)
     bool plsc_on = false;                    // plspm_plsc_enable
     std::vector<uint8_t> plsc_factor;        // ... the factor mask [L] it was enabled with (the default mask until then)
-    Buf plsc_rows, plsc_side, plsc_mask, plsc_fit;      // ... the replicates' records; a pass's side output of assess_kernel [nb x 3 L]; the mask on the device; plspm_plsc_fit's problem
+    Buf plsc_rows, plsc_side, plsc_mask;     // ... the replicates' records; a pass's side output of assess_kernel [nb x 3 L]; the mask on the device
     int64_t plsc_B = 0;                      // ... the last plain bootstrap whose PLSc records are on the handle (0: none)
     // model fit of a plain bootstrap's replicates (kernels_modelfit.h; plspm_modelfit_*): records [modelfit_B x 6] in a buffer of their own, indexed like the PLSc
     // records, which are written whenever these are (the model-fit kernel reads them); the factor mask is PLSc's
@@ -208,7 +208,7 @@ struct BatchCall {
     double* rows_out = nullptr;
     plspm_model::Buf *status_out = nullptr, *iters_out = nullptr;
     double* moments_out = nullptr;       // test seam (plspm_bootstrap_moments): the problems' dense moment matrices go here and the solver is skipped
-    int64_t assess_off = -1;             // >= 0: the call is a sub-batch of plspm_bootstrap() whose assessment records start here in the caller's assess_rows
+    int64_t chain_off = -1;              // >= 0: the call is a sub-batch of plspm_bootstrap() whose derived records (plspm_derived.hip) start here in the caller's buffers
     // in: the LAST kernel of the batch may signal this event on completion instead of a hipEventRecord behind it (plspm_group.cpp: ~5 us of every step);
     // out: a launch took it (the dense metric solvers do, plspm_fit.hip launch_signalling; every other route leaves the event to the caller)
     hipEvent_t stop_event = nullptr;
@@ -227,14 +227,7 @@ inline bool keeps_records(const BatchCall& c) { return c.kind == BatchCall::JACK
 inline bool pairs_problems(const BatchCall& c) { return c.kind == BatchCall::PERMUTATION; }
 // The handle kinds the two-group tests, the cross-validation, the jackknife, the assessment and MICOM cover.
 inline bool plain_metric(const plspm_model* m) { return !m->nonmetric && !m->categorical && !m->n_ind && !m->nmx_K && !m->stage1 && !m->stage2; }
-// A plain bootstrap whose replicates get assessment records (plspm_assess_enable) if the owner of the bootstrap records takes them: a call into the handle's
-// own `rows` does, plspm_bootstrap() does for its sub-batches (assess_off), a group's shard does not.
-// (with PLSc or model fit on the assessment records are written as well: the PLSc kernel reads them, and the model-fit kernel reads the PLSc records)
-inline bool assessable(const plspm_model* m, const BatchCall& c) { return (m->assess_on || m->plsc_on || m->modelfit_on) && plain_metric(m) && c.kind == BatchCall::PLAIN && !c.moments_out; }
-// ... and PLSc records (plspm_plsc_enable) under the same conditions, at the same positions.
-inline bool plsc_applies(const plspm_model* m, const BatchCall& c) { return (m->plsc_on || m->modelfit_on) && assessable(m, c); }
-// ... and model-fit records (plspm_modelfit_enable).
-inline bool modelfit_applies(const plspm_model* m, const BatchCall& c) { return m->modelfit_on && assessable(m, c); }
+// (which plain bootstrap gets assessment, PLSc and model-fit records: plspm_derived.hip derived_begin)
 
 // The records on a handle, and the one place that voids them.  A batch call voids whatever went with the bootstrap records it replaces (REC_ROWS itself only
 // when it writes the handle's own `rows`); plspm_bootstrap_store replaces the bootstrap records from the host; an upload voids everything.

@@ -1,7 +1,7 @@
-// plspm_bootstrap.hip -- host side, part 4: the bootstrap driver (resample -> Gram -> solver per chunk of replicates), its C-ABI entry points,
-// the record download, the device summaries and the confidence intervals, the measurement-model assessment of the replicates (plspm_assess_*), their
-// consistent-PLS records (plspm_plsc_*) and their model-fit records (plspm_modelfit_*).
-// Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h, kernels_assess.h, kernels_plsc.h, kernels_modelfit.h.
+// plspm_bootstrap.hip -- host side, part 4: the bootstrap driver (resample -> Gram -> solver per chunk of replicates, and behind a plain metric chunk's
+// solver the derived records of plspm_derived.hip), its C-ABI entry points, the record download, the device summaries and the confidence intervals,
+// and what the entry points of every kind of side records share (host_internal.h SideRecords).
+// Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h.
 #include "host_internal.h"
 
 #include "philox.h"
@@ -9,113 +9,12 @@
 #include "kernels_resample.h"
 #include "kernels_summary.h"
 #include "kernels_intervals.h"
-#include "kernels_assess.h"
-#include "kernels_plsc.h"
-#include "kernels_modelfit.h"
 
 // dense [C x C] symmetric moment matrix of every replicate out of the tile-packed one (plspm_bootstrap_moments)
 __global__ void __launch_bounds__(256) moments_unpack_kernel(const double* __restrict__ gram, long psize, int T, int C, double* __restrict__ out) {
     const double* g = gram + (long)blockIdx.x * psize;
     double* o = out + (long)blockIdx.x * C * C;
     for (int e = threadIdx.x; e < C * C; e += 256) { const int p = e / C, q = e - p * C; o[e] = g[packed_index(T, p, q)]; }
-}
-
-static inline int assess_width(const plspm_model* m) { return 4 * m->L + 3 * (m->L * (m->L - 1) / 2); }
-
-// Assessment records of `nb` problems: their moment matrices at `gram` (dense: [(P+1) x cov_ld(P)] upper triangles; else tile-packed), their records at `rows`
-// (row_stride 0: one problem) -> out [nb x (A + 2)].  One wave per problem, four per workgroup (kernels_assess.h).
-static int launch_assess(plspm_model* m, long nb, bool dense, const double* gram, const double* rows, long row_stride, double* out, double* side = nullptr) {
-    const size_t lds = (size_t)ASSESS_WAVES * assess_wave_doubles(m->P, m->L) * sizeof(double);
-    auto k = dense ? assess_kernel<true> : assess_kernel<false>;
-    if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
-    AssessArgs a{};
-    a.gram = gram; a.gstride = dense ? cov_doubles(m->P) : packed_size(m->T); a.ld = dense ? cov_ld(m->P) : m->T;
-    a.P = m->P; a.L = m->L; a.R = plspm_row_width(m);
-    a.boff = m->d_boff; a.lvof = m->d_lvof; a.mode = m->d_mode;
-    a.rows = rows; a.row_stride = row_stride; a.out = out; a.nb = nb; a.side = side;
-#ifdef PLSPM_DEBUG_MARKS      // phase clocks of one problem (make marks); never in the release library
-    HIPCHK(m, plspm_dmalloc((void**)&a.marks, 4 * sizeof(long long)));
-#endif
-    {
-        ProfScope ps(m, PLSPM_K_ASSESS);
-        hipLaunchKernelGGL(k, dim3((unsigned)((nb + ASSESS_WAVES - 1) / ASSESS_WAVES)), dim3(64 * ASSESS_WAVES), lds, m->stream, a);
-    }
-#ifdef PLSPM_DEBUG_MARKS
-    {
-        long long h[4];
-        HIPCHK(m, hipStreamSynchronize(m->stream));
-        HIPCHK(m, hipMemcpy(h, a.marks, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[plspm assess clocks] per-MV values %lld  diagonal blocks %lld  block pairs %lld  total %lld\n", h[1] - h[0], h[2] - h[1], h[3] - h[2], h[3] - h[0]);
-        plspm_dfree(a.marks);
-    }
-#endif
-    return 0;
-}
-
-static inline int plsc_width(const plspm_model* m) { return plspm_row_width(m) + m->L * (m->L - 1) / 2; }
-
-// PLSc records of `nb` problems (kernels_plsc.h): their moment matrices and bootstrap records as launch_assess takes them, the assessment records `assess`
-// [nb x (A + 2)] and the side output `side` [nb x 3 L] that launch wrote -> out [nb x (W + 2)].  One wave per problem, four per workgroup.
-static int launch_plsc(plspm_model* m, long nb, bool dense, const double* gram, const double* rows, long row_stride, const double* assess, const double* side, double* out) {
-    const size_t lds = (size_t)PLSC_WAVES * plsc_ws_doubles(m->P, m->L, m->kmax) * sizeof(double);
-    auto k = dense ? plsc_kernel<true> : plsc_kernel<false>;
-    if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
-    PlscArgs a{};
-    a.gram = gram; a.gstride = dense ? cov_doubles(m->P) : packed_size(m->T); a.ld = dense ? cov_ld(m->P) : m->T;
-    a.R = plspm_row_width(m); a.A = assess_width(m);
-    a.md = make_desc(m);
-    a.factor = (const unsigned char*)m->plsc_mask.p;
-    a.rows = rows; a.row_stride = row_stride; a.assess = assess; a.side = side; a.out = out; a.nb = nb;
-#ifdef PLSPM_DEBUG_MARKS      // phase clocks of one problem (make marks); never in the release library
-    HIPCHK(m, plspm_dmalloc((void**)&a.marks, 16 * sizeof(long long)));
-#endif
-    {
-        ProfScope ps(m, PLSPM_K_ASSESS);
-        hipLaunchKernelGGL(k, dim3((unsigned)((nb + PLSC_WAVES - 1) / PLSC_WAVES)), dim3(64 * PLSC_WAVES), lds, m->stream, a);
-    }
-#ifdef PLSPM_DEBUG_MARKS
-    {
-        long long h[16];
-        HIPCHK(m, hipStreamSynchronize(m->stream));
-        HIPCHK(m, hipMemcpy(h, a.marks, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[plspm plsc clocks] per-MV values %lld  rc %lld  regressions and effects %lld  stores %lld  total %lld\n", h[9] - h[8], h[10] - h[9], h[11] - h[10], h[12] - h[11],
-                h[12] - h[8]);
-        plspm_dfree(a.marks);
-    }
-#endif
-    return 0;
-}
-
-// Model-fit records of `nb` problems (kernels_modelfit.h): their moment matrices and bootstrap records as launch_assess takes them and the PLSc records `plsc`
-// [nb x (W + 2)] that launch_plsc wrote -> out [nb x 6].  One wave per problem, four per workgroup.
-static int launch_modelfit(plspm_model* m, long nb, bool dense, const double* gram, const double* rows, long row_stride, const double* plsc, double* out) {
-    const size_t lds = (size_t)MODELFIT_WAVES * modelfit_ws_doubles(m->P, m->L) * sizeof(double);
-    auto k = dense ? modelfit_kernel<true> : modelfit_kernel<false>;
-    if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
-    ModelfitArgs a{};
-    a.gram = gram; a.gstride = dense ? cov_doubles(m->P) : packed_size(m->T); a.ld = dense ? cov_ld(m->P) : m->T;
-    a.R = plspm_row_width(m);
-    a.md = make_desc(m);
-    a.factor = (const unsigned char*)m->plsc_mask.p;
-    a.rows = rows; a.row_stride = row_stride; a.plsc = plsc; a.out = out; a.nb = nb;
-#ifdef PLSPM_DEBUG_MARKS      // phase clocks of one problem (make marks); never in the release library
-    HIPCHK(m, plspm_dmalloc((void**)&a.marks, 8 * sizeof(long long)));
-#endif
-    {
-        ProfScope ps(m, PLSPM_K_ASSESS);
-        hipLaunchKernelGGL(k, dim3((unsigned)((nb + MODELFIT_WAVES - 1) / MODELFIT_WAVES)), dim3(64 * MODELFIT_WAVES), lds, m->stream, a);
-    }
-#ifdef PLSPM_DEBUG_MARKS
-    {
-        long long h[8];
-        HIPCHK(m, hipStreamSynchronize(m->stream));
-        HIPCHK(m, hipMemcpy(h, a.marks, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[plspm modelfit clocks] per-MV values %lld  implied construct correlations %lld  residual sweep %lld  stores %lld  total %lld\n", h[1] - h[0], h[2] - h[1],
-                h[3] - h[2], h[4] - h[3], h[4] - h[0]);
-        plspm_dfree(a.marks);
-    }
-#endif
-    return 0;
 }
 
 int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
@@ -182,23 +81,11 @@ int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
     // Whatever replaces the handle's bootstrap records voids the cross-validation, assessment and MICOM records that went with them (or whose status / iteration
     // buffers are reused); a jackknife call writes into buffers of its own, and whatever the handle holds survives it.
     void_records(m, call);
-    // Assessment records (plspm_assess_enable) of a plain bootstrap: a call of its own (rows_out null) sizes the buffer and starts at record 0; a sub-batch of
-    // plspm_bootstrap() writes from its position in that call (call.assess_off; the buffer is plspm_bootstrap's).  Any other owner of the records (a group's
-    // shard) gets none.
-    const bool assess_own = !call.rows_out;
-    const bool assess = assessable(m, call) && (assess_own || call.assess_off >= 0);
-    const int64_t assess_base = assess_own ? 0 : call.assess_off;
-    const int AS = assess_width(m) + 2;
-    if (assess && assess_own && (rc = ensure(m, m->assess_rows, (size_t)B * AS * sizeof(double)))) return rc;
-    // PLSc records (plspm_plsc_enable): the assessment's offsets and owners; assess_kernel's side output lasts for one pass
-    const bool plsc = assess && plsc_applies(m, call);
-    const int WS = plsc_width(m) + 2;
-    if (plsc && assess_own && (rc = ensure(m, m->plsc_rows, (size_t)B * WS * sizeof(double)))) return rc;
-    if (plsc && (rc = ensure(m, m->plsc_side, (size_t)chunk * 3 * m->L * sizeof(double)))) return rc;
-    // model-fit records (plspm_modelfit_enable): the same offsets and owners
-    const bool modelfit = plsc && modelfit_applies(m, call);
-    const int FS = MODELFIT_WIDTH + 2;
-    if (modelfit && assess_own && (rc = ensure(m, m->modelfit_rows, (size_t)B * FS * sizeof(double)))) return rc;
+    // The derived records of a plain bootstrap (plspm_derived.hip): a call of its own (rows_out null) sizes their buffers and starts at record 0; a sub-batch of
+    // plspm_bootstrap() writes from its position in that call (call.chain_off; the buffers are plspm_bootstrap's).
+    int chain = 0;
+    if ((rc = derived_begin(m, call, &chain))) return rc;
+    const int64_t chain_base = call.rows_out ? call.chain_off : 0;
     // MICOM records (plspm_micom_enable) of a permutation call: one per pair of problems, from position 0 of the call.
     const bool micom = m->micom_on && pairs_problems(call) && plain_metric(m) && !call.rows_out;
     const int MS = 3 * m->L + 2;
@@ -294,19 +181,13 @@ int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
         // (only the last chunk's solver launch may signal the caller's event)
         if ((rc = launch_batch_solver(m, nb, (rows_solver && !f64_gram) ? route : ROUTE_LDS, so, b0 + nb >= B ? call.stop_event : nullptr, &call.stop_taken))) return rc;
         // the chunk's moment matrices are still in m->gram: dense where a dense solver read them, tile-packed for the LDS solver (fp64 Gram, int8 chunks that fell back)
-        double* const assess_out = assess ? (double*)m->assess_rows.p + (assess_base + b0) * AS : nullptr;
-        if (assess && (rc = launch_assess(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, assess_out, plsc ? (double*)m->plsc_side.p : nullptr))) return rc;
-        double* const plsc_out = plsc ? (double*)m->plsc_rows.p + (assess_base + b0) * WS : nullptr;
-        if (plsc && (rc = launch_plsc(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, assess_out, (const double*)m->plsc_side.p, plsc_out))) return rc;
-        if (modelfit && (rc = launch_modelfit(m, nb, rows_solver && !f64_gram, gram_buf, so.row, R, plsc_out, (double*)m->modelfit_rows.p + (assess_base + b0) * FS))) return rc;
+        if ((rc = derived_launch(m, chain, nb, chain_base + b0, rows_solver && !f64_gram, gram_buf, so.row, R))) return rc;
         // (a chunk holds whole 256-problem tiles: the pairs stay together, and the chunk that starts at problem b0 starts at permutation b0 / 2)
         if (micom && (rc = launch_micom(m, nb / 2, rows_solver && !f64_gram, gram_buf, so.row, (double*)m->micom_rows.p + (b0 / 2) * MS))) return rc;
     }
     HIPCHK(m, hipGetLastError());
     if (rows_out == (double*)m->rows.p) m->rows_B = B;
-    if (assess && assess_own) m->assess_B = B;
-    if (plsc && assess_own) m->plsc_B = B;
-    if (modelfit && assess_own) m->modelfit_B = B;
+    if (!call.rows_out) derived_commit(m, chain, B);
     if (micom) m->micom_B = B / 2;
     return 0;
 }
@@ -353,7 +234,7 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     // (a call whose launches may raise the device error word -- model.h may_raise, the driver's own test -- clears that word at the start of every
     //  sub-batch, which would wipe the bits of the sub-batch before: such calls run as one batch, one memset, one read)
     BatchCall call;
-    call.seed = seed; call.d_idx = d_idx;
+    call.B = B; call.seed = seed; call.d_idx = d_idx;
     if (!m->nonmetric && !may_raise(m, call))
         nparts = plspm_detail_chunk_plan(B, (int64_t)RS * (int64_t)sizeof(double), m->tune.boot_chunks, m->tune.boot_ratio, parts, m->tune.boot_align > 0 ? m->tune.boot_align : plspm_detail_round_units(m));
     if (nparts > 1) {
@@ -364,20 +245,16 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     void_records(m, REC_ROWS | REC_ASSESS | REC_PLSC);
     if ((rc = ensure(m, m->rows, (size_t)B * RS * sizeof(double)))) return rc;
     double* const rows = (double*)m->rows.p;
-    // assessment records follow the sub-batches: one buffer for the whole call, every part writes from its first replicate's position (call.assess_off)
-    const bool assess = assessable(m, call);
-    if (assess && (rc = ensure(m, m->assess_rows, (size_t)B * (assess_width(m) + 2) * sizeof(double)))) return rc;
-    const bool plsc = plsc_applies(m, call);      // ... and so do the PLSc records
-    if (plsc && (rc = ensure(m, m->plsc_rows, (size_t)B * (plsc_width(m) + 2) * sizeof(double)))) return rc;
-    const bool modelfit = modelfit_applies(m, call);      // ... and the model-fit records
-    if (modelfit && (rc = ensure(m, m->modelfit_rows, (size_t)B * (MODELFIT_WIDTH + 2) * sizeof(double)))) return rc;
+    // the derived records follow the sub-batches: one buffer per stage for the whole call, every part writes from its first replicate's position (call.chain_off)
+    int chain = 0;
+    if ((rc = derived_begin(m, call, &chain))) return rc;
     int* h_err = (int*)m->h_flag + 10;                   // (+8: plspm_bootstrap_fetch, +9: run_gram_i8's look at the multiplicity flag of an explicit index list)
     h_err[0] = h_err[1] = 0;
     FetchSeg segs[kBootChunksMax];
     int64_t b0 = 0;
     for (int k = 0; k < nparts; ++k) {
         call.B = parts[k]; call.rep_offset = rep_offset + b0; call.d_idx = d_idx ? d_idx + b0 * m->N : nullptr;
-        call.rows_out = rows + b0 * RS; call.assess_off = assess ? b0 : -1;
+        call.rows_out = rows + b0 * RS; call.chain_off = chain ? b0 : -1;
         if ((rc = plspm_detail_bootstrap(m, call))) return rc;
         if (k == nparts - 1) {
             // ONE error word, read with the last sub-batch: copied behind the last kernel, in front of the event its download waits for
@@ -392,9 +269,7 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     if (nparts > 1) HIPCHK(m, hipStreamSynchronize(m->stream));      // (done already: the last download waited for the last kernel; keeps the handle's invariants simple)
     if (rc) return rc;
     m->rows_B = B;
-    if (assess) m->assess_B = B;
-    if (plsc) m->plsc_B = B;
-    if (modelfit) m->modelfit_B = B;
+    derived_commit(m, chain, B);
     if (h_err[0] & 4) return fail(m, PLSPM_E_STATE, "plspm_bootstrap: the persistent Gram gave up waiting for a partial tile (device shared with a long-running kernel?); set_option i8_sched 0");
     if (h_err[0] & 1) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: resample index outside [0, N)");
     if ((h_err[0] & 2) || h_err[1]) return fail(m, PLSPM_E_LIMIT, "plspm_bootstrap: a resample multiplicity exceeded 127 on the int8 Gram path (set_option gram_path 1)");
@@ -714,7 +589,7 @@ int plspm_bootstrap_moments(plspm_model_t* m, int64_t B, uint64_t seed, int64_t 
 
 }  // extern "C"
 
-// ---- side records (host_internal.h SideRecords): the state check, the fetch, the summary and the intervals that plspm_assess_* and plspm_micom_* share
+// ---- side records (host_internal.h SideRecords): the state check, the fetch, the summary and the intervals that the entry points of plspm_derived.hip and plspm_micom_* share
 int side_state(plspm_model* m, const SideRecords& s, int64_t B, const char* who) {
     if (!s.count || !s.buf.p) return fail(m, PLSPM_E_STATE, std::string(who) + s.none);
     if (B != s.count) return fail(m, PLSPM_E_ARG, std::string(who) + s.differs);
@@ -745,217 +620,3 @@ int side_intervals(plspm_model* m, const SideRecords& s, int64_t B, const double
     if (int rc = side_state(m, s, B, who)) return rc;
     return plspm_detail_intervals(m, (const double*)s.buf.p, B, s.width + 2, s.width, original, nullptr, method, level, out, n_used);
 }
-
-// ---- measurement-model assessment: per-replicate records [alpha | rho_a | rho_c | ave | htmt | htmt2 | lv_cor | status | iterations]
-static SideRecords assess_records(const plspm_model* m) {
-    return {m->assess_rows, m->assess_B, assess_width(m), false,
-            ": no assessment records on this handle (plspm_assess_enable, then a plain bootstrap; an upload or a later call replaced them)",
-            ": B differs from the last assessed bootstrap on this handle", ": range exceeds the last assessed bootstrap's replicates",
-            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no assessment records, so there is no bca"};
-}
-
-extern "C" {
-
-int plspm_assess_enable(plspm_model_t* m, int32_t on) {
-    if (!m) return fail(m, PLSPM_E_ARG, "plspm_assess_enable: no handle");
-    if (on && !plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_assess_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    m->assess_on = on != 0;
-    return 0;
-}
-
-int32_t plspm_assess_width(const plspm_model_t* m) { return m ? assess_width(m) : 0; }
-
-int plspm_assess_fit(plspm_model_t* m, double* out, int32_t* status) {
-    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_assess_fit: bad arguments");
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_assess_fit: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_assess_fit: no data uploaded");
-    HIPCHK(m, hipSetDevice(m->device));
-    const int RS = plspm_row_stride(m), A = assess_width(m);
-    int rc;
-    // [record RS | assessment A + 2 | status, iterations (int)]
-    if ((rc = ensure(m, m->assess_fit, (size_t)(RS + A + 2) * sizeof(double) + 2 * sizeof(int)))) return rc;
-    double* d = (double*)m->assess_fit.p;
-    int* d_int = (int*)(d + RS + A + 2);
-    if ((rc = dense_moments(m))) return rc;                       // the full sample's moments, tile-packed, in m->gram
-    SolverOut so{};
-    so.row = d; so.row_stride = 0; so.status = d_int; so.iters = d_int + 1;
-    {
-        const double* Mp; long mp_stride;
-        if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;
-        ProfScope ps(m, PLSPM_K_SOLVER);
-        if ((rc = launch_solver(m, 1, Mp, mp_stride, so, 256))) return rc;      // (the problem plspm_fit solves)
-    }
-    if ((rc = launch_assess(m, 1, false, (const double*)m->gram.p, d, 0, d + RS))) return rc;
-    HIPCHK(m, hipGetLastError());
-    std::vector<double> h((size_t)A + 2);
-    HIPCHK(m, hipMemcpyAsync(h.data(), d + RS, h.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(m, hipStreamSynchronize(m->stream));
-    std::copy(h.begin(), h.begin() + A, out);
-    if (status) *status = (h[A] == h[A]) ? (int32_t)h[A] : -1;
-    return 0;
-}
-
-int plspm_assess_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    return m ? side_fetch(m, assess_records(m), first, count, out, status, "plspm_assess_fetch") : fail(m, PLSPM_E_ARG, "plspm_assess_fetch: bad arguments");
-}
-
-int plspm_assess_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    return m ? side_summary(m, assess_records(m), B, original, summary, n_used, "plspm_assess_summary") : fail(m, PLSPM_E_ARG, "plspm_assess_summary: bad arguments (1 <= B <= 2^30)");
-}
-
-int plspm_assess_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    return m ? side_intervals(m, assess_records(m), B, original, method, level, out, n_used, "plspm_assess_intervals") : fail(m, PLSPM_E_ARG, "plspm_assess_intervals: bad arguments (1 <= B <= 2^30)");
-}
-
-}  // extern "C"
-
-// ---- consistent PLS: per-replicate records [weights | r2 | total | direct | loadings | lv_cor_c | status | iterations]
-static SideRecords plsc_records(const plspm_model* m) {
-    return {m->plsc_rows, m->plsc_B, plsc_width(m), false,
-            ": no PLSc records on this handle (plspm_plsc_enable, then a plain bootstrap; an upload or a later call replaced them)",
-            ": B differs from the last PLSc bootstrap on this handle", ": range exceeds the last PLSc bootstrap's replicates",
-            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no PLSc records, so there is no bca"};
-}
-
-// the default factor mask: every Mode-A block of two items or more
-static std::vector<uint8_t> plsc_default_mask(const plspm_model* m) {
-    std::vector<uint8_t> f((size_t)m->L);
-    for (int l = 0; l < m->L; ++l) f[l] = (m->mode[l] == PLSPM_MODE_A && m->boff[l + 1] - m->boff[l] >= 2) ? 1 : 0;
-    return f;
-}
-
-// the mask the PLSc kernel reads: on the device, behind whatever the stream still runs with the mask before it
-static int plsc_set_mask(plspm_model* m, const std::vector<uint8_t>& f) {
-    HIPCHK(m, hipSetDevice(m->device));
-    if (int rc = ensure(m, m->plsc_mask, (size_t)m->L)) return rc;
-    HIPCHK(m, hipStreamSynchronize(m->stream));
-    HIPCHK(m, hipMemcpy(m->plsc_mask.p, f.data(), (size_t)m->L, hipMemcpyHostToDevice));
-    m->plsc_factor = f;
-    return 0;
-}
-
-// the handle's one factor mask from an entry point's argument (plspm_plsc_enable, plspm_modelfit_enable): checked against what can be a factor, then set
-static int plsc_take_mask(plspm_model* m, const uint8_t* factor, const std::string& who) {
-    std::vector<uint8_t> f = plsc_default_mask(m);
-    for (int l = 0; l < m->L; ++l) {
-        if (factor[l] > 1) return fail(m, PLSPM_E_ARG, who + ": the factor mask holds 0 or 1 per latent variable");
-        if (factor[l] && !f[l]) return fail(m, PLSPM_E_ARG, who + ": latent variable " + std::to_string(l) + " cannot be a common factor (Mode B, or a single item)");
-        f[l] = factor[l];
-    }
-    return plsc_set_mask(m, f);
-}
-
-// The full-sample records (plspm_plsc_fit, plspm_modelfit_fit): the kernels of a replicate on the moments of all uploaded rows and plspm_fit's solver problem,
-// with the handle's mask (the default mask if none was ever set).  h: the PLSc record [W + 2], or with `modelfit` the model-fit record [6].
-static int plsc_full_sample(plspm_model* m, bool modelfit, std::vector<double>& h, const std::string& who) {
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, who + ": plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, who + ": no data uploaded");
-    HIPCHK(m, hipSetDevice(m->device));
-    int rc;
-    if (m->plsc_factor.empty() && (rc = plsc_set_mask(m, plsc_default_mask(m)))) return rc;
-    const int RS = plspm_row_stride(m), A = assess_width(m), W = plsc_width(m), L = m->L, FS = MODELFIT_WIDTH + 2;
-    // [record RS | assessment A + 2 | side 3 L | PLSc W + 2 | model fit 6 | status, iterations (int)]
-    if ((rc = ensure(m, m->plsc_fit, (size_t)(RS + A + 2 + 3 * L + W + 2 + FS) * sizeof(double) + 2 * sizeof(int)))) return rc;
-    double* d = (double*)m->plsc_fit.p;
-    double *d_as = d + RS, *d_side = d_as + A + 2, *d_out = d_side + 3 * L, *d_fit = d_out + W + 2;
-    int* d_int = (int*)(d_fit + FS);
-    if ((rc = dense_moments(m))) return rc;                       // the full sample's moments, tile-packed, in m->gram
-    SolverOut so{};
-    so.row = d; so.row_stride = 0; so.status = d_int; so.iters = d_int + 1;
-    {
-        const double* Mp; long mp_stride;
-        if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;
-        ProfScope ps(m, PLSPM_K_SOLVER);
-        if ((rc = launch_solver(m, 1, Mp, mp_stride, so, 256))) return rc;      // (the problem plspm_fit and plspm_assess_fit solve)
-    }
-    if ((rc = launch_assess(m, 1, false, (const double*)m->gram.p, d, 0, d_as, d_side))) return rc;
-    if ((rc = launch_plsc(m, 1, false, (const double*)m->gram.p, d, 0, d_as, d_side, d_out))) return rc;
-    if (modelfit && (rc = launch_modelfit(m, 1, false, (const double*)m->gram.p, d, 0, d_out, d_fit))) return rc;
-    HIPCHK(m, hipGetLastError());
-    h.resize(modelfit ? (size_t)FS : (size_t)W + 2);
-    HIPCHK(m, hipMemcpyAsync(h.data(), modelfit ? d_fit : d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(m, hipStreamSynchronize(m->stream));
-    return 0;
-}
-
-extern "C" {
-
-int plspm_plsc_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) {
-    if (!m) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: no handle");
-    if (!on) { m->plsc_on = false; return 0; }
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (int rc = factor ? plsc_take_mask(m, factor, "plspm_plsc_enable") : plsc_set_mask(m, plsc_default_mask(m))) return rc;
-    m->plsc_on = true;
-    return 0;
-}
-
-int32_t plspm_plsc_width(const plspm_model_t* m) { return m ? plsc_width(m) : 0; }
-
-int plspm_plsc_fit(plspm_model_t* m, double* out, int32_t* status) {
-    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_plsc_fit: bad arguments");
-    std::vector<double> h;
-    if (int rc = plsc_full_sample(m, false, h, "plspm_plsc_fit")) return rc;
-    const int W = plsc_width(m);
-    std::copy(h.begin(), h.begin() + W, out);
-    if (status) *status = (h[W] == h[W]) ? (int32_t)h[W] : -1;
-    return 0;
-}
-
-int plspm_plsc_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    return m ? side_fetch(m, plsc_records(m), first, count, out, status, "plspm_plsc_fetch") : fail(m, PLSPM_E_ARG, "plspm_plsc_fetch: bad arguments");
-}
-
-int plspm_plsc_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    return m ? side_summary(m, plsc_records(m), B, original, summary, n_used, "plspm_plsc_summary") : fail(m, PLSPM_E_ARG, "plspm_plsc_summary: bad arguments (1 <= B <= 2^30)");
-}
-
-int plspm_plsc_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    return m ? side_intervals(m, plsc_records(m), B, original, method, level, out, n_used, "plspm_plsc_intervals") : fail(m, PLSPM_E_ARG, "plspm_plsc_intervals: bad arguments (1 <= B <= 2^30)");
-}
-
-}  // extern "C"
-
-// ---- model fit: per-replicate records [srmr_sat | d_uls_sat | srmr_est | d_uls_est | status | iterations]
-static SideRecords modelfit_records(const plspm_model* m) {
-    return {m->modelfit_rows, m->modelfit_B, MODELFIT_WIDTH, true,
-            ": no model-fit records on this handle (plspm_modelfit_enable, then a plain bootstrap; an upload or a later call replaced them)",
-            ": B differs from the last model-fit bootstrap on this handle", ": range exceeds the last model-fit bootstrap's replicates",
-            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no model-fit records, so there is no bca"};
-}
-
-extern "C" {
-
-int plspm_modelfit_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) {
-    if (!m) return fail(m, PLSPM_E_ARG, "plspm_modelfit_enable: no handle");
-    if (!on) { m->modelfit_on = false; return 0; }
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_modelfit_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (factor) { if (int rc = plsc_take_mask(m, factor, "plspm_modelfit_enable")) return rc; }
-    else if (m->plsc_factor.empty()) { if (int rc = plsc_set_mask(m, plsc_default_mask(m))) return rc; }      // (NULL keeps the handle's mask)
-    m->modelfit_on = true;
-    return 0;
-}
-
-int32_t plspm_modelfit_width(const plspm_model_t* m) { return m ? MODELFIT_WIDTH : 0; }
-
-int plspm_modelfit_fit(plspm_model_t* m, double* out, int32_t* status) {
-    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_modelfit_fit: bad arguments");
-    std::vector<double> h;
-    if (int rc = plsc_full_sample(m, true, h, "plspm_modelfit_fit")) return rc;
-    std::copy(h.begin(), h.begin() + MODELFIT_WIDTH, out);
-    if (status) *status = (int32_t)h[MODELFIT_WIDTH];
-    return 0;
-}
-
-int plspm_modelfit_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    return m ? side_fetch(m, modelfit_records(m), first, count, out, status, "plspm_modelfit_fetch") : fail(m, PLSPM_E_ARG, "plspm_modelfit_fetch: bad arguments");
-}
-
-int plspm_modelfit_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    return m ? side_summary(m, modelfit_records(m), B, original, summary, n_used, "plspm_modelfit_summary") : fail(m, PLSPM_E_ARG, "plspm_modelfit_summary: bad arguments (1 <= B <= 2^30)");
-}
-
-int plspm_modelfit_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    return m ? side_intervals(m, modelfit_records(m), B, original, method, level, out, n_used, "plspm_modelfit_intervals") : fail(m, PLSPM_E_ARG, "plspm_modelfit_intervals: bad arguments (1 <= B <= 2^30)");
-}
-
-}  // extern "C"

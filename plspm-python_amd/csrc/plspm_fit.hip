@@ -129,6 +129,17 @@ int dense_moments(plspm_model* m) {
     return 0;
 }
 
+int solve_full_sample(plspm_model* m, double* record, int* status_iters) {
+    int rc;
+    if ((rc = dense_moments(m))) return rc;
+    SolverOut so{};
+    so.row = record; so.row_stride = 0; so.status = status_iters; so.iters = status_iters + 1;
+    const double* Mp; long mp_stride;
+    if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;
+    ProfScope ps(m, PLSPM_K_SOLVER);
+    return launch_solver(m, 1, Mp, mp_stride, so, 256);
+}
+
 int launch_gram_lists(plspm_model* m, long nproblems, const int2* ent, const int* nent, long ent_stride, double* out) {
     return launch_gram<false>(m, nproblems, 1, ent, nent, ent_stride, out);
 }

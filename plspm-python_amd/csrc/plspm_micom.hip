@@ -1,10 +1,9 @@
 // plspm_micom.hip -- host side, part 9: MICOM, the permutation test of measurement invariance of composite models.  The pooled inputs of the
 // resident rows (once per upload), the launch of the per-permutation kernel behind a permutation batch's solver (plspm_bootstrap.hip hooks it in beside the
-// assessment), the counts on the records in HBM and the C-ABI entry points (plspm_micom_*).  Kernels: kernels_micom.h (assess_moment: kernels_assess.h).
-#include "host_internal.h"
+// chain of plspm_derived.hip), the counts on the records in HBM and the C-ABI entry points (plspm_micom_*).  Kernels: kernels_micom.h (its opening: kernels_moments.h).
+#include "wave_launch.h"
 
 #include "wave_ops.h"
-#include "kernels_assess.h"
 #include "kernels_micom.h"
 
 static inline int micom_width(const plspm_model* m) { return 3 * m->L; }
@@ -28,16 +27,7 @@ int micom_prepare(plspm_model* m) {
     if ((rc = ensure(m, m->micom_pool, (size_t)(2L * P + K2 + RS) * sizeof(double) + 2 * sizeof(int)))) return rc;
     double* u = (double*)m->micom_pool.p;
     double *s0 = u + P, *r0 = s0 + P, *rec = r0 + K2;
-    int* d_int = (int*)(rec + RS);
-    if ((rc = dense_moments(m))) return rc;                       // the full sample's moments, tile-packed, in m->gram
-    SolverOut so{};
-    so.row = rec; so.row_stride = 0; so.status = d_int; so.iters = d_int + 1;
-    {
-        const double* Mp; long mp_stride;
-        if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;
-        ProfScope ps(m, PLSPM_K_SOLVER);
-        if ((rc = launch_solver(m, 1, Mp, mp_stride, so, 256))) return rc;      // (the problem plspm_fit and plspm_assess_fit solve)
-    }
+    if ((rc = solve_full_sample(m, rec, (int*)(rec + RS)))) return rc;      // (its moments: tile-packed, in m->gram)
     hipLaunchKernelGGL(micom_pooled_kernel, dim3(1), dim3(64), 0, m->stream, (const double*)m->gram.p, m->T, P, m->L, (const int*)m->d_boff, (const double*)rec, plspm_row_width(m), u, s0, r0);
     HIPCHK(m, hipGetLastError());
     m->micom_pool_valid = true;
@@ -46,20 +36,14 @@ int micom_prepare(plspm_model* m) {
 
 int launch_micom(plspm_model* m, long nperm, bool dense, const double* gram, const double* rows, double* out) {
     const int kb = micom_largest_block(m);
-    const size_t lds = (size_t)MICOM_WAVES * micom_wave_doubles(kb) * sizeof(double);
-    auto k = dense ? micom_kernel<true> : micom_kernel<false>;
-    if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
     MicomArgs a{};
-    a.gram = gram; a.gstride = dense ? cov_doubles(m->P) : packed_size(m->T); a.ld = dense ? cov_ld(m->P) : m->T;
-    a.P = m->P; a.L = m->L; a.R = plspm_row_width(m); a.kb = kb;
+    a.mom = moment_layout(m, dense, gram);
+    a.L = m->L; a.R = plspm_row_width(m); a.kb = kb;
     a.boff = m->d_boff;
     a.rows = rows; a.row_stride = plspm_row_stride(m);
     a.u = (const double*)m->micom_pool.p; a.r0 = a.u + 2L * m->P;
     a.out = out; a.np = nperm;
-    {
-        ProfScope ps(m, PLSPM_K_ASSESS);
-        hipLaunchKernelGGL(k, dim3((unsigned)((nperm + MICOM_WAVES - 1) / MICOM_WAVES)), dim3(64 * MICOM_WAVES), lds, m->stream, a);
-    }
+    if (int rc = launch_wave_per_problem(m, dense ? micom_kernel<true> : micom_kernel<false>, a, nperm, MICOM_WAVES, micom_wave_doubles(kb))) return rc;
     m->last_micom_layout = dense ? 1 : 2;
     return 0;
 }

@@ -127,33 +127,16 @@ def load():
     lib.plspm_jackknife_fetch.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.plspm_jackknife_stats.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_bootstrap_intervals.argtypes = [vp, vp, i64, i32, vp, vp, i32, dbl, vp, ctypes.POINTER(i64)]
-    lib.plspm_assess_enable.argtypes = [vp, i32]
-    lib.plspm_assess_width.restype = i32
-    lib.plspm_assess_width.argtypes = [vp]
-    lib.plspm_assess_fit.argtypes = [vp, vp, ctypes.POINTER(i32)]
-    lib.plspm_assess_fetch.argtypes = [vp, i64, i64, vp, vp]
-    lib.plspm_assess_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
-    lib.plspm_assess_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
-    lib.plspm_plsc_enable.argtypes = [vp, i32, vp]
-    lib.plspm_plsc_width.restype = i32
-    lib.plspm_plsc_width.argtypes = [vp]
-    lib.plspm_plsc_fit.argtypes = [vp, vp, ctypes.POINTER(i32)]
-    lib.plspm_plsc_fetch.argtypes = [vp, i64, i64, vp, vp]
-    lib.plspm_plsc_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
-    lib.plspm_plsc_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
-    lib.plspm_modelfit_enable.argtypes = [vp, i32, vp]
-    lib.plspm_modelfit_width.restype = i32
-    lib.plspm_modelfit_width.argtypes = [vp]
-    lib.plspm_modelfit_fit.argtypes = [vp, vp, ctypes.POINTER(i32)]
-    lib.plspm_modelfit_fetch.argtypes = [vp, i64, i64, vp, vp]
-    lib.plspm_modelfit_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
-    lib.plspm_modelfit_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
-    lib.plspm_micom_enable.argtypes = [vp, i32]
-    lib.plspm_micom_width.restype = i32
-    lib.plspm_micom_width.argtypes = [vp]
-    lib.plspm_micom_fetch.argtypes = [vp, i64, i64, vp, vp]
-    lib.plspm_micom_summary.argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
-    lib.plspm_micom_intervals.argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
+    # the four families of side records (assessment, PLSc, model fit, MICOM): one set of signatures; only the first three have a full-sample record
+    for family in ("assess", "plsc", "modelfit", "micom"):
+        getattr(lib, "plspm_%s_enable" % family).argtypes = [vp, i32, vp] if family in ("plsc", "modelfit") else [vp, i32]
+        getattr(lib, "plspm_%s_width" % family).restype = i32
+        getattr(lib, "plspm_%s_width" % family).argtypes = [vp]
+        if family != "micom":
+            getattr(lib, "plspm_%s_fit" % family).argtypes = [vp, vp, ctypes.POINTER(i32)]
+        getattr(lib, "plspm_%s_fetch" % family).argtypes = [vp, i64, i64, vp, vp]
+        getattr(lib, "plspm_%s_summary" % family).argtypes = [vp, i64, vp, vp, ctypes.POINTER(i64)]
+        getattr(lib, "plspm_%s_intervals" % family).argtypes = [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64)]
     lib.plspm_micom_counts.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_profile_enable.argtypes = [vp, i32]
     lib.plspm_profile_read.argtypes = [vp, i32, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
@@ -570,51 +553,63 @@ class NativeModel:
         self._check(self._lib.plspm_jackknife_stats(self._h, G, _ptr(mean), _ptr(se), _ptr(accel), ctypes.byref(used)), "plspm_jackknife_stats")
         return mean, se, accel, used.value
 
+    # ---- side records: the assessment, PLSc and model-fit records of a plain bootstrap and the MICOM records of a permutation call.  One C signature per
+    # operation (plspm_<family>_enable / _width / _fit / _fetch / _summary / _intervals), so one implementation each; the public methods below name the family.
+    def _side_call(self, family, op, *args):
+        name = "plspm_%s_%s" % (family, op)
+        self._check(getattr(self._lib, name)(self._h, *args), name)
+
+    def _side_width(self, family):
+        return int(getattr(self._lib, "plspm_%s_width" % family)(self._h))
+
+    def _side_fit(self, family):
+        out = np.empty(self._side_width(family))
+        status = ctypes.c_int32(-1)
+        self._side_call(family, "fit", _ptr(out), ctypes.byref(status))
+        return out, status.value
+
+    def _side_fetch(self, family, first, count):
+        out = np.empty((max(count, 0), self._side_width(family)))
+        status = np.empty(max(count, 0), dtype=np.int32)
+        self._side_call(family, "fetch", first, count, _ptr(out), _ptr(status))
+        return out, status
+
+    def _side_table(self, family, op, B, original, method=None, level=None):
+        """``summary`` (no method) / ``intervals`` of a family: ([width, 6] table, records used)."""
+        width = self._side_width(family)
+        original = np.ascontiguousarray(original, dtype=np.float64)
+        if original.shape != (width,):
+            raise ValueError("original must have %s_width entries" % family)
+        how = () if method is None else (CI_METHODS.index(method) if isinstance(method, str) else int(method), float(level))
+        out = np.empty((width, 6))
+        used = ctypes.c_int64(0)
+        self._side_call(family, op, B, _ptr(original), *how, _ptr(out), ctypes.byref(used))
+        return out, used.value
+
     def assess_enable(self, on=True):
         """Measurement-model assessment (plspm_assess_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the assessment record
         alpha | rho_a | rho_c | ave [L each] | htmt | htmt2 | lv_cor [L (L - 1) / 2 each] of every replicate; the bootstrap's own records do not change."""
-        self._check(self._lib.plspm_assess_enable(self._h, int(bool(on))), "plspm_assess_enable")
+        self._side_call("assess", "enable", int(bool(on)))
 
     @property
     def assess_width(self):
-        return int(self._lib.plspm_assess_width(self._h))
+        return self._side_width("assess")
 
     def assess_fit(self):
         """The full-sample assessment record (plspm_assess_fit): ([A] values, status of the solver problem behind them)."""
-        out = np.empty(self.assess_width)
-        status = ctypes.c_int32(-1)
-        self._check(self._lib.plspm_assess_fit(self._h, _ptr(out), ctypes.byref(status)), "plspm_assess_fit")
-        return out, status.value
+        return self._side_fit("assess")
 
     def assess_fetch(self, first=0, count=None):
         """Host copy of the assessment records [first, first + count) of the last assessed bootstrap: (records [count, A], status [count])."""
-        if count is None:
-            count = self.last_B - first
-        out = np.empty((max(count, 0), self.assess_width))
-        status = np.empty(max(count, 0), dtype=np.int32)
-        self._check(self._lib.plspm_assess_fetch(self._h, first, count, _ptr(out), _ptr(status)), "plspm_assess_fetch")
-        return out, status
+        return self._side_fetch("assess", first, self.last_B - first if count is None else count)
 
     def assess_summary(self, B, original):
         """``summary`` on the assessment records (plspm_assess_summary): ([A, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
-        original = np.ascontiguousarray(original, dtype=np.float64)
-        if original.shape != (self.assess_width,):
-            raise ValueError("original must have assess_width entries")
-        out = np.empty((self.assess_width, 6))
-        used = ctypes.c_int64(0)
-        self._check(self._lib.plspm_assess_summary(self._h, B, _ptr(original), _ptr(out), ctypes.byref(used)), "plspm_assess_summary")
-        return out, used.value
+        return self._side_table("assess", "summary", B, original)
 
     def assess_intervals(self, B, original, method="percentile", level=0.95):
         """``intervals`` on the assessment records (plspm_assess_intervals; no bca): ([A, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
-        original = np.ascontiguousarray(original, dtype=np.float64)
-        if original.shape != (self.assess_width,):
-            raise ValueError("original must have assess_width entries")
-        mid = CI_METHODS.index(method) if isinstance(method, str) else int(method)
-        out = np.empty((self.assess_width, 6))
-        used = ctypes.c_int64(0)
-        self._check(self._lib.plspm_assess_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_assess_intervals")
-        return out, used.value
+        return self._side_table("assess", "intervals", B, original, method, level)
 
     def plsc_enable(self, on=True, factor=None):
         """Consistent PLS (plspm_plsc_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the PLSc record weights | r2 | total | direct |
@@ -629,44 +624,23 @@ class NativeModel:
 
     @property
     def plsc_width(self):
-        return int(self._lib.plspm_plsc_width(self._h))
+        return self._side_width("plsc")
 
     def plsc_fit(self):
         """The full-sample PLSc record (plspm_plsc_fit): ([W] values, the record's status)."""
-        out = np.empty(self.plsc_width)
-        status = ctypes.c_int32(-1)
-        self._check(self._lib.plspm_plsc_fit(self._h, _ptr(out), ctypes.byref(status)), "plspm_plsc_fit")
-        return out, status.value
+        return self._side_fit("plsc")
 
     def plsc_fetch(self, first=0, count=None):
         """Host copy of the PLSc records [first, first + count) of the last PLSc bootstrap: (records [count, W], status [count])."""
-        if count is None:
-            count = self.last_B - first
-        out = np.empty((max(count, 0), self.plsc_width))
-        status = np.empty(max(count, 0), dtype=np.int32)
-        self._check(self._lib.plspm_plsc_fetch(self._h, first, count, _ptr(out), _ptr(status)), "plspm_plsc_fetch")
-        return out, status
+        return self._side_fetch("plsc", first, self.last_B - first if count is None else count)
 
     def plsc_summary(self, B, original):
         """``summary`` on the PLSc records (plspm_plsc_summary): ([W, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
-        original = np.ascontiguousarray(original, dtype=np.float64)
-        if original.shape != (self.plsc_width,):
-            raise ValueError("original must have plsc_width entries")
-        out = np.empty((self.plsc_width, 6))
-        used = ctypes.c_int64(0)
-        self._check(self._lib.plspm_plsc_summary(self._h, B, _ptr(original), _ptr(out), ctypes.byref(used)), "plspm_plsc_summary")
-        return out, used.value
+        return self._side_table("plsc", "summary", B, original)
 
     def plsc_intervals(self, B, original, method="percentile", level=0.95):
         """``intervals`` on the PLSc records (plspm_plsc_intervals; no bca): ([W, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
-        original = np.ascontiguousarray(original, dtype=np.float64)
-        if original.shape != (self.plsc_width,):
-            raise ValueError("original must have plsc_width entries")
-        mid = CI_METHODS.index(method) if isinstance(method, str) else int(method)
-        out = np.empty((self.plsc_width, 6))
-        used = ctypes.c_int64(0)
-        self._check(self._lib.plspm_plsc_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_plsc_intervals")
-        return out, used.value
+        return self._side_table("plsc", "intervals", B, original, method, level)
 
     def modelfit_enable(self, on=True, factor=None):
         """Model fit (plspm_modelfit_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the record srmr_sat | d_uls_sat | srmr_est |
@@ -681,83 +655,44 @@ class NativeModel:
 
     @property
     def modelfit_width(self):
-        return int(self._lib.plspm_modelfit_width(self._h))
+        return self._side_width("modelfit")
 
     def modelfit_fit(self):
         """The full-sample model-fit record (plspm_modelfit_fit): ([4] values, the record's status)."""
-        out = np.empty(self.modelfit_width)
-        status = ctypes.c_int32(-1)
-        self._check(self._lib.plspm_modelfit_fit(self._h, _ptr(out), ctypes.byref(status)), "plspm_modelfit_fit")
-        return out, status.value
+        return self._side_fit("modelfit")
 
     def modelfit_fetch(self, first=0, count=None):
         """Host copy of the model-fit records [first, first + count) of the last model-fit bootstrap: (records [count, 4], status [count])."""
-        if count is None:
-            count = self.last_B - first
-        out = np.empty((max(count, 0), self.modelfit_width))
-        status = np.empty(max(count, 0), dtype=np.int32)
-        self._check(self._lib.plspm_modelfit_fetch(self._h, first, count, _ptr(out), _ptr(status)), "plspm_modelfit_fetch")
-        return out, status
+        return self._side_fetch("modelfit", first, self.last_B - first if count is None else count)
 
     def modelfit_summary(self, B, original):
         """``summary`` on the model-fit records (plspm_modelfit_summary): ([4, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
-        original = np.ascontiguousarray(original, dtype=np.float64)
-        if original.shape != (self.modelfit_width,):
-            raise ValueError("original must have modelfit_width entries")
-        out = np.empty((self.modelfit_width, 6))
-        used = ctypes.c_int64(0)
-        self._check(self._lib.plspm_modelfit_summary(self._h, B, _ptr(original), _ptr(out), ctypes.byref(used)), "plspm_modelfit_summary")
-        return out, used.value
+        return self._side_table("modelfit", "summary", B, original)
 
     def modelfit_intervals(self, B, original, method="percentile", level=0.95):
         """``intervals`` on the model-fit records (plspm_modelfit_intervals; no bca): ([4, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
-        original = np.ascontiguousarray(original, dtype=np.float64)
-        if original.shape != (self.modelfit_width,):
-            raise ValueError("original must have modelfit_width entries")
-        mid = CI_METHODS.index(method) if isinstance(method, str) else int(method)
-        out = np.empty((self.modelfit_width, 6))
-        used = ctypes.c_int64(0)
-        self._check(self._lib.plspm_modelfit_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_modelfit_intervals")
-        return out, used.value
+        return self._side_table("modelfit", "intervals", B, original, method, level)
 
     def micom_enable(self, on=True):
         """MICOM (plspm_micom_enable): every later ``permutation`` call also writes the record c | dmean | dlogvar [L each] of every permutation --
         compositional invariance and the differences of the pooled composite's means and log variances; the permutation's own records do not change."""
-        self._check(self._lib.plspm_micom_enable(self._h, int(bool(on))), "plspm_micom_enable")
+        self._side_call("micom", "enable", int(bool(on)))
 
     @property
     def micom_width(self):
-        return int(self._lib.plspm_micom_width(self._h))
+        return self._side_width("micom")
 
     def micom_fetch(self, first=0, count=None):
         """Host copy of the MICOM records [first, first + count) of the last MICOM permutation call: (records [count, 3 L], status [count])."""
-        if count is None:
-            count = self.last_B // 2 - first
-        out = np.empty((max(count, 0), self.micom_width))
-        status = np.empty(max(count, 0), dtype=np.int32)
-        self._check(self._lib.plspm_micom_fetch(self._h, first, count, _ptr(out), _ptr(status)), "plspm_micom_fetch")
-        return out, status
+        return self._side_fetch("micom", first, self.last_B // 2 - first if count is None else count)
 
     def micom_summary(self, B, original):
         """``summary`` on the MICOM records (plspm_micom_summary): ([3 L, 6] original, mean, std.error, perc.025, perc.975, t stat.; valid permutations)."""
-        original = np.ascontiguousarray(original, dtype=np.float64)
-        if original.shape != (self.micom_width,):
-            raise ValueError("original must have micom_width entries")
-        out = np.empty((self.micom_width, 6))
-        used = ctypes.c_int64(0)
-        self._check(self._lib.plspm_micom_summary(self._h, B, _ptr(original), _ptr(out), ctypes.byref(used)), "plspm_micom_summary")
-        return out, used.value
+        return self._side_table("micom", "summary", B, original)
 
     def micom_intervals(self, B, original, method="percentile", level=0.95):
         """``intervals`` on the MICOM records (plspm_micom_intervals; no bca): ([3 L, 6] lower, upper, z0, accel, level.lower, level.upper; valid permutations)."""
-        original = np.ascontiguousarray(original, dtype=np.float64)
-        if original.shape != (self.micom_width,):
-            raise ValueError("original must have micom_width entries")
-        mid = CI_METHODS.index(method) if isinstance(method, str) else int(method)
-        out = np.empty((self.micom_width, 6))
-        used = ctypes.c_int64(0)
-        self._check(self._lib.plspm_micom_intervals(self._h, B, _ptr(original), mid, float(level), _ptr(out), ctypes.byref(used)), "plspm_micom_intervals")
-        return out, used.value
+        return self._side_table("micom", "intervals", B, original, method, level)
 
     def micom_counts(self, B, observed):
         """Counts on the MICOM records of the last MICOM permutation call (plspm_micom_counts): ([3 L] int64 #{valid r : x_r <= observed},

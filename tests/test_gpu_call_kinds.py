@@ -1,10 +1,10 @@
 """GPU: every kind of batch call one after the other on ONE handle (plspm_bootstrap.hip plspm_detail_bootstrap and its BatchCall).  The other tests pin each
 kind on a handle of its own; state that a call left behind -- a spec, a destination, an offset, a voided or a forgotten record count -- shows only in a sequence.
 
-On one handle with assessment and MICOM enabled: plain bootstrap (host entry point, cut into sub-batches where the call allows it), permutation, jackknife,
+On one handle with assessment, PLSc, model fit and MICOM enabled: plain bootstrap (host entry point, cut into sub-batches where the call allows it), permutation, jackknife,
 cross-validation, stratified bootstrap, the moments seam, plain bootstrap again (device entry point), upload.  After every step
 
-  * what the step wrote -- records, status, iteration counts, assessment / MICOM records, training moments, moment matrices -- is bit-identical to the same
+  * what the step wrote -- records, status, iteration counts, assessment / PLSc / model-fit / MICOM records, training moments, moment matrices -- is bit-identical to the same
     call on a fresh handle, and
   * every kind's records are there with the expected count, or gone (PLSPM_E_STATE), as the driver's rules say (EFFECT below).
 
@@ -20,26 +20,27 @@ pytestmark = pytest.mark.gpu
 E_ARG, E_STATE = 100, 101
 C3 = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0]])
 B, SPLITS, REPS, K, MOMENTS = 300, 150, 3, 5, 8
-KINDS = ("rows", "cv", "assess", "micom", "jack")
+KINDS = ("rows", "cv", "assess", "plsc", "modelfit", "micom", "jack")
 
 # What a step does to each kind's records: a count (valid, that many), None (void) or absent (unchanged).  Read off plspm_detail_bootstrap: a call voids
-# whatever went with the bootstrap records it replaces; the jackknife writes into buffers of its own.
+# whatever went with the bootstrap records it replaces; the jackknife writes into buffers of its own.  The PLSc and model-fit records follow the assessment's
+# in every step (model.h void_records).
 EFFECT = {
-    "plain": dict(rows=B, cv=None, assess=B, micom=None),
-    "permutation": dict(rows=2 * SPLITS, cv=None, assess=None, micom=SPLITS),
+    "plain": dict(rows=B, cv=None, assess=B, plsc=B, modelfit=B, micom=None),
+    "permutation": dict(rows=2 * SPLITS, cv=None, assess=None, plsc=None, modelfit=None, micom=SPLITS),
     "jackknife": dict(jack="N"),
-    "cv": dict(rows=REPS * K, cv=REPS * K, assess=None, micom=None),
-    "stratified": dict(rows=2 * SPLITS, cv=None, assess=None, micom=None),
-    "moments": dict(rows=None, cv=None, assess=None, micom=None),
-    "plain_device": dict(rows=B, cv=None, assess=B, micom=None),
-    "upload": dict(rows=None, cv=None, assess=None, micom=None, jack=None),
+    "cv": dict(rows=REPS * K, cv=REPS * K, assess=None, plsc=None, modelfit=None, micom=None),
+    "stratified": dict(rows=2 * SPLITS, cv=None, assess=None, plsc=None, modelfit=None, micom=None),
+    "moments": dict(rows=None, cv=None, assess=None, plsc=None, modelfit=None, micom=None),
+    "plain_device": dict(rows=B, cv=None, assess=B, plsc=B, modelfit=B, micom=None),
+    "upload": dict(rows=None, cv=None, assess=None, plsc=None, modelfit=None, micom=None, jack=None),
 }
 SEQUENCE = ("plain", "permutation", "jackknife", "cv", "stratified", "moments", "plain_device", "upload")
 
 
 def new_handle(X, model, cap):
     nm = native_model(model, X)
-    nm.assess_enable()
+    nm.modelfit_enable()                     # (model fit reads the PLSc records, and those the assessment's: all three stages are on)
     nm.micom_enable()
     nm.set_option("boot_pass", cap)
     nm.set_option("boot_chunks", 2)          # plspm_bootstrap() as two sub-batches where the call may be cut (not below 128 rows)
@@ -51,7 +52,7 @@ def run_step(nm, step, X, model, member):
     """The step's call on `nm`; returns every array it wrote."""
     n = X.shape[0]
     if step == "plain":
-        return nm.bootstrap(B, seed=11) + nm.fetch(0, B) + nm.assess_fetch(0, B)
+        return nm.bootstrap(B, seed=11) + nm.fetch(0, B) + nm.assess_fetch(0, B) + nm.plsc_fetch(0, B) + nm.modelfit_fetch(0, B)
     if step == "permutation":
         nm.permutation(SPLITS, (2 * n) // 5, seed=12)
         return nm.fetch(0, 2 * SPLITS) + nm.micom_fetch(0, SPLITS)
@@ -68,7 +69,7 @@ def run_step(nm, step, X, model, member):
         return (nm.bootstrap_moments(MOMENTS, seed=15),)
     if step == "plain_device":
         nm.bootstrap_device(B, seed=16)
-        return nm.fetch(0, B) + nm.assess_fetch(0, B)
+        return nm.fetch(0, B) + nm.assess_fetch(0, B) + nm.plsc_fetch(0, B) + nm.modelfit_fetch(0, B)
     assert step == "upload"
     nm.upload(X, model.mv_order.astype(np.int32))
     return ()
@@ -77,7 +78,8 @@ def run_step(nm, step, X, model, member):
 def check_records(nm, expected):
     """Every kind's fetch serves exactly expected[kind] records, or fails with PLSPM_E_STATE where that is None."""
     from plspm import _native
-    fetch = dict(rows=("plspm_bootstrap_fetch", nm.fetch), assess=("plspm_assess_fetch", nm.assess_fetch), micom=("plspm_micom_fetch", nm.micom_fetch),
+    fetch = dict(rows=("plspm_bootstrap_fetch", nm.fetch), assess=("plspm_assess_fetch", nm.assess_fetch), plsc=("plspm_plsc_fetch", nm.plsc_fetch),
+                 modelfit=("plspm_modelfit_fetch", nm.modelfit_fetch), micom=("plspm_micom_fetch", nm.micom_fetch),
                  jack=("plspm_jackknife_fetch", nm.jackknife_fetch))
     for kind, (name, call) in fetch.items():
         count = expected[kind]
