@@ -27,9 +27,9 @@
 #pragma once
 #include <type_traits>
 #include "wave_ops.h"
+#include "gram_route.h"      // the layout constants the host's plan shares: I8_SLACK_KB, I8_HIST_KB, I8_HIST_KB_BYTES, I8_HIST_KB_NIB
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-#define I8_SLACK_KB 6        // k-blocks of readable slack behind the counts and the digit planes (the DMA ring runs up to 5 k-steps ahead)
 #ifndef I8_DEFAULT_VAR
 #define I8_DEFAULT_VAR 3
 #endif
@@ -185,8 +185,6 @@ __global__ void __launch_bounds__(256) zs_build_kernel(const double* __restrict_
 // 100,000 takes ONE window again (one pass of Philox instead of two) and the histogram already is the output layout.  A Philox count
 // cannot reach 128, let alone carry into its neighbour at 256 (N draws over N >= 65,536 rows: P < 1e-200); explicit index lists CAN carry
 // any multiplicity, so they keep the 16-bit counters (where the overflow bit is reliable).
-#define I8_HIST_KB 1024
-#define I8_HIST_KB_BYTES 2048
 template <bool BYTES>
 __global__ void __launch_bounds__(1024) resample_i8_kernel(int N, int KB, int MT, int shape, const int* __restrict__ idx, uint64_t seed, int64_t rep0, uint4* __restrict__ Cd,
                                                            int* __restrict__ err) {
@@ -256,7 +254,6 @@ __global__ void __launch_bounds__(1024) resample_i8_kernel(int N, int KB, int MT
 // 15 or 16, so "sum of the counts == draws that fell into the window" holds exactly when no counter overflowed.  The read-out accumulates that sum beside
 // its stores; a workgroup whose sum is short draws the replicate again with 8-bit counters, two half-windows in the same LDS, and overwrites its pieces
 // (`force_slow`: that path for every replicate -- tests).  Same draws, same layout, same bits as resample_i8_kernel.
-#define I8_HIST_KB_NIB 4096
 __device__ __forceinline__ unsigned nib_spread16(unsigned t) {      // four nibbles (bits 0 .. 15) -> four bytes
     t = (t | (t << 8)) & 0x00ff00ffu;
     return (t | (t << 4)) & 0x0f0f0f0fu;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/plspm_hip_test.h"
+#include "gram_route.h"
 
 inline thread_local std::string g_create_error;
 
@@ -169,9 +170,9 @@ struct plspm_model {
     int last_i8_persist = 0;      // 1: ... as one persistent workgroup per CU (gram_i8pp_kernel)
     int last_i8_priv = 0;         // 1: the last int8 Gram launch was gram_i8p_kernel (private count fragments)
     int last_i8_rt = 0;           // count tiles (16 replicates each) per workgroup of the last int8 Gram launch: 16, 20 or 8
-    bool mix_valid = false, mix_wide = false; long mix_key[4] = {0, 0, 0, 0}; int mix_tall = 0, mix_short = 0;      // plspm_gram_i8.hip i8_mix_plan: the last tile-row cut
+    plspm::GramI8Cut mix_cut{};      // gram_route.h gram_i8_plan: the last tile-row cut and its key
     int last_i8_mt = 0;           // count tiles (padded) of the last int8 Gram launch: 16 x this many replicate slots went through the matrix pipe
-    int last_i8_short = 0;        // ... and, with 20, how many of its tile rows were short ones (16 count tiles: plspm_gram_i8.hip i8_mix_plan)
+    int last_i8_short = 0;        // ... and, with 20, how many of its tile rows were short ones (16 count tiles: gram_route.h i8_mix_plan)
     int last_solver = 0;          // the SolverRoute (solver_route.h) of the last metric or Scale.NUM / RAW bootstrap batch
     // grow-only pinned host staging for uploads / row downloads (two halves: copy-in of chunk k+1 overlaps the DMA of chunk k)
     void* h_pin = nullptr;

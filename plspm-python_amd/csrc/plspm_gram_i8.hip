@@ -2,6 +2,7 @@
 // + one exact integer product; kernels_gram_i8.h, kernels_gram_i8p.h), the cut of a batch into tile rows, plspm_bootstrap_prepare.
 #include "host_internal.h"
 
+#include <optional>
 #include "philox.h"
 #include "wave_ops.h"
 #include "kernels_gram_i8.h"
@@ -13,10 +14,7 @@ static constexpr size_t kZsBudget = (size_t)24 << 30;       // digit planes of o
 // Can a non-metric bootstrap with on-device draws take its stop-rule passes' row multiplicities from the int8 counts of the digit-plane Gram
 // (plspm_detail_bootstrap counts8_plan)?
 static int cu_count_of(plspm_model* m) {
-    if (!m->cu_count) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, m->device) == hipSuccess) m->cu_count = n;
-    }
+    if (!m->cu_count && hipDeviceGetAttribute(&m->cu_count, hipDeviceAttributeMultiprocessorCount, m->device) != hipSuccess) m->cu_count = 0;
     return m->cu_count;
 }
 
@@ -184,148 +182,151 @@ int prepare_zs(plspm_model* m, int floor) {
     return 0;
 }
 
-// Tile rows of the six-plane int8 Gram for `ct` count tiles (16 replicates each) x `ntx` pair tiles on `cus` CUs in 8 XCDs: `tall` rows of
-// 20 count tiles and -- `mix` -- `shrt` rows of 16 in one launch of gram_i8_kernel<6, 4, ., 16, 20>, or (return false) the 256-replicate
-// kernel.  Cost model = what the device does: an XCD's workgroups go in order to the CU that is free first (one workgroup per CU), so the
-// makespan of a cut is that of list scheduling its tall tiles first, then its short ones, per XCD.  Costs in count-tile rows: 20 per
-// tall tile, 16.6 per short one (the same DMA ring for 4/5 of the MFMAs), 16.35 per tile of the 256-replicate kernel (measured on 960 tiles
-// of each kind, tools/i8_mix_calib.py: 0.391 / 0.3245 / 0.3195 ms).  Deterministic in (ct, ntx, cus): every rank of a job cuts alike -- and the sums are exact
-// integers, so the cut never shows in a result.
-// (profiles/r04_i8_mix_calib.jsonl: 960 tiles of each height, 0.3628 / 0.2990 ms with six planes, 0.3435 / 0.2700 with seven)
-static constexpr double kI8pTall6 = 20.0, kI8pShort6 = 16.5, kI8pTall7 = 16.0, kI8pShort7 = 12.6;
-// Tile heights and their costs: `rt_tall` / `rt_short` count tiles per row, `ca` / `cb` what a tile of each costs (any common unit).  The
-// round-3 kernel: 20 / 16 at 20 / 16.6; gram_i8p_kernel: i8p_costs() below.
-static bool i8_mix_plan(long ct, long ntx, int cus, bool mix, int* tall, int* shrt, int rt_tall = 20, int rt_short = 16, double ca = 20.0, double cb = 16.6, bool vs_rt16 = true) {
-    const int per_xcd = std::max(1, cus / 8);
-    // (tiles of one kind are interchangeable: after the tall ones the CUs of an XCD sit on at most two load levels, and the short ones raise
-    //  the lowest level a whole group of CUs at a time -- a handful of steps per XCD instead of one per tile)
-    auto xcd_span = [&](long na, long nb2, double ca, double cb) {
-        const long c = per_xcd, q = na / c, r = na % c;
-        double lv[3] = {q * ca, (q + 1) * ca, 0.0};
-        long cnt[3] = {c - r, r, 0};
-        int n = r ? 2 : 1;
-        long left = nb2;
-        while (left > 0) {
-            int lo = 0;
-            for (int k = 1; k < n; ++k) if (lv[k] < lv[lo]) lo = k;
-            if (left >= cnt[lo]) { left -= cnt[lo]; lv[lo] += cb; }
-            else { lv[n] = lv[lo] + cb; cnt[n] = left; cnt[lo] -= left; left = 0; ++n; }
-            for (int k = 0; k < n; ++k)                      // merge equal levels (keeps n <= 2 before the last step)
-                for (int k2 = k + 1; k2 < n; ++k2)
-                    if (lv[k2] == lv[k]) { cnt[k] += cnt[k2]; lv[k2] = lv[n - 1]; cnt[k2] = cnt[n - 1]; --n; --k2; }
-        }
-        double worst = 0.0;
-        for (int k = 0; k < n; ++k) if (cnt[k] > 0) worst = std::max(worst, lv[k]);
-        return worst;
-    };
-    auto makespan = [&](long a, long b, double ca, double cb) {
-        double worst = 0.0;
-        const long ta = a * ntx, tb = b * ntx, pa = (ta + 7) / 8, pb = (tb + 7) / 8;
-        long seen_a = -1, seen_b = -1;
-        for (int x = 0; x < 8; ++x) {
-            const long na = std::max(0L, std::min(pa, ta - x * pa)), nb2 = std::max(0L, std::min(pb, tb - x * pb));
-            if (na == seen_a && nb2 == seen_b) continue;
-            seen_a = na; seen_b = nb2;
-            worst = std::max(worst, xcd_span(na, nb2, ca, cb));
-        }
-        return worst;
-    };
-    const long rows16 = (ct + 15) / 16, rows_s = (ct + rt_short - 1) / rt_short;
-    const double ref16 = vs_rt16 ? makespan(rows16, 0, 16.35, 0.0) : 1e300;
-    double best = 1e300;
-    long ba = 0, bb = 0;
-    for (long b = 0; b <= (mix ? std::min(rows_s, 48L) : 0L); ++b) {
-        const long a = std::max(0L, (ct - (long)rt_short * b + rt_tall - 1) / rt_tall);
-        if (a == 0 && b * rt_short < ct) continue;
-        const double t = makespan(a, b, ca, cb);
-        if (t < best - 1e-9) { best = t; ba = a; bb = b; }
-        if (a == 0) break;
-    }
-    *tall = (int)ba; *shrt = (int)bb;
-    return best <= ref16;
+// ------------------------------------------------------------------------------------------------ one chunk through the int8 Gram, phase by phase
+// gram_route.h decides the form of the launch (gram_i8_plan); the launchers below only carry it out.
+static GramI8Data gram_data_of(const plspm_model* m) { return GramI8Data{m->zs_S, m->zs_KB, m->zs_NT, m->zs_npg, m->zs_ind}; }
+static GramI8Options gram_options_of(const plspm_model* m) {
+    return GramI8Options{m->tune.i8_priv, m->tune.i8_persist, m->tune.i8_rt, m->tune.i8_short, m->tune.i8_cus, m->tune.i8_dma, m->tune.i8_nibbles, m->tune.i8_waves, m->tune.i8_shape, m->tune.i8_sched, m->tune.i8_variant};
 }
 
-// Resample nb replicates into dense int8 counts and multiply with the digit planes: the nb moment matrices land at `out`.
-// Explicit indices can carry a multiplicity above 127 (Philox draws of N >= 128 rows cannot, P < 1e-200): the host looks at the
-// flag before the product and reports *fallback so that the caller takes the fp64 Gram for this chunk.
-// out16 (round 5, may be null): where an all-indicator data set's products -- co-occurrence counts -- may leave as uint16 [nb][C][ld16], upper triangle, instead
-// of fp64 slots at `out`; *wrote16 tells whether this call did (the one-plane launch on 0/1 data; any other launch writes `out` as ever).
-int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, double* out, bool dense, bool* fallback,
-                const void** counts, int* counts_MT, unsigned short* out16, bool* wrote16) {
-    const uint64_t seed = call.seed;
-    const int64_t rep0 = call.rep_offset + b0;
-    const int32_t* const d_idx = call.d_idx ? call.d_idx + b0 * m->N : nullptr;
-    *fallback = false;
-    if (counts) *counts = nullptr;
-    if (wrote16) *wrote16 = false;
-    const int S = m->zs_S, KB = m->zs_KB, NT = m->zs_NT;
-    // workgroup tile of the product: 16 RT replicates x 32 pairs; narrow tiles (RT 12 / 8) only in the plain four-wave 16x16x64 launch
-    // Six planes leave registers for a taller workgroup tile: 320 replicates x 32 pairs (`RT` 20: 30 accumulator tiles per wave with eight
-    // waves) moves 9 % fewer LDS-DMA bytes and reads 12 % fewer fragments per MFMA than 256 x 32 -- 2.2 % on the step when the tile grid
-    // fills the machine equally well (5,000 replicates: 960 tiles = 3.75 rounds against 1,200 = 4.69, both five tile-units per CU).  "i8_rt"
-    // 0 (default) takes it when its rounds cost no more than those of the 256-replicate tile; the sums are exact either way.
-#ifdef PLSPM_I8_EXPERIMENTS
-    const bool var20 = m->tune.i8_variant < 0 || m->tune.i8_rt == 20;      // experiments build: the schedule variants exist for the 320-replicate tile too
-#else
-    const bool var20 = m->tune.i8_variant < 0;
-#endif
-    // private count fragments (kernels_gram_i8p.h, "i8_priv"): four waves, the counts straight into registers, only the digit blocks through LDS;
-    // six planes: tile rows of 320 (tall) / 256 (short) replicates, seven planes: 256 / 192
-#ifdef PLSPM_I8_EXPERIMENTS
-    const bool priv_var = true;                                             // schedule variants / ablation probes of the kernel (tools/i8p_bench.py)
-#else
-    const bool priv_var = m->tune.i8_variant < 0;
-#endif
-    const bool priv = m->tune.i8_priv != 0 && m->tune.i8_shape == 16 && m->tune.i8_sched == 0 && priv_var && (S == 6 || S == 7) && !m->zs_ind &&
-                      (m->tune.i8_rt == 0 || m->tune.i8_rt == (S == 6 ? 20 : 16));      // (an explicit other tile height names a round-3 kernel)
-    bool wide20 = !priv && m->tune.i8_shape == 16 && m->tune.i8_sched == 0 && var20 && S == 6 && !m->zs_ind && (m->tune.i8_rt == 20 || m->tune.i8_rt == 0);
-    const int RTtall = priv ? (S == 6 ? 20 : 16) : 20, RTshort = RTtall - 4;
-    // "i8_rt" 0: the cut of the replicates into tile rows is planned (i8_mix_plan below): rows of 320 and -- eight-wave kernel -- rows of 256
-    // in ONE launch, so that the last round of the machine is as full as the others (5,000 replicates x 60 pair tiles: 11 + 6 rows = 1,020
-    // tiles, every CU three tall + one short = 76 count-tile rows, against 16 rows of 320 = 960 tiles, 80 on three CUs of four)
-    int nty_tall = 0, nty_short = 0;
-    if ((wide20 || priv) && m->tune.i8_rt == 0 && m->tune.i8_short < 0) {
-        if (!cu_count_of(m)) return fail(m, PLSPM_E_STATE, "hipDeviceGetAttribute(multiprocessor count) failed");
-        // (the plan of the last shape is kept: a bootstrap calls with the same B again and again, and the search costs of the order of a millisecond)
-        // ("i8_cus": the cut for fewer CUs than the device has -- a launch that shares the chip with a collective's kernels)
-        const long key[4] = {(long)((nb + 15) / 16), (long)(m->zs_npg / 2), (long)std::max(8, m->tune.i8_cus > 0 ? std::min(m->tune.i8_cus, m->cu_count) : m->cu_count),
-                             priv ? 2L + S : (long)(m->tune.i8_waves == 8 && var20 && m->tune.i8_dma != 2)};
-        if (!(m->mix_valid && std::equal(key, key + 4, m->mix_key))) {
-            // (tile costs of gram_i8p_kernel, tools/i8_mix_calib.py on 960 tiles of each height: six planes 320 / 256 replicates, seven planes 256 / 192)
-            if (priv) m->mix_wide = i8_mix_plan(key[0], key[1], (int)key[2], true, &m->mix_tall, &m->mix_short, RTtall, RTshort, S == 6 ? kI8pTall6 : kI8pTall7, S == 6 ? kI8pShort6 : kI8pShort7, false);
-            else m->mix_wide = i8_mix_plan(key[0], key[1], (int)key[2], key[3] != 0, &m->mix_tall, &m->mix_short);
-            std::copy(key, key + 4, m->mix_key); m->mix_valid = true;
-        }
-        if (!priv) wide20 = m->mix_wide;
-        nty_tall = m->mix_tall; nty_short = m->mix_short;
-    } else if (wide20 || priv) {
-        // tall rows only, or -- "i8_short_rows" n >= 0 (test seam) -- n short rows behind as many tall ones as it takes
-        const long ct = (nb + 15) / 16;
-        if (m->tune.i8_short > 0 && (priv || (m->tune.i8_waves == 8 && var20 && m->tune.i8_dma != 2))) nty_short = (int)std::min<long>(m->tune.i8_short, (ct + RTshort - 1) / RTshort);
-        nty_tall = (int)std::max(0L, (ct - (long)RTshort * nty_short + RTtall - 1) / RTtall);
+// the one launch of a kernel with dynamic LDS
+template <class K, class... A>
+static int launch_lds(plspm_model* m, hipStream_t stream, K kfn, size_t lds_bytes, dim3 grid, dim3 block, A... args) {
+    if (const int rc = allow_lds(m, (const void*)kfn, lds_bytes)) return rc;
+    hipLaunchKernelGGL(kfn, grid, block, lds_bytes, stream, args...);
+    return 0;
+}
+
+// What the product's launch reads beside the plan: the counts, the destination table and stride of the moment matrices, the replicates whose results are stored
+struct GramLaunch { plspm_model* m; const GramI8Plan& p; const void* cd; const int* d_dst; double* out; long out_stride; long nrep; };
+// ... and the launch: every Gram kernel starts with the same eight arguments
+template <class K, class... A>
+static int launch_gram(const GramLaunch& g, K kfn, size_t lds_bytes, A... tail) {
+    return launch_lds(g.m, g.m->stream, kfn, lds_bytes, dim3((unsigned)g.p.grid), dim3((unsigned)g.p.block), (const uint4*)g.cd, (const uint4*)g.m->zs.p, g.m->zs_KB, g.p.MT, g.m->zs_NT,
+                      g.p.ntx, g.p.nty, g.d_dst, tail...);
+}
+// the round-3 kernel (kernels_gram_i8.h gram_i8_kernel).  No second destination table: a mirrored second store per element cost 0.08 ms per 5,000 replicates of the
+// metric benchmark -- the rows solver reads the triangle instead.  Categorical problems, whose solver wants the full square: Gram 1.40 -> 2.07 ms per 1,000 problems with
+// the mirrored stores against 0.4 ms saved in nmg_prepare's scatter -- not taken either.
+template <int S, int WM, int VAR, int SH = 16, int RT = 16, bool IND = false>
+static int launch_r3(const GramLaunch& g) {
+    using G = GramI8<S, WM, VAR, SH, RT>;
+    if (g.p.nty_short && !G::MIX) return fail(g.m, PLSPM_E_STATE, "int8 Gram: short tile rows planned for a kernel form without them");
+    return launch_gram(g, gram_i8_kernel<S, WM, VAR, SH, RT, IND>, G::LDS_BYTES, (const int*)nullptr, (const double*)g.m->pair_scale.p, g.m->zs_npair, (long)g.p.call.nb, g.out, g.out_stride,
+                       IND ? (g.p.to16 ? -1 : 0) : g.p.nty_short);
+}
+// the private-count kernel (kernels_gram_i8p.h gram_i8p_kernel): MTW count tiles per wave of a tall row
+template <int S, int VAR>
+static int launch_priv(const GramLaunch& g) {
+    constexpr int MTW = gram_i8p_tall(S) / 4;
+    const auto kfn = g.p.nty_short ? gram_i8p_kernel<S, MTW, VAR, true> : gram_i8p_kernel<S, MTW, VAR, false>;
+    return launch_gram(g, kfn, GramI8P<S, MTW, VAR>::LDS_BYTES, (const double*)g.m->pair_scale.p, g.m->zs_npair, g.nrep, g.out, g.out_stride, g.p.nty_short);
+}
+// ... and the same tiles on ONE persistent workgroup per CU (gram_i8pp_kernel: tiles from a per-XCD counter, the next tile's prologue in front of this tile's
+// epilogue; "i8_persist" 0: the tiled launch, kept as the A/B reference)
+template <int S>
+static int launch_persist(const GramLaunch& g) {
+    constexpr int MTW = gram_i8p_tall(S) / 4;
+    const auto kfn = g.p.nty_short ? gram_i8pp_kernel<S, MTW, 64, true> : gram_i8pp_kernel<S, MTW, 64, false>;
+    return launch_gram(g, kfn, GramI8P<S, MTW, 64>::LDS_BYTES + 64, (const double*)g.m->pair_scale.p, g.m->zs_npair, g.nrep, g.out, g.out_stride, g.p.nty_short, (GramI8PPCtl*)g.m->pp_ctl.p);
+}
+// the plane count as a template argument
+template <int WM, int VAR>
+static int launch_planes(const GramLaunch& g) {
+    switch (g.m->zs_S) {
+        case 1: return launch_r3<1, WM, VAR>(g); case 2: return launch_r3<2, WM, VAR>(g); case 3: return launch_r3<3, WM, VAR>(g); case 4: return launch_r3<4, WM, VAR>(g);
+        case 5: return launch_r3<5, WM, VAR>(g); case 6: return launch_r3<6, WM, VAR>(g); case 7: return launch_r3<7, WM, VAR>(g); default: return launch_r3<8, WM, VAR>(g);
     }
-    const bool rows2 = wide20 || priv;                 // launches whose grid holds tile rows of two heights
-    const bool narrow = wide20 || (!priv && m->tune.i8_rt == 8 && m->tune.i8_shape == 16 && m->tune.i8_waves == 4 && m->tune.i8_sched == 0 && m->tune.i8_variant < 0 && S == 7);
-    const int RTg = rows2 ? RTtall : narrow ? 8 : 16;
-    const bool ind = m->zs_ind && m->tune.i8_sched == 0 && m->tune.i8_variant < 0;
-    const int nty = rows2 ? nty_tall + nty_short : (int)((nb + 16 * RTg - 1) / (16 * RTg)), MT = rows2 ? nty_tall * RTtall + nty_short * RTshort : nty * RTg, ntx = ind ? m->zs_npg / 14 : m->zs_npg / 2;
-    // resample counts from an LDS histogram per (replicate, window of rows): 65,536 rows of 16-bit counters, or -- Philox draws of a data
-    // set that would need more than one such window -- 131,072 rows of 8-bit counters (kernels_gram_i8.h resample_i8_kernel)
-    // (round 5: 4-bit counters with an exact overflow test and an 8-bit second try, resample_i8_nib_kernel -- half the LDS again, three workgroups per CU at N = 100,000;
-    //  option "i8_nibbles" 0: the 8-bit histogram, 2: every replicate through the second try -- tests)
-    const bool hist_byte = KB > I8_HIST_KB && !d_idx;
-    const bool hist_nib = hist_byte && m->tune.i8_nibbles != 0 && m->tune.i8_shape == 16;
-    const int hist_kb = hist_nib ? I8_HIST_KB_NIB : (hist_byte ? I8_HIST_KB_BYTES : I8_HIST_KB);
-    const size_t hist_bytes = (size_t)std::min(KB, hist_kb) * (hist_nib ? 8 : (hist_byte ? 16 : 32)) * sizeof(unsigned);
-    const unsigned hist_windows = (unsigned)((KB + hist_kb - 1) / hist_kb);
-    int rc;
-    if ((rc = allow_lds(m, hist_nib ? (const void*)resample_i8_nib_kernel : (hist_byte ? (const void*)resample_i8_kernel<true> : (const void*)resample_i8_kernel<false>), hist_bytes))) return rc;
-    const auto resample_k = hist_byte ? resample_i8_kernel<true> : resample_i8_kernel<false>;
-    const int nib_slow = m->tune.i8_nibbles == 2 ? 1 : 0;
-    m->last_i8_nibbles = hist_nib ? 1 : 0;
-    // threads per workgroup: the histogram decides how many workgroups share a CU (160 KB of LDS); the VALU-bound Philox loop wants the
-    // CU's wave slots filled either way (N = 100,000: one 128 KB histogram per CU -- 256 threads left three quarters of the SIMD time idle)
-    const unsigned resample_threads = (unsigned)std::min(1024, std::max(256, 256 * (int)(8 / std::max<size_t>(1, (160 * 1024) / std::max<size_t>(1, hist_bytes)))));
+}
+template <int VAR>
+static int launch_priv_planes(const GramLaunch& g) { return g.m->zs_S == 6 ? launch_priv<6, VAR>(g) : launch_priv<7, VAR>(g); }
+
+// the forms of the round-3 kernel that exist with eight waves (WM 4) and with four (WM 2): one plane per pair group, the 320-replicate tile (its buffer form deals
+// 20 count blocks to four waves only), any plane count on the 256-replicate tile; VB: LDS-DMA as buffer_load ... lds, 32-bit offsets from per-workgroup descriptors
+template <int WM>
+static int launch_round3(const GramLaunch& g) {
+    constexpr int V0 = I8_DEFAULT_VAR, VB = I8_DEFAULT_VAR + 800;
+    switch (g.p.form) {
+        case GRAM_I8_IND: return g.p.dma_buffer ? launch_r3<7, WM, VB, 16, 16, true>(g) : launch_r3<7, WM, V0, 16, 16, true>(g);
+        case GRAM_I8_WIDE20: if constexpr (WM == 2) { if (g.p.dma_buffer) return launch_r3<6, WM, VB, 16, 20>(g); } return launch_r3<6, WM, V0, 16, 20>(g);
+        default: return g.p.dma_buffer ? launch_planes<WM, VB>(g) : launch_planes<WM, V0>(g);
+    }
+}
+
+// Release library: the eight-wave forms of the round-3 kernel and the private-count kernel only -- four waves measured equal, the 32x32x32 layout 16 % slower, the narrow
+// 128-replicate tile 2.6 % slower, the persistent stream-K launch neutral with a starvation hazard: DESIGN.md 7b.  `make experiments` builds them, the schedule variants
+// and the timing probe: launch_gram_experiment takes the launches that exist only there (its value: how the launch went) and declines the others (no value).
+#ifdef PLSPM_I8_EXPERIMENTS
+static constexpr bool kI8Experiments = true;
+template <int... VV, class F>
+static bool for_variant(int v, std::integer_sequence<int, VV...>, F&& f) { return ((v == VV && (f(std::integral_constant<int, VV>{}), true)) || ...); }
+template <int S, int WM>
+static int launch_sk(const GramLaunch& g) {       // persistent stream-K schedule (kernels_gram_i8.h gram_i8_sk_kernel)
+    return launch_gram(g, gram_i8_sk_kernel<S, WM>, GramI8<S, WM, I8_DEFAULT_VAR, 16>::LDS_BYTES, (const double*)g.m->pair_scale.p, g.m->zs_npair, (long)g.p.call.nb, g.out, g.out_stride,
+                       (i32x4*)g.m->sk_partial.p, (unsigned*)g.m->sk_flags.p, ++g.m->sk_epoch, (int*)g.m->err.p);
+}
+static std::optional<int> launch_gram_experiment(GramLaunch& g) {
+    plspm_model* m = g.m;
+    const GramI8Plan& p = g.p;
+    constexpr int V0 = I8_DEFAULT_VAR;
+    const bool four = p.waves == 4;
+    const int S = m->zs_S;
+    std::optional<int> rc;
+    // timing probe (results are garbage): "i8_nostore" 1 launches both forms of the private-count kernel with nrep = 0 -- every epilogue store (and the fp64
+    // recombination in front of it) is skipped; tools/persist_ab.py prices the epilogue of the tiled and of the persistent form with it
+    if (m->tune.i8_nostore && (p.form == GRAM_I8_PRIV || p.form == GRAM_I8_PERSIST)) g.nrep = 0;
+    switch (p.form) {
+        case GRAM_I8_PRIV:
+            // "i8_variant" v >= 0: the template's VAR itself -- bits 0-3 ablations, bit 4 digit blocks through staging registers, bits 5-6 the filler schedule
+            // (0 strides / 1 one per gap, DMAs last / 2 VMEM evenly spaced = the release kernel), bit 7 one barrier per two k-steps
+            for_variant(p.variant, std::integer_sequence<int, 0, 1, 2, 4, 8, 15, 16, 32, 128, 192, 64, 65, 66, 68, 72, 69, 77, 79>{}, [&](auto v) { rc = launch_priv_planes<decltype(v)::value>(g); });
+            return rc ? rc : fail(m, PLSPM_E_ARG, "i8_variant: not a built variant of the private-count kernel");
+        case GRAM_I8_SK:
+            return four ? (S == 5 ? launch_sk<5, 2>(g) : S == 6 ? launch_sk<6, 2>(g) : launch_sk<7, 2>(g)) : (S == 5 ? launch_sk<5, 4>(g) : S == 6 ? launch_sk<6, 4>(g) : launch_sk<7, 4>(g));
+        case GRAM_I8_PLAIN:
+            if (p.variant >= 0) {      // every schedule variant of the 7-plane kernel (tools/i8_bench.py --variants); a number that is not built: 33
+                auto go = [&](auto v) { constexpr int V = decltype(v)::value; rc = four ? launch_r3<7, 2, V>(g) : launch_r3<7, 4, V>(g); };
+                if (!for_variant(p.variant, std::integer_sequence<int, 0, 3, 6, 4, 803, 103, 203, 303, 403, 503, 703, 12, 18, 21, 24, 30>{}, go)) go(std::integral_constant<int, 33>{});
+                return rc;
+            }
+            return four ? launch_round3<2>(g) : rc;
+        case GRAM_I8_IND: return four ? launch_round3<2>(g) : rc;
+        case GRAM_I8_WIDE20:
+            if (p.variant < 0) return four ? launch_round3<2>(g) : rc;
+            for_variant(p.variant, std::integer_sequence<int, 0, 1, 3, 4, 5, 6, 7, 12, 13, 18, 21, 103, 203, 403, 703>{}, [&](auto v) { rc = launch_r3<6, 4, decltype(v)::value, 16, 20>(g); });
+            return rc ? rc : fail(m, PLSPM_E_ARG, "i8_variant: not built for the 320-replicate tile");
+        case GRAM_I8_NARROW: return launch_r3<7, 2, V0, 16, 8>(g);
+        case GRAM_I8_SHAPE32:          // v_mfma_i32_32x32x32_i8: four waves (64 replicates x 32 pairs x S planes each)
+            return S == 5 ? launch_r3<5, 2, V0, 32>(g) : S == 6 ? launch_r3<6, 2, V0, 32>(g) : S == 7 ? launch_r3<7, 2, V0, 32>(g) : launch_r3<8, 2, V0, 32>(g);
+        default: return rc;
+    }
+}
+#else
+static constexpr bool kI8Experiments = false;
+static std::optional<int> launch_gram_experiment(GramLaunch&) { return std::nullopt; }
+#endif
+
+// plan: the three inputs of gram_i8_plan from the handle and the call; the handle keeps the last tile-row cut
+static int gram_i8_plan_chunk(plspm_model* m, const BatchCall& call, int64_t nb, bool want16, GramI8Plan& p) {
+    if (!cu_count_of(m)) return fail(m, PLSPM_E_STATE, "hipDeviceGetAttribute(multiprocessor count) failed");
+    p = gram_i8_plan(gram_data_of(m), gram_options_of(m), GramI8Call{nb, call.d_idx != nullptr, brings_counts(call), want16, m->cu_count, kI8Experiments}, &m->mix_cut);
+    return 0;
+}
+
+static int launch_resample(plspm_model* m, const GramI8Plan& p, hipStream_t stream, const int32_t* d_idx, uint64_t seed, int64_t rep0, void* cd, void* err) {
+    const dim3 grid((unsigned)p.call.nb, p.hist_windows), block(p.hist_threads);
+    // (4-bit counters: option "i8_nibbles" 2 sends every replicate through the 8-bit second try -- tests)
+    if (p.hist == GRAM_I8_HIST4)
+        return launch_lds(m, stream, resample_i8_nib_kernel, p.hist_bytes, grid, block, (int)m->N, m->zs_KB, p.MT, seed, rep0, (uint4*)cd, (int*)err, m->tune.i8_nibbles == 2 ? 1 : 0);
+    const auto kfn = p.hist == GRAM_I8_HIST8 ? resample_i8_kernel<true> : resample_i8_kernel<false>;
+    return launch_lds(m, stream, kfn, p.hist_bytes, grid, block, (int)m->N, m->zs_KB, p.MT, m->tune.i8_shape, d_idx, seed, rep0, (uint4*)cd, (int*)err);
+}
+
+// counts: the chunk's dense int8 multiplicities into *cd_out (buffer `*slot_out` of the two that alternate under "resample_aux")
+static int gram_i8_counts(plspm_model* m, const BatchCall& call, const GramI8Plan& p, int64_t b0, int* slot_out, plspm_model::Buf** cd_out) {
+    const int64_t nb = p.call.nb, rep0 = call.rep_offset + b0;
+    const int32_t* const d_idx = call.d_idx ? call.d_idx + b0 * m->N : nullptr;
+    int rc = 0;
     if (m->tune.resample_aux && !m->aux) {
         int lo = 0, hi = 0;
         HIPCHK(m, hipDeviceGetStreamPriorityRange(&lo, &hi));                // (numerically: lowest priority first)
@@ -340,247 +341,111 @@ int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, d
     // counts of this chunk: the buffer the Gram before last read; grown only with both streams idle
     const int slot = m->aux ? (m->cd_slot ^= 1) : 0;
     plspm_model::Buf& cd = slot ? m->cd1 : m->cd;
-    const size_t cd_bytes = (size_t)MT * 16 * ((size_t)KB + I8_SLACK_KB) * 64;
-    if (cd_bytes > cd.cap) { if (m->aux) HIPCHK(m, hipStreamSynchronize(m->aux)); if ((rc = ensure(m, cd, cd_bytes))) return rc; m->cdfree_set[slot] = false; }
-    if (!d_idx && !brings_counts(call) && m->aux) {
-        // Philox draws: on the low-priority stream, as soon as the Gram that last read this buffer is done -- i.e. beside the Gram and the
-        // solver of the PREVIOUS call when the host runs ahead; this call's Gram waits for the counts by event
-        if (m->cdfree_set[slot]) HIPCHK(m, hipStreamWaitEvent(m->aux, m->ev_cdfree[slot], 0));
-        {
-            ProfScope ps(m, PLSPM_K_RESAMPLE, m->aux);
-            if (hist_nib) hipLaunchKernelGGL(resample_i8_nib_kernel, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->aux, (int)m->N, KB, MT, seed, rep0, (uint4*)cd.p, (int*)m->err2.p, nib_slow);
-            else
-            hipLaunchKernelGGL(resample_k, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->aux, (int)m->N, KB, MT, m->tune.i8_shape, d_idx, seed, rep0, (uint4*)cd.p, (int*)m->err2.p);
+    if (p.cd_bytes > cd.cap) { if (m->aux) HIPCHK(m, hipStreamSynchronize(m->aux)); if ((rc = ensure(m, cd, p.cd_bytes))) return rc; m->cdfree_set[slot] = false; }
+    *slot_out = slot; *cd_out = &cd;
+    // Philox draws: on the low-priority stream, as soon as the Gram that last read this buffer is done -- i.e. beside the Gram and the solver of the PREVIOUS call when
+    // the host runs ahead; this call's Gram waits for the counts by event.  Explicit index lists (test / parity seam) and the kinds that bring their own counts
+    // (rep_offset is 0, so rep0 is the chunk's first problem) arrive on the main stream: drawn there, and the host looks at the flag
+    const bool on_aux = !d_idx && !p.call.own_counts && m->aux;
+    const hipStream_t stream = on_aux ? m->aux : m->stream;
+    if (m->aux && m->cdfree_set[slot]) HIPCHK(m, hipStreamWaitEvent(stream, m->ev_cdfree[slot], 0));
+    {
+        ProfScope ps(m, PLSPM_K_RESAMPLE, stream);
+        switch (call.kind) {
+            case BatchCall::PERMUTATION: rc = launch_perm_counts(m, *call.perm, nb, rep0, p.MT, m->zs_KB, cd.p); break;           // 0/1 counts of random splits, plspm_permute.hip
+            case BatchCall::STRATIFIED: rc = launch_strat_counts(m, *call.strat, nb, rep0, p.MT, m->zs_KB, cd.p); break;          // ... its stratified bootstrap: draws inside each group
+            case BatchCall::CROSS_VALIDATION: rc = launch_cv_counts(m, *call.cv, nb, rep0, p.MT, m->zs_KB, cd.p); break;         // 0/1 counts of the training folds, plspm_cv.hip
+            case BatchCall::JACKKNIFE: rc = launch_jack_counts(m, *call.jack, nb, rep0, p.MT, m->zs_KB, cd.p); break;            // 0/1 counts of the rows a problem keeps, plspm_jackknife.hip
+            case BatchCall::PLAIN: rc = launch_resample(m, p, stream, d_idx, call.seed, rep0, cd.p, on_aux ? m->err2.p : m->err.p); break;
         }
+    }
+    if (rc) return rc;
+    if (on_aux) {
         HIPCHK(m, hipEventRecord(m->ev_counts[slot], m->aux));
         HIPCHK(m, hipStreamWaitEvent(m->stream, m->ev_counts[slot], 0));
-    } else {
-        // explicit index lists (test / parity seam) arrive on the main stream: drawn there, and the host looks at the flag
-        if (m->aux && m->cdfree_set[slot]) HIPCHK(m, hipStreamWaitEvent(m->stream, m->ev_cdfree[slot], 0));
-        ProfScope ps(m, PLSPM_K_RESAMPLE);
-        rc = 0;
-        switch (call.kind) {      // (the kinds that bring their own counts: rep_offset is 0, so rep0 is the chunk's first problem)
-            case BatchCall::PERMUTATION: rc = launch_perm_counts(m, *call.perm, nb, rep0, MT, KB, cd.p); break;           // 0/1 counts of random splits, plspm_permute.hip
-            case BatchCall::STRATIFIED: rc = launch_strat_counts(m, *call.strat, nb, rep0, MT, KB, cd.p); break;          // ... its stratified bootstrap: draws inside each group
-            case BatchCall::CROSS_VALIDATION: rc = launch_cv_counts(m, *call.cv, nb, rep0, MT, KB, cd.p); break;         // 0/1 counts of the training folds, plspm_cv.hip
-            case BatchCall::JACKKNIFE: rc = launch_jack_counts(m, *call.jack, nb, rep0, MT, KB, cd.p); break;            // 0/1 counts of the rows a problem keeps, plspm_jackknife.hip
-            case BatchCall::PLAIN:
-                if (hist_nib) hipLaunchKernelGGL(resample_i8_nib_kernel, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->stream, (int)m->N, KB, MT, seed, rep0, (uint4*)cd.p, (int*)m->err.p, nib_slow);
-                else hipLaunchKernelGGL(resample_k, dim3((unsigned)nb, hist_windows), dim3(resample_threads), hist_bytes, m->stream, (int)m->N, KB, MT, m->tune.i8_shape, d_idx, seed, rep0, (uint4*)cd.p, (int*)m->err.p);
-                break;
-        }
-        if (rc) return rc;
     }
-    if (d_idx) {
-        int* h_err = (int*)m->h_flag + 9;
-        HIPCHK(m, hipMemcpyAsync(h_err, m->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    return 0;
+}
+
+// overflow check: explicit indices can carry a multiplicity above 127 (Philox draws of N >= 128 rows cannot, P < 1e-200): the host looks at the flag before the
+// product and reports *fallback so that the caller takes the fp64 Gram for this chunk
+static int gram_i8_overflow(plspm_model* m, bool* fallback) {
+    int* h_err = (int*)m->h_flag + 9;
+    HIPCHK(m, hipMemcpyAsync(h_err, m->err.p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    if (*h_err & 2) {
+        const int keep = *h_err & 1;
+        HIPCHK(m, hipMemcpyAsync(m->err.p, &keep, sizeof(int), hipMemcpyHostToDevice, m->stream));
         HIPCHK(m, hipStreamSynchronize(m->stream));
-        if (*h_err & 2) {
-            const int keep = *h_err & 1;
-            HIPCHK(m, hipMemcpyAsync(m->err.p, &keep, sizeof(int), hipMemcpyHostToDevice, m->stream));
-            HIPCHK(m, hipStreamSynchronize(m->stream));
-            *fallback = true;
-            return 0;
-        }
+        *fallback = true;
     }
-    if (counts && m->tune.i8_shape == 16) { *counts = cd.p; *counts_MT = MT; }       // (16-row pieces: what nm_conv_dense_kernel<.., CNT8> reads)
-    const int total = ntx * nty, per = rows2 ? (ntx * nty_tall + 7) / 8 + (ntx * nty_short + 7) / 8 : (total + 7) / 8;      // workgroups per XCD
-    // packed: the tile-packed slots the LDS solver / impute kernel read; dense: [(Pg+1) x cov_ld(Pg)] row-major, upper triangle (rows solver)
-    const bool to16 = out16 && wrote16 && ind && m->tune.i8_shape == 16;
-    const int* d_dst = (const int*)m->pair_tab.p + (to16 ? 6 : (dense ? 4 : 3)) * (size_t)m->zs_npair;
-    // (a mirrored second store per element cost 0.08 ms per 5,000 replicates of the metric benchmark: the rows solver reads the triangle
-    //  instead.  Categorical problems, whose solver wants the full square: Gram 1.40 -> 2.07 ms per 1,000 problems with the mirrored
-    //  stores against 0.4 ms saved in nmg_prepare's scatter -- not taken either)
-    const int* d_dst2 = nullptr;
-    const long out_stride = to16 ? (long)(m->Pg + 1) * ((m->Pg + 1 + 7) & ~7) : (dense ? cov_doubles(m->Pg) : packed_size(m->T));
-    if (to16) { out = reinterpret_cast<double*>(out16); *wrote16 = true; }
-    // persistent stream-K schedule (kernels_gram_i8.h gram_i8_sk_kernel): one workgroup per CU, whole CUs per XCD
-    const bool sk = m->tune.i8_sched == 1 && m->tune.i8_shape == 16 && m->tune.i8_variant < 0 && S >= 5 && S <= 7;      // (S = 8 spills in the persistent kernel)
-    int sk_grid = 0;
-    if (sk) {
-        if (!cu_count_of(m)) return fail(m, PLSPM_E_STATE, "hipDeviceGetAttribute(multiprocessor count) failed");
-        sk_grid = std::max(8, (m->cu_count / 8) * 8);
-        const size_t slot_bytes = (size_t)32 * S * 1024;                    // 16 count tiles x 2 pair groups x S planes x 1 KB of int32 per workgroup
-        if ((size_t)sk_grid * slot_bytes > m->sk_partial.cap && (rc = ensure(m, m->sk_partial, (size_t)sk_grid * slot_bytes))) return rc;
+    return 0;
+}
+
+// note: what get_option("last_i8_*") reports of the launch
+static void gram_i8_note(plspm_model* m, const GramI8Plan& p) {
+    m->last_i8_nibbles = p.hist == GRAM_I8_HIST4 ? 1 : 0; m->last_i8_dma = p.dma_buffer ? 2 : 1;
+    m->last_i8_rt = p.rt_tall; m->last_i8_short = p.nty_short; m->last_i8_mt = p.MT;
+    m->last_i8_priv = (p.form == GRAM_I8_PRIV || p.form == GRAM_I8_PERSIST) ? 1 : 0; m->last_i8_persist = p.form == GRAM_I8_PERSIST ? 1 : 0;
+}
+
+// gram: the product of the counts at `cd` with the digit planes.  packed: the tile-packed slots the LDS solver / impute kernel read; dense: [(Pg+1) x cov_ld(Pg)]
+// row-major, upper triangle (rows solver); to16: uint16 [nb][C][ld16], upper triangle, at out16
+static int gram_i8_product(plspm_model* m, const GramI8Plan& p, const void* cd, double* out, bool dense, unsigned short* out16, bool* wrote16) {
+    const int* d_dst = (const int*)m->pair_tab.p + (p.to16 ? 6 : (dense ? 4 : 3)) * (size_t)m->zs_npair;
+    const long out_stride = p.to16 ? (long)(m->Pg + 1) * ((m->Pg + 1 + 7) & ~7) : (dense ? cov_doubles(m->Pg) : packed_size(m->T));
+    if (p.to16) { out = reinterpret_cast<double*>(out16); *wrote16 = true; }
+    int rc;
+    if (p.form == GRAM_I8_SK) {
+        const size_t bytes = (size_t)p.sk_grid * 32 * m->zs_S * 1024;      // per workgroup: 16 count tiles x 2 pair groups x S planes x 1 KB of int32
+        if (bytes > m->sk_partial.cap && (rc = ensure(m, m->sk_partial, bytes))) return rc;
         if (!m->sk_flags.p) {
             if ((rc = ensure(m, m->sk_flags, (size_t)2048 * 8 * sizeof(unsigned)))) return rc;
             HIPCHK(m, hipMemsetAsync(m->sk_flags.p, 0, (size_t)2048 * 8 * sizeof(unsigned), m->stream));
             m->sk_epoch = 0;
         }
     }
-    // the buffer form of the LDS-DMA needs every byte offset of a workgroup's walk (incl. the slack k-blocks) below 4 GiB
-    const bool dma_fits = (uint64_t)(KB + I8_SLACK_KB) * (uint64_t)std::max(MT, NT) * 1024ull < (1ull << 32);
-    const bool dma_buffer = !priv && m->tune.i8_dma != 1 && dma_fits && m->tune.i8_shape == 16 && !sk && (!narrow || (wide20 && m->tune.i8_waves == 4)) && m->tune.i8_variant < 0;
-    m->last_i8_dma = dma_buffer ? 2 : 1;
-    m->last_i8_rt = RTg;
-    m->last_i8_short = rows2 ? nty_short : 0;
-    m->last_i8_priv = priv ? 1 : 0;
-    m->last_i8_mt = MT;
+    if (p.form == GRAM_I8_PERSIST && !m->pp_ctl.p) {
+        if ((rc = ensure(m, m->pp_ctl, sizeof(GramI8PPCtl)))) return rc;
+        HIPCHK(m, hipMemsetAsync(m->pp_ctl.p, 0, sizeof(GramI8PPCtl), m->stream));      // (once: the kernel leaves the counters at zero)
+    }
     ProfScope ps(m, PLSPM_K_GRAM);
-    // (release library: the eight-wave forms of the round-3 kernel only -- four waves measured equal, the 32x32x32 layout 16 % slower, the narrow
-    //  128-replicate tile 2.6 % slower, the persistent stream-K launch neutral with a starvation hazard: DESIGN.md 7b; `make experiments` builds them)
-#ifdef PLSPM_I8_EXPERIMENTS
-#define I8_FOUR_WAVES (m->tune.i8_waves == 4)
-#else
-#define I8_FOUR_WAVES false
-#endif
-#define GI8SK(SS, WW)                                                                                                                        \
-    {                                                                                                                                        \
-        const size_t lds_bytes = GramI8<SS, WW, I8_DEFAULT_VAR, 16>::LDS_BYTES;                                                              \
-        if ((rc = allow_lds(m, (const void*)gram_i8_sk_kernel<SS, WW>, lds_bytes))) return rc;                                               \
-        hipLaunchKernelGGL((gram_i8_sk_kernel<SS, WW>), dim3((unsigned)sk_grid), dim3(128 * WW), lds_bytes, m->stream, (const uint4*)cd.p,    \
-                           (const uint4*)m->zs.p, KB, MT, NT, ntx, nty, d_dst, (const double*)m->pair_scale.p, m->zs_npair, (long)nb, out, out_stride, \
-                           (i32x4*)m->sk_partial.p, (unsigned*)m->sk_flags.p, ++m->sk_epoch, (int*)m->err.p);                                \
-    }
-#define GI8P(SS, MM, VV)                                                                                                                     \
-    {                                                                                                                                        \
-        const size_t lds_bytes = GramI8P<SS, MM, VV>::LDS_BYTES;                                                                             \
-        auto kfn = nty_short ? gram_i8p_kernel<SS, MM, VV, true> : gram_i8p_kernel<SS, MM, VV, false>;                                       \
-        if ((rc = allow_lds(m, (const void*)kfn, lds_bytes))) return rc;                                                                     \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)(8 * per)), dim3(256), lds_bytes, m->stream, (const uint4*)cd.p,                               \
-                           (const uint4*)m->zs.p, KB, MT, NT, ntx, nty, d_dst, (const double*)m->pair_scale.p, m->zs_npair, nb_launch, out, out_stride, nty_short); \
-    }
-    // round 5: the same tiles on ONE persistent workgroup per CU (gram_i8pp_kernel: tiles from a per-XCD counter, the next tile's prologue in front
-    // of this tile's epilogue; "i8_persist" 0: the tiled launch of round 4, kept as the A/B reference)
-#define GI8PP(SS, MM)                                                                                                                        \
-    {                                                                                                                                        \
-        const size_t lds_bytes = GramI8P<SS, MM, 64>::LDS_BYTES + 64;                                                                        \
-        auto kfn = nty_short ? gram_i8pp_kernel<SS, MM, 64, true> : gram_i8pp_kernel<SS, MM, 64, false>;                                     \
-        if ((rc = allow_lds(m, (const void*)kfn, lds_bytes))) return rc;                                                                     \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)(8 * pp_wgs)), dim3(256), lds_bytes, m->stream, (const uint4*)cd.p,                            \
-                           (const uint4*)m->zs.p, KB, MT, NT, ntx, nty, d_dst, (const double*)m->pair_scale.p, m->zs_npair, nb_launch, out, out_stride, nty_short, \
-                           (GramI8PPCtl*)m->pp_ctl.p);                                                                                       \
-    }
-#ifdef PLSPM_I8_EXPERIMENTS
-    // timing probe (results are garbage): "i8_nostore" 1 launches both forms of the private-count kernel with nrep = 0 -- every epilogue store (and the
-    // fp64 recombination in front of it) is skipped; tools/persist_ab.py prices the epilogue of the tiled and of the persistent form with it
-    const long nb_launch = m->tune.i8_nostore ? 0 : (long)nb;
-#else
-    const long nb_launch = (long)nb;
-#endif
-    const bool persist = priv && m->tune.i8_persist != 0 && (m->tune.i8_variant < 0 || m->tune.i8_variant == 64);
-    int pp_wgs = 0;
-    if (persist) {
-        if (!cu_count_of(m)) return fail(m, PLSPM_E_STATE, "hipDeviceGetAttribute(multiprocessor count) failed");
-        const int cus = std::max(8, m->tune.i8_cus > 0 ? std::min(m->tune.i8_cus, m->cu_count) : m->cu_count);
-        pp_wgs = std::max(1, std::min(cus / 8, per));                       // one workgroup per CU of an XCD, never more than the XCD has tiles
-        if (!m->pp_ctl.p) {
-            if ((rc = ensure(m, m->pp_ctl, sizeof(GramI8PPCtl)))) return rc;
-            HIPCHK(m, hipMemsetAsync(m->pp_ctl.p, 0, sizeof(GramI8PPCtl), m->stream));      // (once: the kernel leaves the counters at zero)
-        }
-    }
-    m->last_i8_persist = persist ? 1 : 0;
-    if (persist) {
-        if (S == 6) GI8PP(6, 5) else GI8PP(7, 4)
-    } else
-    if (priv) {
-#define GI8PX(VV) case VV: if (S == 6) GI8P(6, 5, VV) else GI8P(7, 4, VV) break;
-#ifdef PLSPM_I8_EXPERIMENTS
-        // "i8_variant" v >= 0: the template's VAR itself -- bits 0-3 ablations, bit 4 digit blocks through staging registers, bits 5-6 the filler
-        // schedule (0 strides / 1 one per gap, DMAs last / 2 VMEM evenly spaced = the release kernel), bit 7 one barrier per two k-steps
-        switch (m->tune.i8_variant < 0 ? 64 : m->tune.i8_variant) {
-            GI8PX(0) GI8PX(1) GI8PX(2) GI8PX(4) GI8PX(8) GI8PX(15) GI8PX(16) GI8PX(32) GI8PX(128) GI8PX(192)
-            GI8PX(64) GI8PX(65) GI8PX(66) GI8PX(68) GI8PX(72) GI8PX(69) GI8PX(77) GI8PX(79)
-            default: return fail(m, PLSPM_E_ARG, "i8_variant: not a built variant of the private-count kernel"); }
-#else
-        switch (64) { GI8PX(64) }
-#endif
-    } else
-#ifdef PLSPM_I8_EXPERIMENTS
-    if (sk) {
-        if (m->tune.i8_waves == 4) { switch (S) { case 5: GI8SK(5, 2) break; case 6: GI8SK(6, 2) break; default: GI8SK(7, 2) break; } }
-        else { switch (S) { case 5: GI8SK(5, 4) break; case 6: GI8SK(6, 4) break; default: GI8SK(7, 4) break; } }
-    } else
-#endif
-#define GI8VS(SS, WW, VV, SH)                                                                                                                \
-    {                                                                                                                                        \
-        const size_t lds_bytes = GramI8<SS, WW, VV, SH>::LDS_BYTES;                                                                          \
-        if ((rc = allow_lds(m, (const void*)gram_i8_kernel<SS, WW, VV, SH>, lds_bytes))) return rc;                                          \
-        hipLaunchKernelGGL((gram_i8_kernel<SS, WW, VV, SH>), dim3((unsigned)(8 * per)), dim3(128 * WW), lds_bytes, m->stream, (const uint4*)cd.p, \
-                           (const uint4*)m->zs.p, KB, MT, NT, ntx, nty, d_dst, d_dst2, (const double*)m->pair_scale.p, m->zs_npair, (long)nb, out, out_stride, 0); \
-    }
-#define GI8V(SS, WW, VV) GI8VS(SS, WW, VV, 16)
-#define GI8(SS, WW) GI8V(SS, WW, I8_DEFAULT_VAR)
-#define GI8B(SS, WW) GI8V(SS, WW, I8_DEFAULT_VAR + 800)
-#ifdef PLSPM_I8_EXPERIMENTS       // every schedule variant of the 7-plane kernel (tools/i8_bench.py --variants; not in the release library)
-#define GI8X(WW) switch (m->tune.i8_variant) { case 0: GI8V(7, WW, 0) break; case 3: GI8V(7, WW, 3) break; case 6: GI8V(7, WW, 6) break; case 4: GI8V(7, WW, 4) break; \
-        case 803: GI8V(7, WW, 803) break; case 103: GI8V(7, WW, 103) break; case 203: GI8V(7, WW, 203) break; case 303: GI8V(7, WW, 303) break; case 403: GI8V(7, WW, 403) break; case 503: GI8V(7, WW, 503) break; case 703: GI8V(7, WW, 703) break; \
-        case 12: GI8V(7, WW, 12) break; case 18: GI8V(7, WW, 18) break; case 21: GI8V(7, WW, 21) break; case 24: GI8V(7, WW, 24) break; case 30: GI8V(7, WW, 30) break; default: GI8V(7, WW, 33) break; }
-    if (S == 7 && m->tune.i8_variant >= 0) { if (m->tune.i8_waves == 4) GI8X(2) else GI8X(4) } else
-#endif
-#define GI8RT(RR)                                                                                                                            \
-    {                                                                                                                                        \
-        const size_t lds_bytes = GramI8<7, 2, I8_DEFAULT_VAR, 16, RR>::LDS_BYTES;                                                            \
-        if ((rc = allow_lds(m, (const void*)gram_i8_kernel<7, 2, I8_DEFAULT_VAR, 16, RR>, lds_bytes))) return rc;                             \
-        hipLaunchKernelGGL((gram_i8_kernel<7, 2, I8_DEFAULT_VAR, 16, RR>), dim3((unsigned)(8 * per)), dim3(256), lds_bytes, m->stream, (const uint4*)cd.p, \
-                           (const uint4*)m->zs.p, KB, MT, NT, ntx, nty, d_dst, d_dst2, (const double*)m->pair_scale.p, m->zs_npair, (long)nb, out, out_stride, 0); \
-    }
-#define GI8IND(WW, VV)                                                                                                                       \
-    {                                                                                                                                        \
-        const size_t lds_bytes = GramI8<7, WW, VV, 16, 16>::LDS_BYTES;                                                                       \
-        if ((rc = allow_lds(m, (const void*)gram_i8_kernel<7, WW, VV, 16, 16, true>, lds_bytes))) return rc;                                 \
-        hipLaunchKernelGGL((gram_i8_kernel<7, WW, VV, 16, 16, true>), dim3((unsigned)(8 * per)), dim3(128 * WW), lds_bytes, m->stream, (const uint4*)cd.p, \
-                           (const uint4*)m->zs.p, KB, MT, NT, ntx, nty, d_dst, d_dst2, (const double*)m->pair_scale.p, m->zs_npair, (long)nb, out, out_stride, to16 ? -1 : 0); \
-    }
-    if (ind) {                   // one plane per pair group, seven groups per wave
-#ifdef PLSPM_I8_EXPERIMENTS
-        if (m->tune.i8_waves == 4) { if (dma_buffer) GI8IND(2, I8_DEFAULT_VAR + 800) else GI8IND(2, I8_DEFAULT_VAR) } else
-#endif
-        if (dma_buffer) GI8IND(4, I8_DEFAULT_VAR + 800) else GI8IND(4, I8_DEFAULT_VAR)
-    } else
-#define GI8RT20(WW, VV)                                                                                                                      \
-    {                                                                                                                                        \
-        const size_t lds_bytes = GramI8<6, WW, VV, 16, 20>::LDS_BYTES;                                                                       \
-        if ((rc = allow_lds(m, (const void*)gram_i8_kernel<6, WW, VV, 16, 20>, lds_bytes))) return rc;                                       \
-        if (nty_short && !GramI8<6, WW, VV, 16, 20>::MIX) return fail(m, PLSPM_E_STATE, "int8 Gram: short tile rows planned for a kernel form without them"); \
-        hipLaunchKernelGGL((gram_i8_kernel<6, WW, VV, 16, 20>), dim3((unsigned)(8 * per)), dim3(128 * WW), lds_bytes, m->stream, (const uint4*)cd.p, \
-                           (const uint4*)m->zs.p, KB, MT, NT, ntx, nty, d_dst, d_dst2, (const double*)m->pair_scale.p, m->zs_npair, (long)nb, out, out_stride, nty_short); \
-    }
-#ifdef PLSPM_I8_EXPERIMENTS
-#define GI8X20(VV) case VV: GI8RT20(4, VV) break;
-    if (wide20 && m->tune.i8_variant >= 0 && m->tune.i8_waves == 8) {
-        switch (m->tune.i8_variant) { GI8X20(0) GI8X20(1) GI8X20(3) GI8X20(4) GI8X20(5) GI8X20(6) GI8X20(7) GI8X20(12) GI8X20(13) GI8X20(18) GI8X20(21) GI8X20(103) GI8X20(203) GI8X20(403) GI8X20(703) default: return fail(m, PLSPM_E_ARG, "i8_variant: not built for the 320-replicate tile"); }
-    } else
-#endif
-#ifdef PLSPM_I8_EXPERIMENTS
-    if (wide20 && m->tune.i8_waves == 4) { if (dma_buffer) GI8RT20(2, I8_DEFAULT_VAR + 800) else GI8RT20(2, I8_DEFAULT_VAR) } else
-    if (narrow && !wide20) GI8RT(8) else
-    if (m->tune.i8_shape == 32 && S >= 5) {    // v_mfma_i32_32x32x32_i8: four waves (64 replicates x 32 pairs x S planes each)
-        switch (S) { case 5: GI8VS(5, 2, I8_DEFAULT_VAR, 32) break; case 6: GI8VS(6, 2, I8_DEFAULT_VAR, 32) break; case 7: GI8VS(7, 2, I8_DEFAULT_VAR, 32) break; default: GI8VS(8, 2, I8_DEFAULT_VAR, 32) break; }
-    } else
-    if (m->tune.i8_waves == 4) {
-        if (dma_buffer) { switch (S) { case 1: GI8B(1, 2) break; case 2: GI8B(2, 2) break; case 3: GI8B(3, 2) break; case 4: GI8B(4, 2) break; case 5: GI8B(5, 2) break; case 6: GI8B(6, 2) break; case 7: GI8B(7, 2) break; default: GI8B(8, 2) break; } }
-        else { switch (S) { case 1: GI8(1, 2) break; case 2: GI8(2, 2) break; case 3: GI8(3, 2) break; case 4: GI8(4, 2) break; case 5: GI8(5, 2) break; case 6: GI8(6, 2) break; case 7: GI8(7, 2) break; default: GI8(8, 2) break; } }
-    } else
-#endif
-    if (wide20) GI8RT20(4, I8_DEFAULT_VAR) else
-    if (dma_buffer) {            // LDS-DMA as buffer_load ... lds (32-bit offsets from per-workgroup descriptors)
-        switch (S) { case 1: GI8B(1, 4) break; case 2: GI8B(2, 4) break; case 3: GI8B(3, 4) break; case 4: GI8B(4, 4) break; case 5: GI8B(5, 4) break; case 6: GI8B(6, 4) break; case 7: GI8B(7, 4) break; default: GI8B(8, 4) break; }
-    } else {
-        switch (S) { case 1: GI8(1, 4) break; case 2: GI8(2, 4) break; case 3: GI8(3, 4) break; case 4: GI8(4, 4) break; case 5: GI8(5, 4) break; case 6: GI8(6, 4) break; case 7: GI8(7, 4) break; default: GI8(8, 4) break; }
-    }
-#undef GI8V
-#undef GI8VS
-#undef GI8
-#undef GI8B
-    HIPCHK(m, hipGetLastError());
+    GramLaunch g{m, p, cd, d_dst, out, out_stride, (long)p.call.nb};
+    if (const std::optional<int> took = launch_gram_experiment(g)) rc = *took;
+    else if (p.form == GRAM_I8_PERSIST) rc = m->zs_S == 6 ? launch_persist<6>(g) : launch_persist<7>(g);
+    else rc = p.form == GRAM_I8_PRIV ? launch_priv_planes<64>(g) : launch_round3<4>(g);
+    if (!rc) HIPCHK(m, hipGetLastError());
+    return rc;
+}
+
+// Resample nb replicates into dense int8 counts and multiply with the digit planes: the nb moment matrices land at `out`.
+// *fallback: an explicit index list carried a multiplicity above 127 -- nothing was multiplied, the caller takes the fp64 Gram for this chunk.
+// out16 (may be null): where an all-indicator data set's products -- co-occurrence counts -- may leave as uint16 [nb][C][ld16], upper triangle, instead
+// of fp64 slots at `out`; *wrote16 tells whether this call did (the one-plane launch on 0/1 data; any other launch writes `out` as ever).
+int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, double* out, bool dense, bool* fallback,
+                const void** counts, int* counts_MT, unsigned short* out16, bool* wrote16) {
+    *fallback = false; if (counts) *counts = nullptr; if (wrote16) *wrote16 = false;
+    GramI8Plan p;
+    plspm_model::Buf* cd = nullptr;
+    int rc, slot = 0;
+    if ((rc = gram_i8_plan_chunk(m, call, nb, out16 && wrote16, p))) return rc;
+    if ((rc = gram_i8_counts(m, call, p, b0, &slot, &cd))) return rc;
+    if (call.d_idx && ((rc = gram_i8_overflow(m, fallback)) || *fallback)) return rc;
+    if (counts && m->tune.i8_shape == 16) { *counts = cd->p; *counts_MT = p.MT; }       // (16-row pieces: what nm_conv_dense_kernel<.., CNT8> reads)
+    gram_i8_note(m, p);
+    if ((rc = gram_i8_product(m, p, cd->p, out, dense, out16, wrote16))) return rc;
     if (m->aux) { HIPCHK(m, hipEventRecord(m->ev_cdfree[slot], m->stream)); m->cdfree_set[slot] = true; }     // the counts buffer is free once this Gram has run
     return 0;
 }
 
 int64_t plspm_detail_round_units_peek(const plspm_model* m) {
     if (!m || !m->d_Xa || m->nonmetric || m->n_ind || !m->zs_valid || !m->cu_count || choose_gram_path(m, (int64_t)1 << 20) != 2) return 64;
-    const int S = m->zs_S;
-    if ((S != 6 && S != 7) || m->zs_ind || m->tune.i8_priv == 0) return 64;
-    const int cus = std::max(8, m->tune.i8_cus > 0 ? std::min(m->tune.i8_cus, m->cu_count) : m->cu_count);
-    const int ntx = std::max(1, m->zs_npg / 2), tall = (S == 6 ? 20 : 16) * 16;
-    return (int64_t)std::max(1, cus / ntx) * tall;
+    return gram_i8_round_units(gram_data_of(m), gram_options_of(m), m->cu_count, kI8Experiments);
 }
 
 int64_t plspm_detail_round_units(plspm_model* m) {
     if (!m || !m->d_Xa || m->nonmetric || m->n_ind || choose_gram_path(m, (int64_t)1 << 20) != 2) return 64;
-    if (hipSetDevice(m->device) != hipSuccess || prepare_zs(m)) return 64;            // (the plane count decides the tile height; built once per upload anyway)
-    if (!cu_count_of(m)) return 64;
+    if (hipSetDevice(m->device) != hipSuccess || prepare_zs(m) || !cu_count_of(m)) return 64;            // (the plane count decides the tile height; built once per upload anyway)
     return plspm_detail_round_units_peek(m);
 }
 
@@ -601,10 +466,7 @@ int plspm_bootstrap_prepare(plspm_model_t* m) {
 
 int plspm_gram_tile_plan(int64_t count_tiles, int64_t pair_tiles, int32_t cus, int32_t mix, int32_t* tall, int32_t* shrt) {
     if (!tall || !shrt || count_tiles < 1 || pair_tiles < 1 || cus < 1 || count_tiles > ((int64_t)1 << 26) || pair_tiles > ((int64_t)1 << 20)) return PLSPM_E_ARG;
-    int a = 0, b = 0;
-    const bool wide = i8_mix_plan((long)count_tiles, (long)pair_tiles, std::max(8, (int)cus), mix != 0, &a, &b);
-    *tall = a; *shrt = b;
-    return wide ? 1 : 0;
+    return i8_mix_plan((long)count_tiles, (long)pair_tiles, std::max(8, (int)cus), mix != 0, tall, shrt) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include "../../plspm-python_amd/csrc/solver_wave16.h"
 #include "../../plspm-python_amd/csrc/solver_route.h"
 #include "../../plspm-python_amd/csrc/nm_route.h"
+#include "../../plspm-python_amd/csrc/gram_route.h"
 
 using namespace plspm;
 
@@ -607,6 +608,20 @@ void hostemu_nm_plan(const long* sh, const long* call, const int* o, long* out) 
     const NmPlan p = nm_plan(s, NmCall{call[0], call[1] != 0, call[2] != 0, call[3] != 0, call[4] != 0}, NmOptions{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11], o[12]});
     const long v[] = {p.error, p.dense, p.dense_whole, p.use_codes, p.use_mfma, p.flag_from_list, p.k16, p.wave_step, p.bound_ok, p.sub_pass, p.one_launch, p.step_lmax, p.step_cmax, p.step_cpl,
                       p.num_one, p.direct16, p.KS, p.tpc, p.nparts, p.nsub, p.cat_fast};
+    for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
+}
+
+// The launch form of one chunk of the int8 Gram (csrc/gram_route.h gram_i8_plan).  data: S, KB, NT, npg, zs_ind; opts in the order of GramI8Options; call: nb, explicit_idx,
+// own_counts, want16, cu_count, experiments.  out: form, waves, variant, dma_buffer, rt_tall, rt_short, nty_tall, nty_short, nty, ntx, MT, per_xcd, grid, block, pp_wgs, sk_grid,
+// hist, hist_bytes, hist_windows, hist_threads, cd_bytes, to16, then whether the private-count kernel takes the data set and the round units of the sub-batch plan
+void hostemu_gram_i8_plan(const int* data, const int* o, const long* call, long* out) {
+    const GramI8Data d{data[0], data[1], data[2], data[3], data[4] != 0};
+    const GramI8Options opt{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10]};
+    const GramI8Call c{call[0], call[1] != 0, call[2] != 0, call[3] != 0, (int)call[4], call[5] != 0};
+    const GramI8Plan p = gram_i8_plan(d, opt, c);
+    const long v[] = {p.form, p.waves, p.variant, p.dma_buffer, p.rt_tall, p.rt_short, p.nty_tall, p.nty_short, p.nty, p.ntx, p.MT, p.per_xcd, p.grid, p.block, p.pp_wgs, p.sk_grid,
+                      p.hist, (long)p.hist_bytes, (long)p.hist_windows, (long)p.hist_threads, (long)p.cd_bytes, p.to16,
+                      gram_i8_priv_takes(d, opt, c.experiments), (long)gram_i8_round_units(d, opt, c.cu_count, c.experiments)};
     for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
 }
 

@@ -10,6 +10,7 @@ import pytest
 
 import plspm_oracle as orc
 from helpers import assert_close, case_modes, load, satisfaction_oracle_inputs
+from helpers_gram_route import PERSIST as GRAM_PERSIST, PRIV as GRAM_PRIV, data as gram_data, load_emu, plan as gram_plan
 from test_gpu_parity import ATOL, RTOL, native_model
 
 pytestmark = pytest.mark.gpu
@@ -833,4 +834,37 @@ def test_tile_row_cut_planned_for_fewer_cus_gives_the_same_records():
         nm.set_option("i8_cus", 3)
     nm.set_option("i8_cus", 0)
     assert (nm.get_option("last_i8_short"), nm.get_option("last_i8_mt")) != (None, None)
+    nm.close()
+
+
+def test_the_launch_is_the_one_the_cpu_plan_describes():
+    """csrc/gram_route.h gram_i8_plan through the emulation build against what the launcher notes on the handle: 300 rows x 12 MVs (three pair tiles, six k-blocks),
+    the tile rows cut for 64 CUs ("i8_cus": the cut then does not depend on the device), six and seven planes, the private-count and the round-3 kernel, batches
+    of one tile row, just past 256 and 320 replicates and past two rows.  The moment matrices are bit for bit those of the 256-replicate round-3 kernel."""
+    C = orc.chain_C(3)
+    X, blocks = orc.synth(300, C, 4, seed=11)
+    model = orc.Model(blocks, C, "AAA", "centroid", True)
+    nm = native_model(model)
+    nm.upload(X)
+    nm.set_option("i8_cus", 64)
+    exp = 1 if experiments_build(nm) else 0
+    emu = load_emu()
+    for slices in (6, 7):
+        nm.set_option("i8_slices", slices)
+        for B in (1, 257, 321, 641):
+            nm.set_option("i8_priv", 0); nm.set_option("i8_rt", 16)
+            M16 = nm.bootstrap_moments(B, seed=2)
+            assert nm.get_option("last_gram_path") == 2 and nm.get_option("last_i8_rt") == 16 and nm.get_option("last_i8_priv") == 0
+            nm.set_option("i8_rt", 0)
+            for priv in (0, 1):
+                nm.set_option("i8_priv", priv)
+                nm.bootstrap_device(B, seed=2)
+                S = nm.get_option("last_i8_slices")
+                assert S == slices
+                want = gram_plan(emu, gram_data(S, 300, 12), B, cu_count=256, experiments=exp, cus=64, priv=priv)      # (any device of 64 CUs and more cuts alike)
+                got = {k: nm.get_option("last_i8_" + k) for k in ("rt", "short", "mt", "priv", "persist", "dma")}
+                assert got == dict(rt=want["rt_tall"], short=want["nty_short"], mt=want["MT"], priv=int(want["form"] in (GRAM_PRIV, GRAM_PERSIST)),
+                                   persist=int(want["form"] == GRAM_PERSIST), dma=2 if want["dma_buffer"] else 1), (slices, B, priv)
+                assert got["priv"] == priv
+                assert np.array_equal(nm.bootstrap_moments(B, seed=2), M16), (slices, B, priv)
     nm.close()
