@@ -1,7 +1,7 @@
 // host_internal.h -- what the translation units of libplspm_hip.so share on the HOST side (round 4: the former one-file host is split by
 // concern so that the units compile side by side): plspm_hip.hip (allocator, handles, options, upload, staging), plspm_fit.hip (fp64 Gram,
 // solvers, non-metric iteration, single fit, operator seam), plspm_gram_i8.hip (digit planes + the int8 Gram of bootstrap batches),
-// plspm_bootstrap.hip (bootstrap driver, record download, summaries), plspm_derived.hip (the records derived from a plain bootstrap's replicates),
+// plspm_bootstrap.hip (batch driver phase by phase as batch_route.h plans it, record download, summaries), plspm_derived.hip (the records derived from a plain bootstrap's replicates),
 // plspm_group.cpp (multi-GPU groups).  Every device kernel lives in
 // exactly one unit's headers; the functions below are the seams between them.  Nothing here is part of the C-ABI (include/plspm_hip.h).
 #pragma once
@@ -32,6 +32,7 @@
 #include "solver_wave16.h"
 #include "solver_route.h"
 #include "nm_route.h"
+#include "batch_route.h"
 
 using namespace plspm;
 
@@ -60,11 +61,28 @@ inline NmOptions nm_options(const plspm_model* m) {
     const plspm_model::Tune& t = m->tune;
     return {t.conv_pass, t.conv_gy, t.nm_k16, t.nm_wave, t.nm_codes, t.nm_mfma, t.nm_subset, t.nm_cat_one, t.nm_cpl, t.nm_c10, t.nm_fast_lds, t.nm_wave16, t.nm_direct16};
 }
-// lists: the call has (row,count) lists for these problems (the dense pass reads their uint16 histograms when the bootstrap built them)
-inline NmPlan plan_nonmetric(const plspm_model* m, long nproblems, bool counts8, bool lists, bool counts16_ready, bool finish) {
-    const plspm_model* src = m->stage1 ? m->stage1 : m;
-    return nm_plan(plan_shape(m), NmCall{nproblems, counts8, lists && src->dcnt_ready, counts16_ready, finish}, nm_options(m));
+inline NmPlan plan_nonmetric(const plspm_model* m, const NmCall& call) { return nm_plan(plan_shape(m), call, nm_options(m)); }
+// batch_route.h: the shape, the options and the kind of a batch call on this handle, and its predicates about the int8 route asked of a handle
+inline BatchShape batch_shape(const plspm_model* m) {
+    BatchShape s{};
+    s.N = m->N; s.P = m->P; s.Pg = m->Pg; s.T = m->T; s.L = m->L; s.R = plspm_row_stride(m); s.n_ind = m->n_ind;
+    s.nonmetric = m->nonmetric != 0; s.has_stage1 = m->stage1 != nullptr; s.has_stage2 = m->stage2 != nullptr; s.micom_on = m->micom_on; s.plain_metric = plain_metric(m);
+    s.route = route_shape(m);
+    if (m->nonmetric) { s.nm = plan_shape(m); if (m->stage2) s.nm2 = plan_shape(m->stage2); }
+    return s;
 }
+inline BatchOptions batch_options(const plspm_model* m) {
+    const plspm_model::Tune& t = m->tune;
+    return {t.gram_path, t.i8_min_batch, t.i8_slices, t.nm_counts8, t.resample_aux, t.i8_shape, t.i8_sched, t.solver_wave, t.solver_quad, t.solver_rows, t.boot_pass,
+            nm_options(m), m->stage2 ? nm_options(m->stage2) : NmOptions{}, m->aux != nullptr};
+}
+inline BatchKind batch_kind(const BatchCall& c) {
+    return {c.B, brings_counts(c), pairs_problems(c), c.kind == BatchCall::STRATIFIED, c.d_idx != nullptr, c.moments_out != nullptr, c.rows_out != nullptr};
+}
+inline bool gram_i8_closed(const plspm_model* m, int slices) { return gram_i8_closed(batch_shape(m), batch_options(m), slices); }
+inline int choose_gram_path(const plspm_model* m, int64_t B) { return choose_gram_path(batch_shape(m), batch_options(m), B); }
+inline bool gram_counts_route_open(const plspm_model* m) { return gram_counts_route_open(batch_shape(m), batch_options(m)); }
+inline bool may_raise(const plspm_model* m, const BatchCall& c) { return batch_may_raise(m->N, m->tune.i8_sched, c.d_idx != nullptr, c.kind == BatchCall::STRATIFIED); }
 inline size_t nm_state_doubles_of(const plspm_model* m) { return (size_t)nm_state_doubles_of(plan_shape(m)); }
 // Dynamic LDS beyond the 64 KiB default needs an explicit opt-in per kernel.
 inline int allow_lds(plspm_model* m, const void* fn, size_t bytes) {
@@ -118,28 +136,26 @@ int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const Solver
 // Scale.NUM / RAW non-metric bootstrap batches as ONE solver launch (round 6; solver_wave16.h NM; nm_route.h num_one says whether the model has such a kernel)
 // (dense moment matrices at m->gram; maps / steps as kernels_solver.h solver_nmwave_kernel takes them; force + live: the replay of `nb` listed replicates)
 int launch_nm_wave_solver(plspm_model* m, long nb, const SolverOut& so, double* maps, long maps_stride, int* steps, const int* force, const int* live);
-// plspm_nonmetric.hip: the non-metric solve of pl.call.nproblems problems as `pl` (plan_nonmetric) routes it.  Mp: their packed scatter matrices (unless the
-// Gram wrote the uint16 counts); ent / nent: their (row,count) lists or null; cd8 / cd8_MT: the int8 row multiplicities the digit-plane Gram consumed or null
-int run_nonmetric(plspm_model* m, const NmPlan& pl, const double* Mp, long mp_stride, const SolverOut& so_in, const int2* ent, const int* nent, long ent_stride, int threads,
-                  const void* cd8 = nullptr, int cd8_MT = 0);
+// What a non-metric solve reads of its problems.  Mp: their packed scatter matrices (unless the Gram wrote the uint16 counts); ent / nent: their (row,count) lists
+// or null; cd8 / cd8_MT: the int8 row multiplicities the digit-plane Gram consumed or null; threads per problem of the launch-by-launch kernels
+struct NmInputs { const double* Mp; long mp_stride; const int2* ent; const int* nent; long ent_stride; const void* cd8; int cd8_MT; int threads; };
+// plspm_nonmetric.hip: the non-metric solve of pl.call.nproblems problems as `pl` (plan_nonmetric) routes it
+int run_nonmetric(plspm_model* m, const NmPlan& pl, const NmInputs& in, const SolverOut& so_in);
 // second-stage moments of a HOC pair by congruence with the first stage's score maps: m->gram (stage 1) -> m2->gram
 int run_hoc_moments(plspm_model* m, plspm_model* m2, long nb);
 
 // ---- plspm_gram_i8.hip
-static inline int i8_kblocks(long N) { return (int)((N + 127) / 128) * 2; }      // k-blocks of 64 rows, an even number
-static inline long i8_pairs(const plspm_model* m) { const long C = m->Pg + 1; return C * (C + 1) / 2; }
-bool nm_counts8_possible(const plspm_model* m);
-bool gram_i8_closed(const plspm_model* m, int slices);      // the int8 route is closed for the resident data at this plane count (stage 1, N, non-metric window, plane budget)
-int choose_gram_path(const plspm_model* m, int64_t B);      // 1 fp64 MFMA on (row,count) lists, 2 int8 digit planes: the "gram_path" / "i8_min_batch" policy where the route is open
-// the route of the calls that bring their own counts (model.h brings_counts): open at the seven planes at least such a call cuts, whatever the policy says
-inline bool gram_counts_route_open(const plspm_model* m) { return !gram_i8_closed(m, std::max(m->tune.i8_slices, 7)); }
+static inline long i8_pairs(const plspm_model* m) { return i8_pair_count(m->Pg); }
 int prepare_zs_stats(plspm_model* m);
 int prepare_zs(plspm_model* m, int floor = 0);      // floor: at least this many digit planes (0: the handle's own choice)
-// problems [b0, b0 + nb) of `call`: their counts (drawn, or the kind's own count kernel) and the product
-int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, double* out, bool dense, bool* fallback, const void** counts = nullptr,
-                int* counts_MT = nullptr, unsigned short* out16 = nullptr, bool* wrote16 = nullptr);
-// plspm_nonmetric.hip: a Scale.NUM / RAW batch as one solver launch + verification (pl.num_one)
-int run_nonmetric_wave(plspm_model* m, const NmPlan& pl, const SolverOut& so, const void* cd8, int cd8_MT);
+// What one pass through the int8 Gram leaves.  fallback: an explicit index list carried a multiplicity above 127 -- nothing was multiplied, the caller takes the
+// fp64 Gram for these problems; counts / counts_MT: the dense int8 multiplicities in 16-row pieces (null: another layout); wrote16: the products left as uint16 at out16
+struct GramI8Result { bool fallback; const void* counts; int counts_MT; bool wrote16; };
+// problems [b0, b0 + nb) of `call`: their counts (drawn, or the kind's own count kernel) and the product.  out16 (may be null): where an all-indicator data set's
+// products -- co-occurrence counts -- may leave as uint16 [nb][C][ld16], upper triangle, instead of fp64 slots at `out`
+int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, double* out, bool dense, unsigned short* out16, GramI8Result* res);
+// plspm_nonmetric.hip: a Scale.NUM / RAW batch as one solver launch + verification (pl.num_one); reads in.cd8 / in.cd8_MT and the dense moment matrices at m->gram
+int run_nonmetric_wave(plspm_model* m, const NmPlan& pl, const NmInputs& in, const SolverOut& so);
 
 // ---- plspm_derived.hip: the chain assessment -> PLSc -> model fit behind a plain metric bootstrap's solver, as the batch driver sees it
 // Once per call: *depth = the deepest stage that applies (0 none, 1 assessment, 2 + PLSc, 3 + model fit) -- a plain call on a plain metric handle, no moments seam,

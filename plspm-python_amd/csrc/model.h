@@ -91,7 +91,7 @@ struct plspm_model {
     // non-metric data with missing values (solver_nmx.h): K incomplete rows live in side tables, their rows of Xa are zero
     Buf dcnt, ctable, Xt;        // dense stop-rule pass of the non-metric bootstrap: uint16 histograms, coefficient table, tiled copy of Xa
     long dcnt_stride = 0;
-    bool Xt_valid = false, dcnt_ready = false;
+    bool Xt_valid = false;
     int nmx_K = 0, nmx_raw = 0;
     double *d_Xk = nullptr, *d_Mk = nullptr;
     int* d_rowid = nullptr;
@@ -103,7 +103,7 @@ struct plspm_model {
     Buf scores;
     Buf xa, up_raw, up_ci, up_partial;   // resident matrix (d_Xa points into `xa` while data are uploaded) and the upload staging
     int64_t rows_B = 0;           // number of valid records in `rows` (0: none)
-    bool err_clean = false;       // the device error word is zero and no call since could have raised it (plspm_detail_bootstrap)
+    bool err_clean = false;       // the device error word is zero and no call since could have raised it (plspm_detail_bootstrap; batch_route.h batch_may_raise)
     // launch-geometry options (plspm_model_set_option); validated there, never read from the environment
     struct Tune { int wide_nw = 4, fit_chunks = 0, conv_pass = 0, conv_gy = 0, nm_threads = 0, solver_threads = 128, scores_tile = 0, gram_lds_kb = 0;
                   int gram_path = 0, i8_slices = 0, i8_min_batch = 1, i8_waves = 8, i8_rt = 0, i8_short = -1, i8_cus = 0, upload_direct = 0, i8_dma = 0, i8_variant = -1, solver_rows = 1, solver_wave = 1, solver_quad = 1, nm_counts8 = 1, nm_fast_lds = 1, nm_k16 = 1, nm_codes = 1, i8_ind = 1, i8_shape = 16, resample_aux = 0, i8_sched = 0, i8_priv = 1, boot_chunks = 0, boot_ratio = 60, boot_align = 0, i8_persist = 0, i8_min_slices = 0, i8_nostore = 0, nm_wave = 1, nm_live = 1, nm_mfma = 1, nm_direct16 = 1, i8_nibbles = 1, nm_wave16 = 1, nm_verify_rows = 0, nm_bound_shift = 0, wide_ring = 4, nm_subset = 4, nm_cat_one = 1, nm_cpl = 0, nm_c10 = 1, nm_vlong = 1, strat_rows = 0, boot_pass = 0; } tune;
@@ -218,10 +218,6 @@ struct BatchCall {
 // The kind brings its own counts: the int8 route whatever "gram_path" / "i8_min_batch" say (its caller asked gram_counts_route_open), seven digit planes at
 // least (their counts add up to less than N: plspm_gram_i8.hip prepare_zs), and no draws on the aux stream.
 inline bool brings_counts(const BatchCall& c) { return c.kind != BatchCall::PLAIN; }
-// The call's launches may raise the device error word (index out of range / multiplicity above 127 / stream-K wait expired): explicit indices, draws inside a
-// group, the persistent Gram -- and data sets of fewer than 128 rows, which cannot exceed a multiplicity of 127 but take the short-N launch forms that share
-// the word with the index check.  A Philox call on the tiled launch neither raises nor needs to clear it.
-inline bool may_raise(const plspm_model* m, const BatchCall& c) { return c.d_idx != nullptr || c.kind == BatchCall::STRATIFIED || m->tune.i8_sched != 0 || m->N < 128; }
 // The call leaves the handle's records alone (the jackknife: buffers of its own, so that the bootstrap whose BCa intervals ask for it keeps its records).
 inline bool keeps_records(const BatchCall& c) { return c.kind == BatchCall::JACKKNIFE; }
 // Problems 2p / 2p + 1 are the two sides of split p of the resident rows: what a MICOM record compares.

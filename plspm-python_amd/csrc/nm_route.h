@@ -1,5 +1,5 @@
 // nm_route.h -- which route a non-metric batch takes (stop-rule pass, step kernel, one-launch forms) and the sizes that follow from it: a pure function of
-// the model's shape, the call's inputs and the options, read by the planner (plspm_bootstrap.hip, plspm_gram_i8.hip) and the runner (plspm_nonmetric.hip).
+// the model's shape, the call's inputs and the options, read by the planner (batch_route.h) and the runner (plspm_nonmetric.hip).
 // Free of the HIP runtime: the CPU tests compile it (tests/hostemu).
 #pragma once
 #include <stddef.h>

@@ -1,5 +1,5 @@
-// plspm_bootstrap.hip -- host side, part 4: the bootstrap driver (resample -> Gram -> solver per chunk of replicates, and behind a plain metric chunk's
-// solver the derived records of plspm_derived.hip), its C-ABI entry points, the record download, the device summaries and the confidence intervals,
+// plspm_bootstrap.hip -- host side, part 4: the batch driver of every call kind, phase by phase as batch_route.h plans it (check -> plan -> digit planes -> reserve ->
+// void records, begin the derived chain -> error word -> per pass: Gram, lists, one of four solver arrangements -> commit), its C-ABI entry points, the record download, the device summaries and the confidence intervals,
 // and what the entry points of every kind of side records share (host_internal.h SideRecords).
 // Kernels: kernels_resample.h, kernels_summary.h, kernels_intervals.h.
 #include "host_internal.h"
@@ -17,180 +17,197 @@ __global__ void __launch_bounds__(256) moments_unpack_kernel(const double* __res
     for (int e = threadIdx.x; e < C * C; e += 256) { const int p = e / C, q = e - p * C; o[e] = g[packed_index(T, p, q)]; }
 }
 
-int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
-    const int64_t B = call.B, rep_offset = call.rep_offset;
-    const int32_t* const d_idx = call.d_idx;
-    call.stop_taken = false;
-    if (!m || B < 1 || rep_offset < 0 || B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: bad arguments (1 <= B <= 2^30, rep_offset >= 0)");
+// ------------------------------------------------------------------------------------------------ the batch driver, phase by phase
+// batch_route.h decides -- batch_plan once per call, batch_chunk once per pass; the phases below only carry it out.
+// What the phases of one call share
+struct BatchRun {
+    plspm_model* m;
+    BatchCall& call;
+    BatchShape shape; BatchOptions opts; BatchPlan plan;
+    int R;                                               // record pitch
+    int chain; int64_t chain_base;                       // the derived records (plspm_derived.hip): depth of the chain, position of the call's first record
+    double* rows_out; plspm_model::Buf *status_buf, *iters_buf;
+};
+// ... and of one pass: problems [b0, b0 + nb), what the int8 Gram left, what batch_chunk made of it, where the solver writes
+struct BatchPass { int64_t b0, nb; GramI8Result gram; BatchChunk k; SolverOut so; };
+
+static int batch_check(plspm_model* m, const BatchCall& call) {
+    if (!m || call.B < 1 || call.rep_offset < 0 || call.B > ((int64_t)1 << 30)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: bad arguments (1 <= B <= 2^30, rep_offset >= 0)");
     if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_bootstrap: no data uploaded");
     // (run_gram_i8 hands a count kernel rep_offset + b0 as its first problem)
-    if (brings_counts(call) && (rep_offset || d_idx)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: a call that brings its own counts takes no offset or indices");
-    const long N = m->N;
-    const bool lds_hist = (N <= 65535);        // N * 2 bytes of LDS histogram (16-bit counters, <= 128 KB); beyond that a global scratch slice per replicate
-    HIPCHK(m, hipSetDevice(m->device));
-    const int R = plspm_row_stride(m);
-    const long psize = packed_size(m->T);
-    const long ent_stride = ((N + 3) & ~3L) + 4;
-    // replicates per pass: bound the (row,count) + Gram scratch to ~2 GiB
-    // non-metric solvers: dense uint16 histograms for the dense stop-rule pass (LDS-histogram path only)
-    // non-metric models on the int8 route with Philox draws (round 3): the dense stop-rule pass reads its row multiplicities from the int8
-    // counts the Gram consumed -- no second resample kernel, no (row,count) lists, no uint16 histograms (set_option "nm_counts8" 0: the
-    // round-2 path, kept for A/B and for the cases below)
-    // (a two-group permutation call, plspm_permute.hip, always takes the int8 route: its caller checked that the route is open; so do a cross-validation call, plspm_cv.hip, and a jackknife call, plspm_jackknife.hip)
-    const int gpath = brings_counts(call) ? 2 : choose_gram_path(m, B);
-    // (explicit index lists of at most 65,535 rows keep the round-3 arrangement -- uint16 histograms beside the lists they need anyway; beyond
-    //  one window the int8 counts are the only dense multiplicities there are)
-    const bool counts8_plan = gpath == 2 && (!d_idx || !lds_hist) && nm_counts8_possible(m);
-    const bool want_dcnt = m->nonmetric && lds_hist && !counts8_plan;
-    const long dcnt_stride = ((N + 15) & ~15L);
-    m->last_gram_path = gpath;
-    // metric models on the int8 Gram: a solver on dense moment matrices (solver_route.h) unless the model is outside every dense solver's class
-    const SolverRoute route = metric_batch_route(route_shape(m), m->tune.solver_wave, m->tune.solver_quad, m->tune.solver_rows);
-    const bool rows_solver = gpath == 2 && route != ROUTE_LDS && !m->n_ind && !m->nonmetric && !call.moments_out;
-    // The non-metric route of the call as its batches will take it (nm_route.h): planned here with the int8 counts the call expects, and again per chunk with
-    // what the chunk has (a chunk whose explicit indices made the int8 Gram fall back to the fp64 one has none) -- the same function, so buffers and launches agree.
-    // round 6: Scale.NUM / RAW batches on the int8 route as one solver launch on dense moment matrices + a verification pass (plspm_nonmetric.hip
-    // run_nonmetric_wave) -- needs the int8 counts the Gram consumed (explicit index lists of at most 65,535 rows keep the per-iteration launches and their
-    // uint16 histograms)
-    const NmPlan nm = m->nonmetric ? plan_nonmetric(m, B, counts8_plan, false, false, true) : NmPlan{};
-    const bool nm_wave = gpath == 2 && !call.moments_out && nm.num_one;
-    // the fp64 Gram walks (row,count) lists (explicit indices may fall back to it); so do the stop-rule passes of the non-metric solvers
-    const bool need_lists = gpath == 1 || d_idx != nullptr || (m->nonmetric && !counts8_plan);
-    const size_t kpad = (size_t)i8_kblocks(N) * 64;
-    // (the global-scratch histogram serves the (row,count) lists only: the int8 route on Philox draws never builds them)
-    const bool need_ghist = !lds_hist && need_lists;
-    const bool cat_one = nm.one_launch;
-    const size_t per_rep = (need_lists ? (size_t)ent_stride * sizeof(int2) : 0) + (size_t)std::max<long>(psize, cov_doubles(m->Pg)) * sizeof(double) + (need_ghist ? (size_t)N * sizeof(unsigned) : 0) +
-                           (want_dcnt ? (size_t)dcnt_stride * sizeof(unsigned short) : 0) + (gpath == 2 ? kpad : 0) +
-                           ((nm_wave || cat_one) ? nm.verify_bytes_per_rep : 0);      // (the one-launch forms: score maps + verification tables)
-    // (the one-launch categorical batch lasts as long as its slowest replicate -- the ones that never converge run max_iter + 1 steps in one wave --, so cutting a call
-    //  into passes multiplies that tail: 16 GiB of the 288 for it instead of 2)
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(((cat_one ? 16ull : 2ull) << 30) / per_rep)));
-    if (gpath == 2 && chunk < B) chunk = std::max<int64_t>(256, chunk & ~(int64_t)255);      // whole 256-replicate tiles per pass
-    if (m->tune.boot_pass > 0 && m->tune.boot_pass < chunk) chunk = m->tune.boot_pass;        // test seam "boot_pass" (a multiple of 256): later passes at test sizes
-    m->last_boot_passes = (int)((B + chunk - 1) / chunk);
+    if (brings_counts(call) && (call.rep_offset || call.d_idx)) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: a call that brings its own counts takes no offset or indices");
+    return 0;
+}
+
+// reserve: per pass, chunk x the bytes per problem that entered the plan's per_rep; per call, the records
+static int batch_reserve(BatchRun& r) {
+    plspm_model* m = r.m;
+    const BatchPlan& p = r.plan;
+    const size_t chunk = (size_t)p.chunk, B = (size_t)r.call.B;
     int rc;
-    if (gpath == 2) {
-        if ((rc = prepare_zs(m, brings_counts(call) ? 7 : 0))) return rc;      // (a permutation / stratified / cross-validation / jackknife call: seven planes at least, plspm_permute.hip, plspm_cv.hip, plspm_jackknife.hip)
-    }
-    if (need_lists) {
-        if ((rc = ensure(m, m->ent, (size_t)chunk * ent_stride * sizeof(int2)))) return rc;
-        if ((rc = ensure(m, m->nent, (size_t)chunk * sizeof(int)))) return rc;
-    }
-    if ((rc = ensure(m, m->gram, (size_t)chunk * std::max<long>(psize, (rows_solver || nm_wave) ? cov_doubles(m->Pg) : 0) * sizeof(double)))) return rc;
-    // Whatever replaces the handle's bootstrap records voids the cross-validation, assessment and MICOM records that went with them (or whose status / iteration
-    // buffers are reused); a jackknife call writes into buffers of its own, and whatever the handle holds survives it.
-    void_records(m, call);
-    // The derived records of a plain bootstrap (plspm_derived.hip): a call of its own (rows_out null) sizes their buffers and starts at record 0; a sub-batch of
-    // plspm_bootstrap() writes from its position in that call (call.chain_off; the buffers are plspm_bootstrap's).
-    int chain = 0;
-    if ((rc = derived_begin(m, call, &chain))) return rc;
-    const int64_t chain_base = call.rows_out ? call.chain_off : 0;
-    // MICOM records (plspm_micom_enable) of a permutation call: one per pair of problems, from position 0 of the call.
-    const bool micom = m->micom_on && pairs_problems(call) && plain_metric(m) && !call.rows_out;
-    const int MS = 3 * m->L + 2;
-    if (micom && (rc = ensure(m, m->micom_rows, (size_t)(B / 2) * MS * sizeof(double)))) return rc;
-    if (!call.rows_out && (rc = ensure(m, m->rows, (size_t)B * R * sizeof(double)))) return rc;
-    double* const rows_out = call.rows_out ? call.rows_out : (double*)m->rows.p;
-    plspm_model::Buf& status_buf = call.status_out ? *call.status_out : m->status;
-    plspm_model::Buf& iters_buf = call.iters_out ? *call.iters_out : m->iters;
-    if ((rc = ensure(m, status_buf, (size_t)B * sizeof(int)))) return rc;
-    if ((rc = ensure(m, iters_buf, (size_t)B * sizeof(int)))) return rc;
+    if ((rc = ensure(m, m->ent, chunk * p.ent_bytes)) || (rc = ensure(m, m->nent, chunk * p.nent_bytes)) || (rc = ensure(m, m->gram, chunk * p.gram_bytes)) ||
+        (rc = ensure(m, m->ghist, chunk * p.ghist_bytes)) || (rc = ensure(m, m->dcnt, chunk * p.dcnt_bytes)))
+        return rc;
+    if (p.want16 && (rc = ensure(m, m->gK16, chunk * p.gk16_bytes + 64))) return rc;
+    m->dcnt_stride = p.dcnt_stride;
+    if (p.micom && (rc = ensure(m, m->micom_rows, (B / 2) * p.micom_stride * sizeof(double)))) return rc;
+    if (!r.call.rows_out && (rc = ensure(m, m->rows, B * r.R * sizeof(double)))) return rc;
+    r.rows_out = r.call.rows_out ? r.call.rows_out : (double*)m->rows.p;
+    r.status_buf = r.call.status_out ? r.call.status_out : &m->status;
+    r.iters_buf = r.call.iters_out ? r.call.iters_out : &m->iters;
+    if ((rc = ensure(m, *r.status_buf, B * sizeof(int))) || (rc = ensure(m, *r.iters_buf, B * sizeof(int)))) return rc;
     const void* err_before = m->err.p;
     if ((rc = ensure(m, m->err, sizeof(int)))) return rc;
     if (m->err.p != err_before) m->err_clean = false;
-    if (need_ghist && (rc = ensure(m, m->ghist, (size_t)chunk * N * sizeof(unsigned)))) return rc;
-    if (want_dcnt && (rc = ensure(m, m->dcnt, (size_t)chunk * dcnt_stride * sizeof(unsigned short)))) return rc;
-    m->dcnt_stride = dcnt_stride; m->dcnt_ready = want_dcnt;
-    // The error word is cleared only in front of a call that may raise it (model.h may_raise), or behind one that could have: the 4-byte memset is a kernel of
-    // its own on the stream, ~8 us with its gaps, 1.5 % of a 5,000-replicate step
-    const bool raises = may_raise(m, call);
-    if (!m->err_clean || raises) HIPCHK(m, hipMemsetAsync(m->err.p, 0, sizeof(int), m->stream));
-    m->err_clean = !raises;
-    double* const gram_buf = (double*)m->gram.p;
-    // round 5: all-indicator categorical models on the wave step -- the int8 product writes the uint16 count matrices the step streams itself (no fp64 slots, no
-    // scatter pass: kernels_gram_i8.h IND epilogue, kernels_nonmetric.h nmg_kernel<4>); option "nm_direct16" 0: the packed fp64 matrices + nmg_kernel<3>
-    const bool want16 = gpath == 2 && m->nonmetric && !call.moments_out && nm.direct16;
-    if (want16 && (rc = ensure(m, m->gK16, (size_t)chunk * (m->P + 1) * ((m->P + 1 + 7) & ~7) * sizeof(unsigned short) + 64))) return rc;
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = std::min<int64_t>(chunk, B - b0);
-        bool f64_gram = gpath == 1;
-        const void* cd8 = nullptr;
-        int cd8_MT = 0;
-        bool wrote16 = false;
-        if (gpath == 2) {
-            bool fallback = false;
-            if ((rc = run_gram_i8(m, call, nb, b0, gram_buf, rows_solver || nm_wave, &fallback, &cd8, &cd8_MT,
-                                  want16 ? (unsigned short*)m->gK16.p : nullptr, &wrote16))) return rc;
-            f64_gram = fallback;
-        }
-        if (!counts8_plan || f64_gram) cd8 = nullptr;                  // (a chunk that fell back has no usable int8 counts)
-        if (f64_gram || (m->nonmetric && !cd8)) {                      // (row,count) lists (+ dense uint16 histograms): the same draws as the int8 counts
-            if (lds_hist) {
-                const size_t hist_bytes = (size_t)((N + 1) / 2) * sizeof(unsigned);
-                if ((rc = allow_lds(m, (const void*)resample_kernel, hist_bytes))) return rc;
-                ProfScope ps(m, PLSPM_K_RESAMPLE);
-                hipLaunchKernelGGL(resample_kernel, dim3((unsigned)nb), dim3(256), hist_bytes, m->stream, (int)N,
-                                   d_idx ? d_idx + b0 * N : nullptr, call.seed, rep_offset + b0, (int2*)m->ent.p, (int*)m->nent.p, ent_stride, (int*)m->err.p,
-                                   want_dcnt ? (unsigned short*)m->dcnt.p : (unsigned short*)nullptr, dcnt_stride);
-            } else {
-                ProfScope ps(m, PLSPM_K_RESAMPLE);
-                hipLaunchKernelGGL(resample_global_kernel, dim3((unsigned)nb), dim3(256), 0, m->stream, (int)N, d_idx ? d_idx + b0 * N : nullptr, call.seed,
-                                   rep_offset + b0, (unsigned*)m->ghist.p, (int2*)m->ent.p, (int*)m->nent.p, ent_stride, (int*)m->err.p);
-            }
-        }
-        if (f64_gram) {
-            ProfScope ps(m, PLSPM_K_GRAM);
-            if ((rc = launch_gram_lists(m, nb, (const int2*)m->ent.p, (const int*)m->nent.p, ent_stride, (double*)m->gram.p))) return rc;
-        }
-        if (call.moments_out) {                      // plspm_bootstrap_moments (test seam): the replicates' moment matrices, dense, no solver
-            const int C = m->Pg + 1;
-            hipLaunchKernelGGL(moments_unpack_kernel, dim3((unsigned)nb), dim3(256), 0, m->stream, (const double*)m->gram.p, psize, m->T, C, call.moments_out + b0 * C * C);
-            continue;
-        }
-        SolverOut so{};
-        so.row = rows_out + b0 * R; so.row_stride = R; so.status = (int*)status_buf.p + b0; so.iters = (int*)iters_buf.p + b0;
-        const bool lists = need_lists && !cd8;                         // (built above only when the int8 counts are not used)
-        const int2* ent_l = lists ? (const int2*)m->ent.p : nullptr;
-        const int* nent_l = lists ? (const int*)m->nent.p : nullptr;
-        if (m->nonmetric && m->stage2) {
-            // two-stage HOC estimation per replicate (solver_hoc.h): stage 1 to convergence (no report), stage-2 moments by congruence,
-            // stage 2 on the second handle's descriptors with the convergence pass streaming THIS handle's data
-            plspm_model* m2 = m->stage2;
-            const long psize2 = packed_size(m2->Ts);
-            // (threads per problem: 128 unless the handle's "nm_threads" option says otherwise -- each stage reads its own handle's)
-            const int t1 = m->tune.nm_threads > 0 ? m->tune.nm_threads : 128, t2 = m2->tune.nm_threads > 0 ? m2->tune.nm_threads : 128;
-            if ((rc = run_nonmetric(m, plan_nonmetric(m, nb, cd8 != nullptr, lists, false, false), (const double*)m->gram.p, psize, SolverOut{}, ent_l, nent_l, ent_stride, t1, cd8, cd8_MT))) return rc;
-            if ((rc = run_hoc_moments(m, m2, nb))) return rc;
-            rc = run_nonmetric(m2, plan_nonmetric(m2, nb, cd8 != nullptr, lists, false, true), (const double*)m2->gram.p, psize2, so, ent_l, nent_l, ent_stride, t2, cd8, cd8_MT);
-            if (rc) return fail(m, rc, "second stage: " + m2->error);
-            continue;
-        }
-        if (m->nonmetric && nm_wave && cd8 && !f64_gram) {
-            if ((rc = run_nonmetric_wave(m, plan_nonmetric(m, nb, true, false, false, true), so, cd8, cd8_MT))) return rc;
-            continue;
-        }
-        if (m->nonmetric) {
-            m->last_nm_wave16 = 0;
-            // threads per problem by model width (measured: 60 columns 0.60 / 0.64 / 0.81 ms with 64 / 128 / 256 threads; 300 indicator
-            // columns 21.0 / 13.5 / 10.0 ms)
-            const int nm_threads = m->tune.nm_threads > 0 ? m->tune.nm_threads : (m->P > 128 ? 256 : (m->P > 64 ? 128 : 64));
-            if ((rc = run_nonmetric(m, plan_nonmetric(m, nb, cd8 != nullptr, lists, wrote16, true), (const double*)m->gram.p, psize, so, ent_l, nent_l, ent_stride, nm_threads, cd8, cd8_MT))) return rc;
-            continue;
-        }
-        // (only the last chunk's solver launch may signal the caller's event)
-        if ((rc = launch_batch_solver(m, nb, (rows_solver && !f64_gram) ? route : ROUTE_LDS, so, b0 + nb >= B ? call.stop_event : nullptr, &call.stop_taken))) return rc;
-        // the chunk's moment matrices are still in m->gram: dense where a dense solver read them, tile-packed for the LDS solver (fp64 Gram, int8 chunks that fell back)
-        if ((rc = derived_launch(m, chain, nb, chain_base + b0, rows_solver && !f64_gram, gram_buf, so.row, R))) return rc;
-        // (a chunk holds whole 256-problem tiles: the pairs stay together, and the chunk that starts at problem b0 starts at permutation b0 / 2)
-        if (micom && (rc = launch_micom(m, nb / 2, rows_solver && !f64_gram, gram_buf, so.row, (double*)m->micom_rows.p + (b0 / 2) * MS))) return rc;
-    }
-    HIPCHK(m, hipGetLastError());
-    if (rows_out == (double*)m->rows.p) m->rows_B = B;
-    if (!call.rows_out) derived_commit(m, chain, B);
-    if (micom) m->micom_B = B / 2;
     return 0;
 }
+
+// The error word is cleared only in front of a call that may raise it (batch_route.h batch_may_raise), or behind one that could have: the 4-byte memset is a kernel
+// of its own on the stream, ~8 us with its gaps, 1.5 % of a 5,000-replicate step
+static int batch_error_word(BatchRun& r) {
+    plspm_model* m = r.m;
+    if (!m->err_clean || r.plan.raises) HIPCHK(m, hipMemsetAsync(m->err.p, 0, sizeof(int), m->stream));
+    m->err_clean = !r.plan.raises;
+    return 0;
+}
+
+// (row,count) lists (+ dense uint16 histograms where the plan wants them) of a pass: the same draws as the int8 counts
+static int launch_resample_lists(BatchRun& r, const BatchPass& ps) {
+    plspm_model* m = r.m;
+    const BatchPlan& p = r.plan;
+    const int N = (int)m->N;
+    const int32_t* const d_idx = r.call.d_idx ? r.call.d_idx + ps.b0 * m->N : nullptr;
+    const int64_t rep0 = r.call.rep_offset + ps.b0;
+    if (!p.lds_hist) {
+        ProfScope prof(m, PLSPM_K_RESAMPLE);
+        hipLaunchKernelGGL(resample_global_kernel, dim3((unsigned)ps.nb), dim3(256), 0, m->stream, N, d_idx, r.call.seed, rep0, (unsigned*)m->ghist.p, (int2*)m->ent.p, (int*)m->nent.p,
+                           p.ent_stride, (int*)m->err.p);
+        return 0;
+    }
+    const size_t hist_bytes = (size_t)((m->N + 1) / 2) * sizeof(unsigned);
+    if (int rc = allow_lds(m, (const void*)resample_kernel, hist_bytes)) return rc;
+    ProfScope prof(m, PLSPM_K_RESAMPLE);
+    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)ps.nb), dim3(256), hist_bytes, m->stream, N, d_idx, r.call.seed, rep0, (int2*)m->ent.p, (int*)m->nent.p, p.ent_stride, (int*)m->err.p,
+                       p.want_dcnt ? (unsigned short*)m->dcnt.p : (unsigned short*)nullptr, p.dcnt_stride);
+    return 0;
+}
+
+// Gram + lists of a pass: the int8 product where the call takes it, the list resample where something reads lists, the fp64 Gram on them where the pass has no other
+static int batch_gram(BatchRun& r, BatchPass& ps) {
+    plspm_model* m = r.m;
+    const BatchPlan& p = r.plan;
+    int rc;
+    ps.gram = GramI8Result{};
+    if (p.gpath == 2 && (rc = run_gram_i8(m, r.call, ps.nb, ps.b0, (double*)m->gram.p, p.dense, p.want16 ? (unsigned short*)m->gK16.p : nullptr, &ps.gram))) return rc;
+    ps.k = batch_chunk(p, ps.nb, ps.gram.fallback, ps.gram.wrote16);
+    if (ps.k.build_lists && (rc = launch_resample_lists(r, ps))) return rc;
+    if (ps.k.f64_gram) {
+        ProfScope prof(m, PLSPM_K_GRAM);
+        if ((rc = launch_gram_lists(m, ps.nb, (const int2*)m->ent.p, (const int*)m->nent.p, p.ent_stride, (double*)m->gram.p))) return rc;
+    }
+    return 0;
+}
+
+// Threads per problem of the launch-by-launch non-metric kernels unless the handle's "nm_threads" says otherwise (each stage of a HOC pair reads its own): 128 for
+// the stages of a pair, else by model width (measured: 60 columns 0.60 / 0.64 / 0.81 ms with 64 / 128 / 256 threads; 300 indicator columns 21.0 / 13.5 / 10.0 ms)
+static int nm_threads_of(const plspm_model* h, bool hoc_stage) {
+    if (h->tune.nm_threads > 0) return h->tune.nm_threads;
+    return hoc_stage ? 128 : (h->P > 128 ? 256 : (h->P > 64 ? 128 : 64));
+}
+// what a non-metric solve on handle `h` reads of the pass: h's moment matrices, the first stage's lists and int8 counts
+static NmInputs nm_inputs(const BatchRun& r, const BatchPass& ps, const plspm_model* h, long mp_stride, bool hoc_stage) {
+    const plspm_model* m = r.m;
+    const bool lists = ps.k.lists, c8 = ps.k.counts8;
+    return NmInputs{(const double*)h->gram.p, mp_stride, lists ? (const int2*)m->ent.p : nullptr, lists ? (const int*)m->nent.p : nullptr, r.plan.ent_stride,
+                    c8 ? ps.gram.counts : nullptr, c8 ? ps.gram.counts_MT : 0, nm_threads_of(h, hoc_stage)};
+}
+
+// plspm_bootstrap_moments (test seam): the problems' moment matrices, dense, no solver
+static int solve_moments(BatchRun& r, const BatchPass& ps) {
+    plspm_model* m = r.m;
+    const int C = m->Pg + 1;
+    hipLaunchKernelGGL(moments_unpack_kernel, dim3((unsigned)ps.nb), dim3(256), 0, m->stream, (const double*)m->gram.p, r.plan.psize, m->T, C, r.call.moments_out + ps.b0 * C * C);
+    return 0;
+}
+// two-stage HOC estimation per problem (solver_hoc.h): stage 1 to convergence (no report), stage-2 moments by congruence, stage 2 on the second handle's descriptors
+// with the convergence pass streaming THIS handle's data
+static int solve_hoc(BatchRun& r, const BatchPass& ps) {
+    plspm_model* m = r.m;
+    plspm_model* m2 = m->stage2;
+    int rc;
+    if ((rc = run_nonmetric(m, nm_plan(r.shape.nm, ps.k.call, r.opts.nm), nm_inputs(r, ps, m, r.plan.psize, true), SolverOut{}))) return rc;
+    if ((rc = run_hoc_moments(m, m2, ps.nb))) return rc;
+    rc = run_nonmetric(m2, nm_plan(r.shape.nm2, ps.k.call2, r.opts.nm2), nm_inputs(r, ps, m2, packed_size(m2->Ts), true), ps.so);
+    return rc ? fail(m, rc, "second stage: " + m2->error) : 0;
+}
+static int solve_nm_wave(BatchRun& r, const BatchPass& ps) {
+    return run_nonmetric_wave(r.m, nm_plan(r.shape.nm, ps.k.call, r.opts.nm), nm_inputs(r, ps, r.m, r.plan.psize, false), ps.so);
+}
+static int solve_nonmetric(BatchRun& r, const BatchPass& ps) {
+    r.m->last_nm_wave16 = 0;
+    return run_nonmetric(r.m, nm_plan(r.shape.nm, ps.k.call, r.opts.nm), nm_inputs(r, ps, r.m, r.plan.psize, false), ps.so);
+}
+// the metric batch solver, and behind it what reads the pass's moment matrices while they are still in m->gram -- dense where a dense solver read them, tile-packed
+// for the LDS solver (fp64 Gram, int8 passes that fell back): the derived chain, MICOM
+static int solve_metric(BatchRun& r, const BatchPass& ps) {
+    plspm_model* m = r.m;
+    const bool dense = ps.k.dense_solver, last = ps.b0 + ps.nb >= r.call.B;
+    const double* gram = (const double*)m->gram.p;
+    int rc;
+    // (only the last pass's solver launch may signal the caller's event)
+    if ((rc = launch_batch_solver(m, ps.nb, ps.k.route, ps.so, last ? r.call.stop_event : nullptr, &r.call.stop_taken))) return rc;
+    if ((rc = derived_launch(m, r.chain, ps.nb, r.chain_base + ps.b0, dense, gram, ps.so.row, r.R))) return rc;
+    // (a pass holds whole 256-problem tiles: the pairs stay together, and the pass that starts at problem b0 starts at permutation b0 / 2)
+    if (r.plan.micom) return launch_micom(m, ps.nb / 2, dense, gram, ps.so.row, (double*)m->micom_rows.p + (ps.b0 / 2) * r.plan.micom_stride);
+    return 0;
+}
+static int batch_solve(BatchRun& r, BatchPass& ps) {
+    ps.so = SolverOut{};
+    ps.so.row = r.rows_out + ps.b0 * r.R; ps.so.row_stride = r.R; ps.so.status = (int*)r.status_buf->p + ps.b0; ps.so.iters = (int*)r.iters_buf->p + ps.b0;
+    switch (ps.k.solve) {
+        case BATCH_SOLVE_MOMENTS: return solve_moments(r, ps);
+        case BATCH_SOLVE_HOC: return solve_hoc(r, ps);
+        case BATCH_SOLVE_NM_WAVE: return solve_nm_wave(r, ps);
+        case BATCH_SOLVE_NONMETRIC: return solve_nonmetric(r, ps);
+        default: return solve_metric(r, ps);
+    }
+}
+
+static void batch_commit(BatchRun& r) {
+    plspm_model* m = r.m;
+    if (r.rows_out == (double*)m->rows.p) m->rows_B = r.call.B;
+    if (!r.call.rows_out) derived_commit(m, r.chain, r.call.B);
+    if (r.plan.micom) m->micom_B = r.call.B / 2;
+}
+
+int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
+    call.stop_taken = false;
+    int rc;
+    if ((rc = batch_check(m, call))) return rc;
+    HIPCHK(m, hipSetDevice(m->device));
+    BatchRun r{m, call, batch_shape(m), batch_options(m)};
+    r.plan = batch_plan(r.shape, r.opts, batch_kind(call));
+    r.R = r.shape.R;
+    m->last_gram_path = r.plan.gpath; m->last_boot_passes = (int)r.plan.passes;
+    if (r.plan.gpath == 2 && (rc = prepare_zs(m, r.plan.plane_floor))) return rc;
+    if ((rc = batch_reserve(r))) return rc;
+    // Whatever replaces the handle's bootstrap records voids the cross-validation, assessment and MICOM records that went with them (or whose status / iteration
+    // buffers are reused); a jackknife call writes into buffers of its own, and whatever the handle holds survives it.
+    void_records(m, call);
+    // The derived records of a plain bootstrap: a call of its own (rows_out null) sizes their buffers and starts at record 0; a sub-batch of plspm_bootstrap()
+    // writes from its position in that call (call.chain_off; the buffers are plspm_bootstrap's).
+    if ((rc = derived_begin(m, call, &r.chain))) return rc;
+    r.chain_base = call.rows_out ? call.chain_off : 0;
+    if ((rc = batch_error_word(r))) return rc;
+    for (int64_t b0 = 0; b0 < call.B; b0 += r.plan.chunk) {
+        BatchPass ps{b0, std::min<int64_t>(r.plan.chunk, call.B - b0)};
+        if ((rc = batch_gram(r, ps)) || (rc = batch_solve(r, ps))) return rc;
+    }
+    HIPCHK(m, hipGetLastError());
+    batch_commit(r);
+    return 0;
+}
+
 
 static int fetch_segments(plspm_model* m, hipStream_t cs, const double* d_records, int32_t stride, const FetchSeg* segs, int nsegs, int64_t B_total, double* out, int32_t* status,
                           int32_t* iters);
@@ -231,11 +248,11 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     int64_t parts[kBootChunksMax];
     int nparts = 1;
     parts[0] = B;
-    // (a call whose launches may raise the device error word -- model.h may_raise, the driver's own test -- clears that word at the start of every
-    //  sub-batch, which would wipe the bits of the sub-batch before: such calls run as one batch, one memset, one read)
+    // (a call whose launches may raise the device error word -- the driver's own test -- clears that word at the start of every sub-batch, which would wipe
+    //  the bits of the sub-batch before: such calls run as one batch, one memset, one read; batch_route.h batch_sub_batches_ok)
     BatchCall call;
     call.B = B; call.seed = seed; call.d_idx = d_idx;
-    if (!m->nonmetric && !may_raise(m, call))
+    if (batch_sub_batches_ok(m->nonmetric != 0, may_raise(m, call)))
         nparts = plspm_detail_chunk_plan(B, (int64_t)RS * (int64_t)sizeof(double), m->tune.boot_chunks, m->tune.boot_ratio, parts, m->tune.boot_align > 0 ? m->tune.boot_align : plspm_detail_round_units(m));
     if (nparts > 1) {
         if (!m->dl) HIPCHK(m, plspm_stream_acquire(&m->dl));

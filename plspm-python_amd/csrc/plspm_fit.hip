@@ -280,7 +280,7 @@ int plspm_fit(plspm_model_t* m, const plspm_fit_result_t* out) {
     so.fit.lv_cov = d + o_lc; so.fit.indirect = d + o_ind; so.fit.score_w = d + o_sw; so.fit.score_c = d + o_sc;
     so.fit.cov = out->cov ? d + o_cov : nullptr; so.fit.mean = d + o_mean; so.fit.sign = d_sign;
     if (m->nonmetric) {
-        if ((rc = run_nonmetric(m, plan_nonmetric(m, 1, false, false, false, true), (const double*)m->gram.p, psize, so, nullptr, nullptr, 0, 256))) return rc;
+        if ((rc = run_nonmetric(m, plan_nonmetric(m, NmCall{1, false, false, false, true}), NmInputs{(const double*)m->gram.p, psize, nullptr, nullptr, 0, nullptr, 0, 256}, so))) return rc;
     } else {
         const double* Mp; long mp_stride;
         if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;

@@ -9,39 +9,10 @@
 #include "kernels_gram_i8p.h"
 
 // ------------------------------------------------------------------------------------------------ int8 digit-plane Gram (kernels_gram_i8.h)
-static constexpr size_t kZsBudget = (size_t)24 << 30;       // digit planes of one data set: at most 24 GiB of the 288 GiB
-// Which Gram a bootstrap call of B replicates takes: 1 = fp64 MFMA on the (row,count) lists, 2 = int8 digit planes.
-// Can a non-metric bootstrap with on-device draws take its stop-rule passes' row multiplicities from the int8 counts of the digit-plane Gram
-// (plspm_detail_bootstrap counts8_plan)?
+// (whether the route is open for a data set and which calls take it: batch_route.h gram_i8_closed / choose_gram_path)
 static int cu_count_of(plspm_model* m) {
     if (!m->cu_count && hipDeviceGetAttribute(&m->cu_count, hipDeviceAttributeMultiprocessorCount, m->device) != hipSuccess) m->cu_count = 0;
     return m->cu_count;
-}
-
-bool nm_counts8_possible(const plspm_model* m) {
-    return m->nonmetric && m->tune.nm_counts8 != 0 && m->tune.resample_aux == 0 && !m->aux && m->tune.i8_shape == 16 && m->nmx_K == 0 &&
-           nm_dense_lds(plan_shape(m), m->tune.conv_pass, nullptr) != 0 && (!m->stage2 || nm_dense_lds(plan_shape(m->stage2), m->stage2->tune.conv_pass, nullptr) != 0);
-}
-// The int8 route is closed for the resident data at `slices` digit planes (0: the automatic count, budgeted as seven) -- whatever the options would prefer.
-bool gram_i8_closed(const plspm_model* m, int slices) {
-    // every model's replicates start from the moment matrix of the uploaded columns (metric, mean-imputed, non-metric, categorical
-    // indicator columns, incomplete rows zeroed, first stage of a HOC pair).  The LDS histogram bounds N; int32 accumulators need
-    // 128 N < 2^31.
-    // (int32 accumulators: |sum_i c_bi d_is| <= 128 sum_i c_bi = 128 N < 2^31, i.e. N < 2^24; the resample counts come from an LDS
-    // histogram of 65,536 rows per workgroup, larger data sets take several windows per replicate)
-    if (m->stage1 || m->N >= (1 << 24) || m->N < 2) return true;
-    // non-metric models beyond one 16-bit histogram window: the int8 route when their stop-rule passes can read the Gram's int8 counts
-    // (on-device draws, and -- round 4 -- explicit index lists too: windowed 16-bit histograms, resample_i8_kernel; a chunk that carries a
-    // multiplicity above 127 falls back to row lists from the global histogram, the fp64 Gram and the gathering pass, as for metric models);
-    // else the fp64 route
-    if (m->nonmetric && m->N > 65535 && !nm_counts8_possible(m)) return true;
-    const size_t zs_bytes = (size_t)(i8_kblocks(m->N) + I8_SLACK_KB) * (size_t)(((i8_pairs(m) + 31) / 32) * 2 * (slices ? slices : 7)) * 1024;
-    return zs_bytes > kZsBudget;
-}
-// ... and the policy on top: "gram_path" 1 / 2 decides where the route is open, else batches of "i8_min_batch" replicates and more take it.
-int choose_gram_path(const plspm_model* m, int64_t B) {
-    if (m->tune.gram_path == 1 || gram_i8_closed(m, m->tune.i8_slices)) return 1;
-    return (m->tune.gram_path == 2 || B >= m->tune.i8_min_batch) ? 2 : 1;
 }
 
 // Digit planes + pair tables of the resident data (once per upload / digit count).
@@ -418,22 +389,19 @@ static int gram_i8_product(plspm_model* m, const GramI8Plan& p, const void* cd, 
     return rc;
 }
 
-// Resample nb replicates into dense int8 counts and multiply with the digit planes: the nb moment matrices land at `out`.
-// *fallback: an explicit index list carried a multiplicity above 127 -- nothing was multiplied, the caller takes the fp64 Gram for this chunk.
-// out16 (may be null): where an all-indicator data set's products -- co-occurrence counts -- may leave as uint16 [nb][C][ld16], upper triangle, instead
-// of fp64 slots at `out`; *wrote16 tells whether this call did (the one-plane launch on 0/1 data; any other launch writes `out` as ever).
-int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, double* out, bool dense, bool* fallback,
-                const void** counts, int* counts_MT, unsigned short* out16, bool* wrote16) {
-    *fallback = false; if (counts) *counts = nullptr; if (wrote16) *wrote16 = false;
+// Resample nb replicates into dense int8 counts and multiply with the digit planes: the nb moment matrices land at `out` -- or, res->wrote16, as uint16 at out16
+// (the one-plane launch on 0/1 data; any other launch writes `out` as ever).
+int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, double* out, bool dense, unsigned short* out16, GramI8Result* res) {
+    *res = GramI8Result{};
     GramI8Plan p;
     plspm_model::Buf* cd = nullptr;
     int rc, slot = 0;
-    if ((rc = gram_i8_plan_chunk(m, call, nb, out16 && wrote16, p))) return rc;
+    if ((rc = gram_i8_plan_chunk(m, call, nb, out16 != nullptr, p))) return rc;
     if ((rc = gram_i8_counts(m, call, p, b0, &slot, &cd))) return rc;
-    if (call.d_idx && ((rc = gram_i8_overflow(m, fallback)) || *fallback)) return rc;
-    if (counts && m->tune.i8_shape == 16) { *counts = cd->p; *counts_MT = p.MT; }       // (16-row pieces: what nm_conv_dense_kernel<.., CNT8> reads)
+    if (call.d_idx && ((rc = gram_i8_overflow(m, &res->fallback)) || res->fallback)) return rc;
+    if (m->tune.i8_shape == 16) { res->counts = cd->p; res->counts_MT = p.MT; }       // (16-row pieces: what nm_conv_dense_kernel<.., CNT8> reads)
     gram_i8_note(m, p);
-    if ((rc = gram_i8_product(m, p, cd->p, out, dense, out16, wrote16))) return rc;
+    if ((rc = gram_i8_product(m, p, cd->p, out, dense, out16, &res->wrote16))) return rc;
     if (m->aux) { HIPCHK(m, hipEventRecord(m->ev_cdfree[slot], m->stream)); m->cdfree_set[slot] = true; }     // the counts buffer is free once this Gram has run
     return 0;
 }

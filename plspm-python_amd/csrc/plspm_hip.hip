@@ -347,7 +347,7 @@ int plspm_upload(plspm_model_t* m, const double* X, int64_t N, int32_t src_cols,
     if (m->aux) HIPCHK(m, hipStreamSynchronize(m->aux));
     HIPCHK(m, hipStreamSynchronize(m->stream));
     // whatever was resident is gone from here on (a failed upload leaves an empty, re-usable handle)
-    m->N = 0; m->d_Xa = nullptr; m->Xt_valid = false; m->codes_valid = false; m->ind8_valid = false; if (m->stage2) { m->stage2->codes_valid = false; m->stage2->ind8_valid = false; } void_records(m, REC_ALL); m->micom_pool_valid = false; m->dcnt_ready = false; m->zs_valid = false; m->zs_stats_ready = false;
+    m->N = 0; m->d_Xa = nullptr; m->Xt_valid = false; m->codes_valid = false; m->ind8_valid = false; if (m->stage2) { m->stage2->codes_valid = false; m->stage2->ind8_valid = false; } void_records(m, REC_ALL); m->micom_pool_valid = false; m->zs_valid = false; m->zs_stats_ready = false;
     drop_incomplete_rows(m);
     // persistent grow-only buffers: a repeated upload of the same shape allocates nothing
     const size_t raw_bytes = (size_t)N * src_cols * sizeof(double);
@@ -734,7 +734,7 @@ int plspm_model_set_incomplete_rows(plspm_model_t* m, int32_t K, const int32_t* 
 #undef NMXCHK
     plspm_dfree(d_mask);
     // the rows of Xa were rewritten: everything derived from them is stale (a caller may have run plspm_bootstrap_prepare before this call)
-    m->nmx_K = K; m->nmx_raw = raw_scale ? 1 : 0; m->Xt_valid = false; m->zs_valid = false; m->zs_stats_ready = false; m->codes_valid = false; m->ind8_valid = false; m->dcnt_ready = false;
+    m->nmx_K = K; m->nmx_raw = raw_scale ? 1 : 0; m->Xt_valid = false; m->zs_valid = false; m->zs_stats_ready = false; m->codes_valid = false; m->ind8_valid = false;
     return 0;
 }
 

@@ -394,13 +394,12 @@ int nm_run_steps(NmRun& r) {
 
 }  // namespace
 
-int run_nonmetric(plspm_model* m, const NmPlan& pl, const double* Mp, long mp_stride, const SolverOut& so_in, const int2* ent, const int* nent, long ent_stride, int threads,
-                  const void* cd8, int cd8_MT) {
+int run_nonmetric(plspm_model* m, const NmPlan& pl, const NmInputs& in, const SolverOut& so_in) {
     if (pl.error == NM_PLAN_COUNTS8_WITHOUT_DENSE) return fail(m, PLSPM_E_STATE, "non-metric bootstrap: the dense stop-rule pass does not fit and no (row,count) lists were built");
     if (pl.error == NM_PLAN_COUNTS16_WITHOUT_WAVE) return fail(m, PLSPM_E_STATE, "non-metric solver: uint16 counts without the wave step");
     if (pl.error == NM_PLAN_WORKSPACE) return fail(m, PLSPM_E_LIMIT, "non-metric solver: workspace exceeds LDS");
-    if (pl.call.counts8 != (cd8 != nullptr)) return fail(m, PLSPM_E_STATE, "non-metric solver: the plan and the call disagree about the int8 counts");
-    NmRun r{m, m->stage1 ? m->stage1 : m, pl, pl.call.nproblems, Mp, mp_stride, so_in, ent, nent, ent_stride, threads, cd8, cd8_MT};
+    if (pl.call.counts8 != (in.cd8 != nullptr)) return fail(m, PLSPM_E_STATE, "non-metric solver: the plan and the call disagree about the int8 counts");
+    NmRun r{m, m->stage1 ? m->stage1 : m, pl, pl.call.nproblems, in.Mp, in.mp_stride, so_in, in.ent, in.nent, in.ent_stride, in.threads, in.cd8, in.cd8_MT};
     r.cat = m->categorical != 0; r.nmx = m->nmx_K > 0;
     r.fuse = pl.call.finish ? 1 : 0;
     r.codes_base = m->stage1 ? m->d_mv_base2 : m->d_mv_base;
@@ -428,7 +427,9 @@ int run_nonmetric(plspm_model* m, const NmPlan& pl, const double* Mp, long mp_st
 // replicates of the headline's shape (profiles/r05_nonmetric_kernels.txt).  Here: 1 launch that iterates on the bound, then -- for the steps it continued
 // behind -- an eighth of the rows (a lower bound of the criterion that only has to clear the tolerance), ONE host read-back, and the exact pass + replay for
 // whatever the lower bound could not confirm (nothing, as a rule).  Dense moment matrices at m->gram; cd8 / cd8_MT: the int8 counts the Gram consumed.
-int run_nonmetric_wave(plspm_model* m, const NmPlan& pl, const SolverOut& so, const void* cd8, int cd8_MT) {
+int run_nonmetric_wave(plspm_model* m, const NmPlan& pl, const NmInputs& in, const SolverOut& so) {
+    const void* const cd8 = in.cd8;
+    const int cd8_MT = in.cd8_MT;
     const int P = m->P, L = m->L, W = P + L + 1;                 // a map: c_p | k_l | the bound of its step
     const long N = m->N, ntiles16 = pl.ntiles16, nb = pl.call.nproblems;
     int rc;

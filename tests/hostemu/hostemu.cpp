@@ -19,6 +19,7 @@
 #include "../../plspm-python_amd/csrc/solver_route.h"
 #include "../../plspm-python_amd/csrc/nm_route.h"
 #include "../../plspm-python_amd/csrc/gram_route.h"
+#include "../../plspm-python_amd/csrc/batch_route.h"
 
 using namespace plspm;
 
@@ -185,6 +186,28 @@ static void run_plain(int nthreads_in, Body body) {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t) th.emplace_back([&, t]() { HostExec ex{t, nthreads, &bar, red.data()}; body(ex); });
     for (auto& x : th) x.join();
+}
+
+// flat arrays -> the inputs of nm_plan (the order hostemu_nm_plan documents) and of batch_plan (hostemu_batch_plan)
+static NmShape nm_shape_of(const long* sh) {
+    NmShape s{};
+    s.P = (int)sh[0]; s.P1 = (int)sh[1]; s.Pm = (int)sh[2]; s.L = (int)sh[3]; s.kmax = (int)sh[4]; s.n_chol = (int)sh[5]; s.n_eff = (int)sh[6]; s.nedge = (int)sh[7]; s.cmax = (int)sh[8];
+    s.kmv = (int)sh[9]; s.kb = (int)sh[10]; s.max_iter = (int)sh[11]; s.N = sh[12]; s.nmx_K = (int)sh[13];
+    s.nonmetric = sh[14]; s.categorical = sh[15]; s.cat_pure = sh[16]; s.src_cat_pure = sh[17]; s.all_mode_a = sh[18]; s.attached = sh[19]; s.has_stage2 = sh[20]; s.has_ind = sh[21];
+    s.codes_tables = sh[22];
+    return s;
+}
+static NmOptions nm_options_of(const int* o) { return NmOptions{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11], o[12]}; }
+struct BatchIn { BatchShape s; BatchOptions o; BatchKind c; };
+static BatchIn batch_in_of(const long* sh, const int* boff, const long* nm1, const long* nm2, const int* o, const int* onm1, const int* onm2, const long* call) {
+    BatchIn in{};
+    in.s.N = sh[0]; in.s.P = (int)sh[1]; in.s.Pg = (int)sh[2]; in.s.T = (int)sh[3]; in.s.L = (int)sh[4]; in.s.R = (int)sh[5]; in.s.n_ind = (int)sh[6];
+    in.s.nonmetric = sh[7]; in.s.has_stage1 = sh[8]; in.s.has_stage2 = sh[9]; in.s.micom_on = sh[10]; in.s.plain_metric = sh[11];
+    in.s.route = RouteShape{in.s.P, in.s.L, (int)sh[12], (int)sh[13], (int)sh[14], (int)sh[15], boff};
+    in.s.nm = nm_shape_of(nm1); in.s.nm2 = nm_shape_of(nm2);
+    in.o = BatchOptions{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], nm_options_of(onm1), nm_options_of(onm2), o[11] != 0};
+    in.c = BatchKind{call[0], call[1] != 0, call[2] != 0, call[3] != 0, call[4] != 0, call[5] != 0, call[6] != 0};
+    return in;
 }
 
 extern "C" {
@@ -600,12 +623,7 @@ int hostemu_solver_route(int P, int L, int kmax, int n_chol, int n_eff, int nedg
 // order of NmOptions.  out: error, dense, dense_whole, use_codes, use_mfma, flag_from_list, k16, wave_step, bound_ok, sub_pass, one_launch, step LMAX, CMAX, CPL, num_one,
 // direct16, KS, tpc, nparts, nsub, cat_fast
 void hostemu_nm_plan(const long* sh, const long* call, const int* o, long* out) {
-    NmShape s{};
-    s.P = (int)sh[0]; s.P1 = (int)sh[1]; s.Pm = (int)sh[2]; s.L = (int)sh[3]; s.kmax = (int)sh[4]; s.n_chol = (int)sh[5]; s.n_eff = (int)sh[6]; s.nedge = (int)sh[7]; s.cmax = (int)sh[8];
-    s.kmv = (int)sh[9]; s.kb = (int)sh[10]; s.max_iter = (int)sh[11]; s.N = sh[12]; s.nmx_K = (int)sh[13];
-    s.nonmetric = sh[14]; s.categorical = sh[15]; s.cat_pure = sh[16]; s.src_cat_pure = sh[17]; s.all_mode_a = sh[18]; s.attached = sh[19]; s.has_stage2 = sh[20]; s.has_ind = sh[21];
-    s.codes_tables = sh[22];
-    const NmPlan p = nm_plan(s, NmCall{call[0], call[1] != 0, call[2] != 0, call[3] != 0, call[4] != 0}, NmOptions{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11], o[12]});
+    const NmPlan p = nm_plan(nm_shape_of(sh), NmCall{call[0], call[1] != 0, call[2] != 0, call[3] != 0, call[4] != 0}, nm_options_of(o));
     const long v[] = {p.error, p.dense, p.dense_whole, p.use_codes, p.use_mfma, p.flag_from_list, p.k16, p.wave_step, p.bound_ok, p.sub_pass, p.one_launch, p.step_lmax, p.step_cmax, p.step_cpl,
                       p.num_one, p.direct16, p.KS, p.tpc, p.nparts, p.nsub, p.cat_fast};
     for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
@@ -622,6 +640,33 @@ void hostemu_gram_i8_plan(const int* data, const int* o, const long* call, long*
     const long v[] = {p.form, p.waves, p.variant, p.dma_buffer, p.rt_tall, p.rt_short, p.nty_tall, p.nty_short, p.nty, p.ntx, p.MT, p.per_xcd, p.grid, p.block, p.pp_wgs, p.sk_grid,
                       p.hist, (long)p.hist_bytes, (long)p.hist_windows, (long)p.hist_threads, (long)p.cd_bytes, p.to16,
                       gram_i8_priv_takes(d, opt, c.experiments), (long)gram_i8_round_units(d, opt, c.cu_count, c.experiments)};
+    for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
+}
+
+// The plan of one call of the batch driver (csrc/batch_route.h batch_plan).  sh: N, P, Pg, T, L, R, n_ind, then the flags nonmetric, has_stage1, has_stage2, micom_on,
+// plain_metric, then kmax, n_chol, n_eff, nedge of the RouteShape (boff beside it); nm1 / nm2: the NmShape of the handle and of its second stage as hostemu_nm_plan takes
+// them; o: gram_path, i8_min_batch, i8_slices, nm_counts8, resample_aux, i8_shape, i8_sched, solver_wave, solver_quad, solver_rows, boot_pass, aux_stream; onm1 / onm2 in the
+// order of NmOptions; call: B, own_counts, pairs, stratified, explicit_idx, moments, rows_out.  out: gpath, plane_floor, lds_hist, counts8_plan, want_dcnt, route, rows_solver,
+// nm_wave, dense, need_lists, need_ghist, cat_one, want16, micom, raises, ent_stride, dcnt_stride, psize, gk16_stride, micom_stride, kpad, then the bytes per problem ent, gram_budget,
+// gram, ghist, dcnt, counts, verify, nent, gk16, then per_rep, budget, chunk, passes, then the int8 route's predicates: closed at the handle's plane count, open for a call
+// that brings its counts, nm_counts8_possible, sub-batches allowed
+void hostemu_batch_plan(const long* sh, const int* boff, const long* nm1, const long* nm2, const int* o, const int* onm1, const int* onm2, const long* call, long* out) {
+    const BatchIn in = batch_in_of(sh, boff, nm1, nm2, o, onm1, onm2, call);
+    const BatchPlan p = batch_plan(in.s, in.o, in.c);
+    const long v[] = {p.gpath, p.plane_floor, p.lds_hist, p.counts8_plan, p.want_dcnt, p.route, p.rows_solver, p.nm_wave, p.dense, p.need_lists, p.need_ghist, p.cat_one, p.want16, p.micom, p.raises,
+                      p.ent_stride, p.dcnt_stride, p.psize, p.gk16_stride, p.micom_stride, (long)p.kpad, (long)p.ent_bytes, (long)p.gram_budget_bytes, (long)p.gram_bytes, (long)p.ghist_bytes,
+                      (long)p.dcnt_bytes, (long)p.counts_bytes, (long)p.verify_bytes, (long)p.nent_bytes, (long)p.gk16_bytes, (long)p.per_rep, (long)p.budget, (long)p.chunk, (long)p.passes,
+                      gram_i8_closed(in.s, in.o, in.o.i8_slices), gram_counts_route_open(in.s, in.o), nm_counts8_possible(in.s, in.o), batch_sub_batches_ok(in.s.nonmetric, p.raises)};
+    for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
+}
+
+// What a pass of `nb` problems revises of that plan (batch_chunk): the same inputs, then nb, fell_back, wrote16.  out: f64_gram, counts8, build_lists, lists, dense_solver,
+// route, solve, then the NmCall of the pass and of a HOC pair's second stage (nproblems, counts8, lists_dcnt, counts16_ready, finish each)
+void hostemu_batch_chunk(const long* sh, const int* boff, const long* nm1, const long* nm2, const int* o, const int* onm1, const int* onm2, const long* call, const long* pass, long* out) {
+    const BatchIn in = batch_in_of(sh, boff, nm1, nm2, o, onm1, onm2, call);
+    const BatchChunk k = batch_chunk(batch_plan(in.s, in.o, in.c), pass[0], pass[1] != 0, pass[2] != 0);
+    const long v[] = {k.f64_gram, k.counts8, k.build_lists, k.lists, k.dense_solver, k.route, k.solve, k.call.nproblems, k.call.counts8, k.call.lists_dcnt, k.call.counts16_ready, k.call.finish,
+                      k.call2.nproblems, k.call2.counts8, k.call2.lists_dcnt, k.call2.counts16_ready, k.call2.finish};
     for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
 }
 

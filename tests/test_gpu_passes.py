@@ -147,3 +147,28 @@ def test_jackknife_in_three_passes():
     records = capped_and_not(nm, G, call)
     for q in later_passes(G):
         check_oracle(X, model, records, q, np.arange(N) % G != q)
+
+
+def test_the_plan_is_what_runs():
+    """csrc/batch_route.h through the emulation build (helpers_batch_route) against the handle's own report: the passes and the Gram route of this file's handle at
+    B 600, uncapped and capped, on either Gram; and of a Scale.NUM handle of 300 rows."""
+    import helpers_batch_route as hb
+    import test_nm_route as nmr
+    from test_gpu_nmwave import _handle
+    emu = hb.load_emu()
+    _, _, nm = handle()
+    shape = hb.metric_shape([3, 3, 3], "ABA", C3, N)
+    for gram_path in (0, 1):
+        for cap in (0, CAP):
+            nm.set_option("gram_path", gram_path)
+            nm.set_option("boot_pass", cap)
+            nm.bootstrap_device(600, seed=3)
+            p = hb.plan(emu, shape, hb.call(600), gram_path=gram_path, boot_pass=cap)
+            assert (p["passes"], p["gpath"]) == (nm.get_option("last_boot_passes"), nm.get_option("last_gram_path")) == (3 if cap else 1, 1 if gram_path else 2)
+    Cn = orc.chain_C(2)
+    X, blocks = orc.synth(300, Cn, 7, seed=21)
+    num = _handle(X, blocks, Cn, "AA", "factorial")             # (Scale.NUM; sets gram_path 2)
+    num.bootstrap_device(300, seed=3)
+    p = hb.plan(emu, hb.nonmetric_shape(nmr.num_shape([7, 7], 300)), hb.call(300), gram_path=2)
+    assert (p["passes"], p["gpath"]) == (num.get_option("last_boot_passes"), num.get_option("last_gram_path")) == (1, 2)
+    assert p["nm_wave"] == num.get_option("last_nm_wave16") == 1
