@@ -10,6 +10,7 @@
 
 #include "../../include/plspm_hip_test.h"
 #include "gram_route.h"
+#include "group_route.h"
 
 inline thread_local std::string g_create_error;
 
@@ -262,8 +263,8 @@ int plspm_detail_fetch_records(plspm_model* m, const double* d_records, int64_t 
 // collective (plspm_group_bootstrap): sizes in a geometric progression (ratio_pct / 100: what moving a unit costs relative to computing it), so that
 // the transfer of sub-batch k hides under the kernels of sub-batch k + 1 and only the last, smallest transfer is exposed; every part but the last
 // a multiple of `align` units (64: whole count tiles of the int8 Gram; plspm_detail_round_units: whole rounds of the machine).  chunks_opt 0: automatic (one part below 2 MiB of results, else up to three),
-// n >= 1: n parts.  Returns the number of parts (<= kBootChunksMax), sizes in parts[].  Host arithmetic only (plspm_group.cpp).
-static constexpr int kBootChunksMax = 8;
+// n >= 1: n parts.  Returns the number of parts (<= kBootChunksMax), sizes in parts[].  Host arithmetic only (group_route.h chunk_plan).
+using plspm::kBootChunksMax;
 int plspm_detail_chunk_plan(int64_t B, int64_t bytes_per_unit, int chunks_opt, int ratio_pct, int64_t* parts, int64_t align = 64);
 // Replicates that fill ONE round of the device with tall tiles of the int8 Gram on this handle's model (whole tile rows: a row of tall tiles
 // is 320 / 256 replicates x every pair tile) -- the alignment of the sub-batches of a call: a part that ends inside a round pays for the

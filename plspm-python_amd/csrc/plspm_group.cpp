@@ -25,6 +25,8 @@
 
 #include "model.h"
 
+using namespace plspm;      // group_route.h: the plan of a call
+
 namespace {
 
 struct Rccl {
@@ -99,6 +101,7 @@ struct Local {
     double* d_word = nullptr;                      // barrier / max scratch
     double* h_word = nullptr;                      // pinned mirror
     plspm_model::Buf bcast;                        // gather_root: the summary table on its way from rank 0 to the other ranks
+    int shard_rc = 0, shard_done = 0;              // the call being enqueued: its shard's error, sub-batches whose `computed` event is recorded
 };
 
 // Resident helper threads of a group with several local handles: every handle's shard is enqueued by its own thread (handle 0 by the
@@ -175,13 +178,9 @@ struct plspm_group {
     std::vector<Local> loc;
     int next_slot = 0, last_slot = -1;
     bool pending[2] = {false, false};
-    int64_t last_B = 0, last_cap = 0;              // last call: replicates, records per rank (all sub-batches)
-    // sub-batches of the last call ("chunks"): sub-batch k = the global replicate ids [sub_first[k], sub_first[k] + sub_B[k]), sharded over the ranks like
-    // a call of its own; its gathered records start at record nranks * sub_off[k] of the receive buffer, sub_cap[k] per rank
-    int last_K = 1;
-    int64_t sub_B[kBootChunksMax] = {}, sub_first[kBootChunksMax] = {}, sub_cap[kBootChunksMax] = {}, sub_off[kBootChunksMax] = {};
-    int opt_chunks = 0, opt_ratio = 50;            // plspm_group_set_option
-    int opt_align = 0;                             // "chunk_align": 0 = whole rounds of the device (plspm_detail_round_units), n > 0 = multiples of n replicates per rank
+    GroupPlan last{};                              // the plan of the last call (group_route.h): its sub-batches and where their shards lie in the receive buffer
+    GroupOptions opt{0, 50, 0};                    // plspm_group_set_option "chunks", "chunk_ratio", "chunk_align" (0 = whole rounds of the device: plspm_detail_round_units)
+    bool one_device = false;                       // handles sharing one device (tests, single-GPU runs of this path) exchange their records in ONE launch instead of G x G copies
     // The automatic alignment is rank-LOCAL state (CU count, "i8_cus", whether the digit planes could be built), while the number and sizes of the
     // collectives must be the same on every rank: the ranks agree on it (max over ranks, one blocking all-reduce) in the first plspm_group_bootstrap
     // that consults it, and again after an upload / option change on a handle (calls every rank makes alike).  0 = not agreed.
@@ -216,13 +215,16 @@ int gfail(plspm_group* g, int code, const std::string& msg) {
         if (n__ != ncclSuccess) return gfail((g), -(1000 + (int)n__), std::string(#call) + ": " + (r)->GetErrorString(n__)); \
     } while (0)
 
-void shard_of(int64_t B, int nranks, int rank, int64_t* first, int64_t* count) {
-    const int64_t base = B / nranks, extra = B % nranks;
-    *first = rank * base + std::min<int64_t>(rank, extra);
-    *count = base + (rank < extra ? 1 : 0);
-}
+// The first failure of a sequence of calls that all have to be made whatever happens (a collective every rank joins): later ones are dropped.
+struct FirstError {
+    int code = 0;
+    std::string text;
+    void set(int c, const std::string& t) { if (!code) { code = c; text = t; } }
+    void hip(hipError_t e, const char* what) { if (e != hipSuccess && !code) set(-(int)e, std::string(what) + hipGetErrorString(e)); }
+    void nccl(ncclResult_t n, const char* what) { if (n != ncclSuccess && !code) set(-(1000 + (int)n), std::string(what) + g_rccl.GetErrorString(n)); }
+};
 
-int grow(plspm_group* g, Local& l, plspm_model::Buf& b, size_t bytes) {
+int grow(plspm_group* g, plspm_model::Buf& b, size_t bytes) {
     if (bytes <= b.cap) return 0;
     if (b.p) plspm_dfree(b.p);                     // (the caller synchronised every stream of the group)
     b.p = nullptr; b.cap = 0;
@@ -277,30 +279,216 @@ void plspm_detail_group_orphan(void* group) { if (group) group_release((plspm_gr
 void plspm_detail_group_plan_changed(void* group) { if (group) ((plspm_group*)group)->agreed_units = 0; }
 
 int plspm_detail_chunk_plan(int64_t B, int64_t bytes_per_unit, int chunks_opt, int ratio_pct, int64_t* parts, int64_t align) {
-    parts[0] = B;
-    if (B < 1) return 1;
-    if (align < 1) align = 64;
-    int n = chunks_opt;
-    if (n <= 0) n = (B * bytes_per_unit < ((int64_t)2 << 20)) ? 1 : 3;           // automatic: nothing worth hiding below 2 MiB of results
-    n = std::min(n, kBootChunksMax);
-    // no part below 512 units (a sub-batch's fixed costs: three launches + an event) -- nor below one alignment unit (a round of the machine)
-    n = (int)std::min<int64_t>(n, std::max<int64_t>(1, (B + align / 2) / std::max<int64_t>(512, align)));
-    if (n <= 1) return 1;
-    const double q = std::min(100, std::max(10, ratio_pct)) / 100.0;
-    double wsum = 0.0, w = 1.0;
-    for (int k = 0; k < n; ++k, w *= q) wsum += w;
-    int64_t left = B;
-    w = 1.0;
-    int k = 0;
-    for (; k < n - 1; ++k, w *= q) {
-        int64_t c = (int64_t)((double)B * w / wsum + 0.5);
-        c = std::max<int64_t>(align, (c + align / 2) / align * align);
-        if (left - c < std::min<int64_t>(align, 64)) break;                        // the remainder would be no part of its own
-        parts[k] = c; left -= c;
-    }
-    parts[k] = left;
-    return k + 1;
+    return chunk_plan(B, bytes_per_unit, chunks_opt, ratio_pct, parts, align);
 }
+
+namespace {
+
+// ---- communicator set-up
+ncclConfig_t capped_config(int max_channels) {      // (0: RCCL's default channel count)
+    ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
+    if (max_channels > 0) { cfg.minCTAs = 1; cfg.maxCTAs = max_channels; }
+    return cfg;
+}
+
+// The plspm_comm a set-up function is building: a failed set-up destroys it.  The communicators a failed group of ncclCommInitRankConfig / ncclCommSplit calls did
+// create are destroyed with it, not dropped (ncclCommAbort where the library has it: the peers of a half-built communicator may never arrive at a collective destroy).
+struct CommDestroy { void operator()(plspm_comm* c) const { plspm_comm_destroy(c); } };
+using CommOwner = std::unique_ptr<plspm_comm, CommDestroy>;
+
+// One init call per local device (ncclCommInitRankConfig / ncclCommSplit), as one group call where `grouped`: the first error wins, and nothing returns between
+// GroupStart and GroupEnd.  *what names the call that failed.
+template <class Init>
+ncclResult_t init_per_device(const Rccl* r, const plspm_comm* c, bool grouped, const char** what, Init init) {
+    ncclResult_t first = ncclSuccess, rc = grouped ? r->GroupStart() : ncclSuccess;
+    if (rc != ncclSuccess) { *what = "ncclGroupStart"; return rc; }
+    for (int i = 0; i < (int)c->devices.size(); ++i) {
+        if (hipSetDevice(c->devices[i]) != hipSuccess) { if (first == ncclSuccess) first = ncclUnhandledCudaError; continue; }
+        rc = init(i);
+        if (rc != ncclSuccess && first == ncclSuccess) first = rc;
+    }
+    if (grouped) { rc = r->GroupEnd(); if (first == ncclSuccess) first = rc; }
+    return first;
+}
+
+// ---- one call of plspm_group_bootstrap, phase by phase
+// (one rank, or ranks that share a device -- one copy launch of microseconds: nothing travels, nothing to hide; unless sub-batches are asked for by number)
+bool nothing_to_hide(const plspm_group* g) { return g->nranks == 1 || (g->comm && g->comm->transport == 3); }
+
+// The automatic alignment of the sub-batches is rank-local state: the ranks agree on it before the first plan that reads it (plspm_group.agreed_units).
+int agree_units(plspm_group* g) {
+    if (!group_consults_units(g->opt, nothing_to_hide(g)) || g->agreed_units > 0) return 0;
+    // every rank takes this branch alike (group options, rank count, and an agreement voided only by calls all ranks make); what a rank
+    // contributes is its own business -- a rank whose planes could not be built says 64 and fails in its shard below, BEHIND the collectives
+    double units = 64.0;
+    for (auto& l : g->loc) units = std::max(units, (double)plspm_detail_round_units(l.m));
+    int arc = plspm_group_max(g, &units);
+    if (arc) return arc;
+    g->agreed_units = (int64_t)units;
+    return 0;
+}
+
+// How a call of B replicates is cut into sub-batches on this group ("chunks" / "chunk_ratio"): K ranges of global replicate ids, each sharded
+// over the ranks like a call of its own.  A function of rank-INVARIANT inputs only -- B, nranks, the group's options, the record width and the
+// alignment the ranks agreed on (agree_units) -- so every rank of a job issues the same number of collectives of the same sizes whatever
+// happened to it locally.  The forecast (plspm_group_plan) and the call itself plan here.
+GroupPlan plan_call(const plspm_group* g, int64_t B) {
+    // (not agreed yet -- a forecast through plspm_group_plan before the first call: this rank's own figure as its handle stands, nothing built for it)
+    const int64_t units = g->opt.align > 0 ? g->opt.align : (g->agreed_units > 0 ? g->agreed_units : plspm_detail_round_units_peek(g->loc[0].m));
+    return group_plan(B, g->nranks, plspm_row_stride(g->loc[0].m), g->opt, units, nothing_to_hide(g));
+}
+
+// The send and receive buffers of slot s (of both slots, when they grow) hold the call.
+int reserve_slot(plspm_group* g, int s, const GroupPlan& p) {
+    bool must_grow = false;
+    for (auto& l : g->loc) if (l.send[s].cap < p.send_bytes || l.recv[s].cap < p.recv_bytes) must_grow = true;
+    if (!must_grow) return 0;
+    int rc;
+    if ((rc = sync_all(g))) return rc;                 // nothing may be in flight on a buffer that is about to be replaced
+    g->pending[0] = g->pending[1] = false; g->last_slot = -1;
+    for (auto& l : g->loc) {
+        GHIP(g, hipSetDevice(l.m->device));
+        for (int k = 0; k < 2; ++k) if ((rc = grow(g, l.send[k], p.send_bytes)) || (rc = grow(g, l.recv[k], p.recv_bytes))) return rc;
+    }
+    return 0;
+}
+
+// The shard kernels of local handle i, every sub-batch of the call (enqueue only; non-metric models iterate with host read-backs), into its send buffer of slot s.
+// Leaves Local.shard_rc / shard_done.  Runs on the handle's own resident thread (ShardCrew).
+void run_shard(plspm_group* g, const GroupPlan& p, int s, uint64_t seed, int64_t rep_offset, int i) {
+    Local& l = g->loc[i];
+    plspm_model* m = l.m;
+    l.shard_rc = 0; l.shard_done = 0;
+    if (hipSetDevice(m->device) != hipSuccess) { l.shard_rc = fail(m, PLSPM_E_STATE, "hipSetDevice failed"); return; }
+    if (g->pending[s]) {
+        // slot s was last read / written by the collective of two calls ago -- long finished, as a rule: then no wait is enqueued at all (a wait
+        // is a barrier packet the queue drains the device for even when its event has fired: ~5 us of a 0.48 ms step)
+        auto wait_unless_done = [&](hipEvent_t e) { if (!g->opt_lean_events || hipEventQuery(e) != hipSuccess) { (void)hipGetLastError(); hipStreamWaitEvent(m->stream, e, 0); } };
+        if (g->use_rccl || g->one_device) wait_unless_done(l.gathered[s]);          // (one launch / one collective read every send buffer)
+        else for (auto& peer : g->loc) wait_unless_done(peer.gathered[s]);          // peers pull from this send buffer
+    }
+    const int RS = p.RS;
+    for (int k = 0; k < p.K; ++k) {
+        const GroupSub& sub = p.sub[k];
+        const GroupShard sh = group_shard(p, k, g->first_rank + i);
+        double* send = (double*)l.send[s].p + sub.off * RS;
+        // (a full shard: its last kernel signals `computed` itself; a ragged one records the event behind the padding below)
+        const bool fused = g->opt_lean_events && group_shard_full(p, k, sh.count);
+        BatchCall call;
+        call.B = sh.count; call.seed = seed; call.rep_offset = rep_offset + sub.first + sh.first; call.rows_out = send;
+        call.stop_event = fused ? l.computed[s][k] : nullptr;
+        if (sh.count > 0 && (l.shard_rc = plspm_detail_bootstrap(m, call))) return;
+        if (call.stop_taken) { l.shard_done = k + 1; continue; }      // (taken by the solver launch; left alone by routes that do not end in it)
+        if (sh.count < sub.cap && hipMemsetAsync(send + sh.count * RS, 0xFF, (size_t)(sub.cap - sh.count) * RS * sizeof(double), m->stream) != hipSuccess) {   // NaN status: not a replicate
+            l.shard_rc = fail(m, PLSPM_E_STATE, "hipMemsetAsync failed"); return;
+        }
+        if (hipEventRecord(l.computed[s][k], m->stream) != hipSuccess) { l.shard_rc = fail(m, PLSPM_E_STATE, "hipEventRecord failed"); return; }
+        l.shard_done = k + 1;
+    }
+}
+
+// A failed shard (out of memory, an LDS limit, a read-back error of a non-metric model) must not keep this rank out of the
+// collectives: the other ranks of the job are already inside them and would wait forever.  Its send buffer becomes NaN-status
+// records (never counted as replicates) from the failed sub-batch on, every all-gather runs as planned, and the error is reported afterwards.
+// Returns the first local handle whose shard failed, -1 when none did.
+int void_failed_shards(plspm_group* g, const GroupPlan& p, int s) {
+    int first_bad = -1;
+    for (int i = 0; i < (int)g->loc.size(); ++i) {
+        Local& l = g->loc[i];
+        if (!l.shard_rc) continue;
+        if (first_bad < 0) first_bad = i;
+        hipSetDevice(l.m->device);
+        (void)hipGetLastError();
+        const int k0 = l.shard_done;
+        hipMemsetAsync((double*)l.send[s].p + p.sub[k0].off * p.RS, 0xFF, (size_t)(p.cap - p.sub[k0].off) * p.RS * sizeof(double), l.m->stream);
+        for (int k = k0; k < p.K; ++k) hipEventRecord(l.computed[s][k], l.m->stream);
+    }
+    return first_bad;
+}
+
+// The exchange of sub-batch k on the gather streams, behind that sub-batch's shard kernels: one function per transport, chosen once per call.  Every rank's
+// block of the sub-batch is `doubles` long, starts at `soff` of a send buffer and lands at `roff` + rank * doubles of a receive buffer (in doubles).
+struct SubSpan { size_t doubles, soff, roff; };
+SubSpan span_of(const GroupPlan& p, int k) {
+    const size_t soff = (size_t)p.sub[k].off * p.RS;
+    return SubSpan{(size_t)p.sub[k].cap * p.RS, soff, soff * p.nranks};
+}
+using Exchange = void (*)(plspm_group* g, const GroupPlan& p, int s, int k, bool root_only, FirstError& err);
+
+// diagnostics ("skip_exchange"): the step without its exchange
+void exchange_skip(plspm_group* g, const GroupPlan&, int s, int k, bool, FirstError&) {
+    for (auto& l : g->loc) { hipSetDevice(l.m->device); hipStreamWaitEvent(l.cstream, l.computed[s][k], 0); }
+}
+
+// RCCL: one all-gather per local rank in one group call; gather_root: sends to rank 0 and its receives
+void exchange_rccl(plspm_group* g, const GroupPlan& p, int s, int k, bool root_only, FirstError& err) {
+    const Rccl* r = &g_rccl;
+    const SubSpan sp = span_of(p, k);
+    for (auto& l : g->loc) {
+        hipError_t e = hipSetDevice(l.m->device);
+        if (e == hipSuccess) e = hipStreamWaitEvent(l.cstream, l.computed[s][k], 0);
+        err.hip(e, "hipStreamWaitEvent: ");
+    }
+    ncclResult_t n = r->GroupStart();
+    if (n != ncclSuccess) { err.nccl(n, "ncclGroupStart: "); return; }
+    // between GroupStart and GroupEnd nothing returns early: an open group call would poison every later RCCL call of the process
+    for (int i = 0; i < (int)g->loc.size(); ++i) {
+        Local& l = g->loc[i];
+        hipSetDevice(l.m->device);
+        if (root_only) {
+            // the gather SURVEY 8(e) names: every rank sends its shard to rank 0, rank 0 posts one receive per rank (its own included) -- one group call
+            n = r->Send((const double*)l.send[s].p + sp.soff, sp.doubles, ncclDouble, 0, l.comm, l.cstream);
+            if (n == ncclSuccess && g->first_rank + i == 0)
+                for (int src = 0; src < g->nranks && n == ncclSuccess; ++src)
+                    n = r->Recv((double*)l.recv[s].p + sp.roff + (size_t)src * sp.doubles, sp.doubles, ncclDouble, src, l.comm, l.cstream);
+            err.nccl(n, "ncclSend / ncclRecv: ");
+            continue;
+        }
+        n = r->AllGather((const double*)l.send[s].p + sp.soff, (double*)l.recv[s].p + sp.roff, sp.doubles, ncclDouble, l.comm, l.cstream);
+        err.nccl(n, "ncclAllGather: ");
+    }
+    err.nccl(r->GroupEnd(), "ncclGroupEnd: ");
+}
+
+// handles sharing one device: ONE launch on local handle 0's gather stream instead of G x G copies
+void exchange_one_launch(plspm_group* g, const GroupPlan& p, int s, int k, bool root_only, FirstError& err) {
+    const int nl = (int)g->loc.size();
+    const SubSpan sp = span_of(p, k);
+    Local& l0 = g->loc[0];
+    hipError_t e = hipSetDevice(l0.m->device);
+    const double* send[PLSPM_GATHER_LOCAL_MAX];
+    double* recv[PLSPM_GATHER_LOCAL_MAX];
+    for (int i = 0; i < nl; ++i) {
+        if (e == hipSuccess) e = hipStreamWaitEvent(l0.cstream, g->loc[i].computed[s][k], 0);
+        send[i] = (const double*)g->loc[i].send[s].p + sp.soff; recv[i] = (double*)g->loc[i].recv[s].p + sp.roff;
+    }
+    if (e == hipSuccess && plspm_detail_gather_local(l0.cstream, nl, send, recv, sp.doubles, root_only ? 1 : nl)) e = hipErrorLaunchFailure;
+    err.hip(e, "record exchange: ");
+}
+
+// copy-engine exchange (single process, peer-mapped buffers; plspm_comm_create_ex transport 2): every rank PULLS the peers' shards with
+// device-to-device copies on its own gather stream -- no kernel, no CU: the SDMA engines move the records over xGMI
+void exchange_copies(plspm_group* g, const GroupPlan& p, int s, int k, bool root_only, FirstError& err) {
+    const int nl = (int)g->loc.size();
+    const SubSpan sp = span_of(p, k);
+    for (int d = 0; d < (root_only ? 1 : nl); ++d) {      // (gather_root: only rank 0's copy engines pull)
+        Local& dst = g->loc[d];
+        hipSetDevice(dst.m->device);
+        for (int i = 0; i < nl; ++i) {
+            hipError_t e = hipStreamWaitEvent(dst.cstream, g->loc[i].computed[s][k], 0);
+            if (e == hipSuccess) e = hipMemcpyAsync((double*)dst.recv[s].p + sp.roff + (size_t)i * sp.doubles, (const double*)g->loc[i].send[s].p + sp.soff, sp.doubles * sizeof(double), hipMemcpyDeviceToDevice, dst.cstream);
+            err.hip(e, "record exchange: ");
+        }
+    }
+}
+
+// `gathered` of slot s: the records of the call are complete in every receive buffer (behind the last exchange on the gather streams)
+void record_gathered(plspm_group* g, int s, FirstError& err) {
+    if (g->one_device) { for (auto& l : g->loc) { hipError_t e = hipEventRecord(l.gathered[s], g->loc[0].cstream); if (e != hipSuccess) err.set(-(int)e, "hipEventRecord failed"); } }
+    else for (auto& l : g->loc) { hipSetDevice(l.m->device); hipEventRecord(l.gathered[s], l.cstream); }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -339,21 +527,6 @@ void plspm_comm_destroy(plspm_comm_t* c) {
 // max_channels > 0: RCCL may run at most that many workgroups ("channels", ncclConfig_t.maxCTAs) for this communicator's collectives.  Why: the
 // all-gather of step k runs beside the Gram of step k + 1, a Gram workgroup needs a whole CU, and every CU an RCCL channel sits on is missing from a
 // launch that was cut for all of them; 44 MB per 0.48 ms (eight ranks, 5,000 replicates each) does not need RCCL's default channel count.
-// communicators a failed group of ncclCommInitRankConfig / ncclCommSplit calls did create are destroyed, not dropped (ncclCommAbort where the library has it:
-// the peers of a half-built communicator may never arrive at a collective destroy)
-static void drop_partial_comms(const Rccl* r, plspm_comm* c) {
-    for (size_t i = 0; i < c->comms.size(); ++i)
-        if (c->comms[i]) { hipSetDevice(c->devices[i]); r->CommDestroy(c->comms[i]); c->comms[i] = nullptr; }
-    c->comms.clear();
-}
-
-static ncclConfig_t capped_config(int max_channels) {
-    ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
-    cfg.minCTAs = 1;
-    cfg.maxCTAs = max_channels;
-    return cfg;
-}
-
 plspm_comm_t* plspm_comm_create_ex(const int32_t* device_ids, int32_t n_local, int32_t nranks, int32_t first_rank, const uint8_t* unique_id, int32_t transport,
                                    int32_t max_channels) {
     g_group_create_error.clear();
@@ -371,7 +544,7 @@ plspm_comm_t* plspm_comm_create_ex(const int32_t* device_ids, int32_t n_local, i
         for (int j = 0; j < i; ++j) if (device_ids[i] == device_ids[j]) distinct = false;
     }
     if (transport == PLSPM_TRANSPORT_RCCL && !distinct) return bad(PLSPM_E_ARG, "plspm_comm_create: RCCL refuses ranks that share a device");
-    plspm_comm* c = new (std::nothrow) plspm_comm();
+    CommOwner c(new (std::nothrow) plspm_comm());
     if (!c) return bad(PLSPM_E_STATE, "out of host memory");
     c->nranks = nranks; c->first_rank = first_rank;
     c->devices.assign(device_ids, device_ids + n_local);
@@ -385,52 +558,46 @@ plspm_comm_t* plspm_comm_create_ex(const int32_t* device_ids, int32_t n_local, i
                 for (int j = 0; j < n_local; ++j) {
                     if (i == j) continue;
                     int can = 0;
-                    if (hipDeviceCanAccessPeer(&can, device_ids[i], device_ids[j]) != hipSuccess || !can) { delete c; return bad(PLSPM_E_STATE, "plspm_comm_create: device " + std::to_string(device_ids[i]) + " cannot map the memory of device " + std::to_string(device_ids[j])); }
-                    if (hipSetDevice(device_ids[i]) != hipSuccess) { delete c; return bad(PLSPM_E_STATE, "hipSetDevice failed"); }
+                    if (hipDeviceCanAccessPeer(&can, device_ids[i], device_ids[j]) != hipSuccess || !can) return bad(PLSPM_E_STATE, "plspm_comm_create: device " + std::to_string(device_ids[i]) + " cannot map the memory of device " + std::to_string(device_ids[j]));
+                    if (hipSetDevice(device_ids[i]) != hipSuccess) return bad(PLSPM_E_STATE, "hipSetDevice failed");
                     const hipError_t e = hipDeviceEnablePeerAccess(device_ids[j], 0);
-                    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { delete c; return bad(-(int)e, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e)); }
+                    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return bad(-(int)e, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
                     (void)hipGetLastError();
                 }
         }
-        return c;
+        return c.release();
     }
     std::string why;
     const Rccl* r = rccl(why);
-    if (!r) { delete c; return bad(PLSPM_E_STATE, why); }
-    if (max_channels > 0 && !r->CommInitRankConfig) { delete c; return bad(PLSPM_E_STATE, "this librccl has no ncclCommInitRankConfig: max_channels needs it"); }
+    if (!r) return bad(PLSPM_E_STATE, why);
+    if (max_channels > 0 && !r->CommInitRankConfig) return bad(PLSPM_E_STATE, "this librccl has no ncclCommInitRankConfig: max_channels needs it");
     c->comms.assign(n_local, nullptr);
     c->max_channels = max_channels;
-    ncclResult_t rc;
     StdoutToStderr quiet;
+    // (what the failed call left of the communicator goes while stdout is still turned away)
+    auto nccl_bad = [&](ncclResult_t rc, const char* what) { c.reset(); return bad(-(1000 + (int)rc), std::string(what) + ": " + r->GetErrorString(rc)); };
+    ncclResult_t rc;
     if (n_local == nranks && max_channels == 0) {
         rc = r->CommInitAll(c->comms.data(), n_local, c->devices.data());
-        if (rc != ncclSuccess) { delete c; return bad(-(1000 + (int)rc), std::string("ncclCommInitAll: ") + r->GetErrorString(rc)); }
+        if (rc != ncclSuccess) return nccl_bad(rc, "ncclCommInitAll");
     } else if (n_local == nranks) {
         // all ranks of this process with a configuration: what ncclCommInitAll does, by hand (one unique id, a group of ncclCommInitRankConfig)
         ncclUniqueId uid;
         rc = r->GetUniqueId(&uid);
-        if (rc != ncclSuccess) { delete c; return bad(-(1000 + (int)rc), std::string("ncclGetUniqueId: ") + r->GetErrorString(rc)); }
-        ncclResult_t first = ncclSuccess;
-        rc = r->GroupStart();
-        if (rc != ncclSuccess) { delete c; return bad(-(1000 + (int)rc), std::string("ncclGroupStart: ") + r->GetErrorString(rc)); }
+        if (rc != ncclSuccess) return nccl_bad(rc, "ncclGetUniqueId");
         std::vector<ncclConfig_t> cfg(n_local, capped_config(max_channels));
-        for (int i = 0; i < n_local; ++i) {
-            if (hipSetDevice(c->devices[i]) != hipSuccess) { if (first == ncclSuccess) first = ncclUnhandledCudaError; continue; }
-            rc = r->CommInitRankConfig(&c->comms[i], nranks, uid, i, &cfg[i]);
-            if (rc != ncclSuccess && first == ncclSuccess) first = rc;
-        }
-        rc = r->GroupEnd();
-        if (first == ncclSuccess) first = rc;
-        if (first != ncclSuccess) { drop_partial_comms(r, c); delete c; return bad(-(1000 + (int)first), std::string("ncclCommInitRankConfig: ") + r->GetErrorString(first)); }
+        const char* what = "ncclCommInitRankConfig";
+        rc = init_per_device(r, c.get(), true, &what, [&](int i) { return r->CommInitRankConfig(&c->comms[i], nranks, uid, i, &cfg[i]); });
+        if (rc != ncclSuccess) return nccl_bad(rc, what);
     } else {
         ncclUniqueId uid;
         memcpy(&uid, unique_id, sizeof(uid));
-        if (hipSetDevice(c->devices[0]) != hipSuccess) { delete c; return bad(PLSPM_E_STATE, "hipSetDevice failed"); }
+        if (hipSetDevice(c->devices[0]) != hipSuccess) return bad(PLSPM_E_STATE, "hipSetDevice failed");
         if (max_channels > 0) { ncclConfig_t cfg = capped_config(max_channels); rc = r->CommInitRankConfig(&c->comms[0], nranks, uid, first_rank, &cfg); }
         else rc = r->CommInitRank(&c->comms[0], nranks, uid, first_rank);
-        if (rc != ncclSuccess) { delete c; return bad(-(1000 + (int)rc), std::string("ncclCommInitRank: ") + r->GetErrorString(rc)); }
+        if (rc != ncclSuccess) return nccl_bad(rc, "ncclCommInitRank");
     }
-    return c;
+    return c.release();
 }
 
 plspm_comm_t* plspm_comm_create(const int32_t* device_ids, int32_t n_local, int32_t nranks, int32_t first_rank, const uint8_t* unique_id) {
@@ -446,24 +613,17 @@ plspm_comm_t* plspm_comm_split(plspm_comm_t* parent, int32_t max_channels) {
     if (!parent->use_rccl) return bad(PLSPM_E_STATE, "plspm_comm_split: the parent does not use RCCL");
     const Rccl* r = &g_rccl;
     if (!r->CommSplit) return bad(PLSPM_E_STATE, "this librccl has no ncclCommSplit");
-    plspm_comm* c = new (std::nothrow) plspm_comm();
+    CommOwner c(new (std::nothrow) plspm_comm());
     if (!c) return bad(PLSPM_E_STATE, "out of host memory");
     c->nranks = parent->nranks; c->first_rank = parent->first_rank; c->devices = parent->devices; c->use_rccl = true; c->transport = PLSPM_TRANSPORT_RCCL; c->max_channels = max_channels;
     const int n_local = (int)c->devices.size();
     c->comms.assign(n_local, nullptr);
     StdoutToStderr quiet;
-    std::vector<ncclConfig_t> cfg(n_local);
-    for (auto& f : cfg) { ncclConfig_t init = NCCL_CONFIG_INITIALIZER; f = init; if (max_channels > 0) { f.minCTAs = 1; f.maxCTAs = max_channels; } }
-    ncclResult_t first = ncclSuccess, rc = n_local > 1 ? r->GroupStart() : ncclSuccess;
-    if (rc != ncclSuccess) { delete c; return bad(-(1000 + (int)rc), std::string("ncclGroupStart: ") + r->GetErrorString(rc)); }
-    for (int i = 0; i < n_local; ++i) {
-        if (hipSetDevice(c->devices[i]) != hipSuccess) { if (first == ncclSuccess) first = ncclUnhandledCudaError; continue; }
-        rc = r->CommSplit(parent->comms[i], 0, parent->first_rank + i, &c->comms[i], &cfg[i]);
-        if (rc != ncclSuccess && first == ncclSuccess) first = rc;
-    }
-    if (n_local > 1) { rc = r->GroupEnd(); if (first == ncclSuccess) first = rc; }
-    if (first != ncclSuccess) { drop_partial_comms(r, c); delete c; return bad(-(1000 + (int)first), std::string("ncclCommSplit: ") + r->GetErrorString(first)); }
-    return c;
+    std::vector<ncclConfig_t> cfg(n_local, capped_config(max_channels));
+    const char* what = "ncclCommSplit";
+    const ncclResult_t rc = init_per_device(r, c.get(), n_local > 1, &what, [&](int i) { return r->CommSplit(parent->comms[i], 0, parent->first_rank + i, &c->comms[i], &cfg[i]); });
+    if (rc != ncclSuccess) { c.reset(); return bad(-(1000 + (int)rc), std::string(what) + ": " + r->GetErrorString(rc)); }
+    return c.release();
 }
 
 int32_t plspm_comm_size(const plspm_comm_t* c) { return c ? c->nranks : 0; }
@@ -493,6 +653,8 @@ plspm_group_t* plspm_group_create(plspm_comm_t* c, plspm_model_t* const* models)
     g->comm = c; g->nranks = c->nranks; g->first_rank = c->first_rank; g->use_rccl = c->use_rccl;
     g->loc.resize(n_local);
     for (int i = 0; i < n_local; ++i) { g->loc[i].m = models[i]; if (c->use_rccl) g->loc[i].comm = c->comms[i]; }
+    g->one_device = !c->use_rccl && n_local <= PLSPM_GATHER_LOCAL_MAX;
+    for (int i = 1; i < n_local && g->one_device; ++i) g->one_device = models[i]->device == models[0]->device;
     auto bail = [&](const std::string& why) { plspm_group_destroy(g); g_group_create_error = why; return (plspm_group_t*)nullptr; };
     for (auto& l : g->loc) {
         l.m->group = g;
@@ -526,33 +688,6 @@ int plspm_group_sync(plspm_group_t* g) {
     return sync_all(g);
 }
 
-// How a call of B replicates is cut into sub-batches on this group ("chunks" / "chunk_ratio"): K ranges of global replicate ids, each sharded
-// over the ranks like a call of its own.  A function of rank-INVARIANT inputs only -- B, nranks, the group's options, the record width and the
-// alignment the ranks agreed on (agree_units) -- so every rank of a job issues the same number of collectives of the same sizes whatever
-// happened to it locally.
-static bool plan_consults_units(const plspm_group* g) {
-    const bool nothing_to_hide = g->nranks == 1 || (g->comm && g->comm->transport == 3);
-    return !(nothing_to_hide && g->opt_chunks <= 0) && g->opt_chunks != 1 && g->opt_align <= 0;
-}
-
-static int plan_sub_batches(const plspm_group* g, int64_t B, int RS, int64_t* sub_first, int64_t* sub_B) {
-    const int64_t per_rank = (B + g->nranks - 1) / g->nranks;
-    int64_t parts[kBootChunksMax];
-    // (one rank, or ranks that share a device -- one copy launch of microseconds: nothing travels, nothing to hide; unless sub-batches are asked for by number)
-    const bool nothing_to_hide = g->nranks == 1 || (g->comm && g->comm->transport == 3);
-    // (not agreed yet -- a forecast through plspm_group_plan before the first call: this rank's own figure as its handle stands, nothing built for it)
-    const int64_t units = g->opt_align > 0 ? g->opt_align : (g->agreed_units > 0 ? g->agreed_units : plspm_detail_round_units_peek(g->loc[0].m));
-    const int K = (nothing_to_hide && g->opt_chunks <= 0) ? 1 : plspm_detail_chunk_plan(per_rank, (int64_t)RS * (int64_t)sizeof(double), g->opt_chunks, g->opt_ratio, parts, units);
-    int64_t at = 0;
-    int n = 0;
-    for (int k = 0; k < K && at < B; ++k) {
-        const int64_t take = (k == K - 1) ? B - at : std::min<int64_t>(B - at, parts[k] * g->nranks);
-        sub_first[n] = at; sub_B[n] = take; at += take; ++n;
-    }
-    if (at < B) sub_B[n - 1] += B - at;
-    return n;
-}
-
 int plspm_chunk_plan(int64_t B, int64_t bytes_per_unit, int32_t chunks, int32_t ratio_pct, int64_t align, int64_t* parts) {
     if (!parts || B < 1 || bytes_per_unit < 1 || chunks < 0 || chunks > kBootChunksMax || ratio_pct < 10 || ratio_pct > 100 || align < 0) return -PLSPM_E_ARG;
     return plspm_detail_chunk_plan(B, bytes_per_unit, chunks, ratio_pct, parts, align);
@@ -561,17 +696,25 @@ int plspm_chunk_plan(int64_t B, int64_t bytes_per_unit, int32_t chunks, int32_t 
 int plspm_group_set_option(plspm_group_t* g, const char* key, int32_t value) {
     if (!g || !key) return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: bad arguments");
     const std::string k(key);
-    if (k == "chunks") { if (value < 0 || value > kBootChunksMax) return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: chunks in 0 .. 8"); g->opt_chunks = value; }
-    else if (k == "chunk_align") { if (value < 0 || value > (1 << 20)) return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: chunk_align in 0 .. 2^20"); g->opt_align = value; }
-    else if (k == "lean_events") { if (value < 0 || value > 1) return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: lean_events 0 | 1"); g->opt_lean_events = value; }
+    // every option is an integer in [lo, hi]; `slot`: where a plain one is kept (the two others act below)
+    const struct { const char* key; int lo, hi; const char* range; int* slot; } options[] = {
+        {"chunks", 0, kBootChunksMax, "chunks in 0 .. 8", &g->opt.chunks},
+        {"chunk_align", 0, 1 << 20, "chunk_align in 0 .. 2^20", &g->opt.align},
+        {"chunk_ratio", 10, 100, "chunk_ratio in 10 .. 100", &g->opt.ratio},
+        {"lean_events", 0, 1, "lean_events 0 | 1", &g->opt_lean_events},
+        {"skip_exchange", 0, 1, "skip_exchange 0 | 1", &g->opt_skip_exchange},
+        {"gather_root", 0, 1, "gather_root 0 | 1", nullptr},
+        {"events_device_scope", 0, 1, "events_device_scope 0 | 1", nullptr},
+    };
+    const auto* o = std::find_if(std::begin(options), std::end(options), [&](const auto& x) { return k == x.key; });
+    if (o == std::end(options)) return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: unknown option '" + k + "'");
+    if (value < o->lo || value > o->hi) return gfail(g, PLSPM_E_ARG, std::string("plspm_group_set_option: ") + o->range);
+    if (o->slot) *o->slot = value;
     else if (k == "gather_root") {
-        if (value < 0 || value > 1) return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: gather_root 0 | 1");
         if (value && g->use_rccl && (!g_rccl.Send || !g_rccl.Recv || !g_rccl.Broadcast)) return gfail(g, PLSPM_E_STATE, "plspm_group_set_option: this librccl has no ncclSend / ncclRecv / ncclBroadcast");
         g->opt_gather_root = value;
     }
-    else if (k == "skip_exchange") { if (value < 0 || value > 1) return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: skip_exchange 0 | 1"); g->opt_skip_exchange = value; }
-    else if (k == "events_device_scope") {
-        if (value < 0 || value > 1) return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: events_device_scope 0 | 1");
+    else {                                             // "events_device_scope"
         int rc = sync_all(g);
         if (rc) return rc;
         for (auto& l : g->loc) {
@@ -585,190 +728,52 @@ int plspm_group_set_option(plspm_group_t* g, const char* key, int32_t value) {
         }
         g->pending[0] = g->pending[1] = false;
     }
-    else if (k == "chunk_ratio") { if (value < 10 || value > 100) return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: chunk_ratio in 10 .. 100"); g->opt_ratio = value; }
-    else return gfail(g, PLSPM_E_ARG, "plspm_group_set_option: unknown option '" + k + "'");
     return 0;
 }
 
 int plspm_group_plan(const plspm_group_t* g, int64_t B, int32_t* n_sub, int64_t* sub_first, int64_t* sub_count) {
     if (!g || B < 1 || !n_sub || !sub_first || !sub_count || g->loc.empty()) return PLSPM_E_ARG;
-    *n_sub = plan_sub_batches(g, B, plspm_row_stride(g->loc[0].m), sub_first, sub_count);
+    const GroupPlan p = plan_call(g, B);
+    *n_sub = p.K;
+    for (int k = 0; k < p.K; ++k) { sub_first[k] = p.sub[k].first; sub_count[k] = p.sub[k].B; }
     return 0;
 }
 
+// sub-batches (round 5): the all-gather of sub-batch k runs on the gather streams beside the shard kernels of sub-batch k + 1, so that ONE
+// call hides its merge the way a loop of calls does; the gathered buffer holds the sub-batches one after the other, each in the layout of a
+// call of its own -- i.e. in replicate-id order throughout (what the device summaries' fixed-order sums rely on)
 int plspm_group_bootstrap(plspm_group_t* g, int64_t B, uint64_t seed, int64_t rep_offset) {
     if (!g || B < 1 || rep_offset < 0 || B > ((int64_t)1 << 30)) return gfail(g, PLSPM_E_ARG, "plspm_group_bootstrap: bad arguments (1 <= B <= 2^30, rep_offset >= 0)");
     if (g->loc.empty()) return gfail(g, PLSPM_E_STATE, "the group's handles were destroyed");
-    const int nl = (int)g->loc.size();
-    const int RS = plspm_row_stride(g->loc[0].m);
-    // sub-batches (round 5): the all-gather of sub-batch k runs on the gather streams beside the shard kernels of sub-batch k + 1, so that ONE
-    // call hides its merge the way a loop of calls does; the gathered buffer holds the sub-batches one after the other, each in the layout of a
-    // call of its own -- i.e. in replicate-id order throughout (what the device summaries' fixed-order sums rely on)
-    int64_t sub_first[kBootChunksMax], sub_B[kBootChunksMax], sub_cap[kBootChunksMax], sub_off[kBootChunksMax];
-    if (plan_consults_units(g) && g->agreed_units <= 0) {
-        // every rank takes this branch alike (group options, rank count, and an agreement voided only by calls all ranks make); what a rank
-        // contributes is its own business -- a rank whose planes could not be built says 64 and fails in its shard below, BEHIND the collectives
-        double units = 64.0;
-        for (auto& l : g->loc) units = std::max(units, (double)plspm_detail_round_units(l.m));
-        int arc = plspm_group_max(g, &units);
-        if (arc) return arc;
-        g->agreed_units = (int64_t)units;
-    }
-    const int K = plan_sub_batches(g, B, RS, sub_first, sub_B);
-    int64_t cap = 0;
-    for (int k = 0; k < K; ++k) { sub_cap[k] = (sub_B[k] + g->nranks - 1) / g->nranks; sub_off[k] = cap; cap += sub_cap[k]; }
-    const size_t send_bytes = (size_t)cap * RS * sizeof(double), recv_bytes = send_bytes * g->nranks;
-    const int s = g->next_slot;
     int rc;
-    bool must_grow = false;
-    for (auto& l : g->loc) if (l.send[s].cap < send_bytes || l.recv[s].cap < recv_bytes) must_grow = true;
-    if (must_grow) {                                   // nothing may be in flight on a buffer that is about to be replaced
-        if ((rc = sync_all(g))) return rc;
-        g->pending[0] = g->pending[1] = false; g->last_slot = -1;
-        for (auto& l : g->loc) {
-            GHIP(g, hipSetDevice(l.m->device));
-            for (int k = 0; k < 2; ++k) if ((rc = grow(g, l, l.send[k], send_bytes)) || (rc = grow(g, l, l.recv[k], recv_bytes))) return rc;
-        }
-    }
-    // handles sharing one device (tests, single-GPU runs of this path) exchange their records in ONE launch instead of G x G copies
-    bool one_device = !g->use_rccl && nl <= PLSPM_GATHER_LOCAL_MAX;
-    for (int i = 1; i < nl && one_device; ++i) one_device = g->loc[i].m->device == g->loc[0].m->device;
-    // 1. shard kernels (enqueue only; non-metric models iterate with host read-backs): every local handle by its own resident thread
-    std::vector<int> shard_rc(nl, 0), shard_done(nl, 0);      // shard_done[i]: sub-batches of handle i whose `computed` event is recorded
-    auto run_shard = [&](int i) {
-        Local& l = g->loc[i];
-        plspm_model* m = l.m;
-        if (hipSetDevice(m->device) != hipSuccess) { shard_rc[i] = fail(m, PLSPM_E_STATE, "hipSetDevice failed"); return; }
-        if (g->pending[s]) {
-            // slot s was last read / written by the collective of two calls ago -- long finished, as a rule: then no wait is enqueued at all (a wait
-            // is a barrier packet the queue drains the device for even when its event has fired: ~5 us of a 0.48 ms step)
-            auto wait_unless_done = [&](hipEvent_t e) { if (!g->opt_lean_events || hipEventQuery(e) != hipSuccess) { (void)hipGetLastError(); hipStreamWaitEvent(m->stream, e, 0); } };
-            if (g->use_rccl || one_device) wait_unless_done(l.gathered[s]);            // (one launch / one collective read every send buffer)
-            else for (auto& peer : g->loc) wait_unless_done(peer.gathered[s]);          // peers pull from this send buffer
-        }
-        for (int k = 0; k < K; ++k) {
-            int64_t first = 0, count = 0;
-            shard_of(sub_B[k], g->nranks, g->first_rank + i, &first, &count);
-            double* send = (double*)l.send[s].p + sub_off[k] * RS;
-            // (a full shard: its last kernel signals `computed` itself; a ragged one records the event behind the padding below)
-            const bool fused = g->opt_lean_events && count == sub_cap[k] && count > 0;
-            BatchCall call;
-            call.B = count; call.seed = seed; call.rep_offset = rep_offset + sub_first[k] + first; call.rows_out = send;
-            call.stop_event = fused ? l.computed[s][k] : nullptr;
-            if (count > 0 && (shard_rc[i] = plspm_detail_bootstrap(m, call))) return;
-            if (call.stop_taken) { shard_done[i] = k + 1; continue; }      // (taken by the solver launch; left alone by routes that do not end in it)
-            if (count < sub_cap[k] && hipMemsetAsync(send + count * RS, 0xFF, (size_t)(sub_cap[k] - count) * RS * sizeof(double), m->stream) != hipSuccess) {   // NaN status: not a replicate
-                shard_rc[i] = fail(m, PLSPM_E_STATE, "hipMemsetAsync failed"); return;
-            }
-            if (hipEventRecord(l.computed[s][k], m->stream) != hipSuccess) { shard_rc[i] = fail(m, PLSPM_E_STATE, "hipEventRecord failed"); return; }
-            shard_done[i] = k + 1;
-        }
-    };
+    if ((rc = agree_units(g))) return rc;
+    const GroupPlan plan = plan_call(g, B);
+    const int s = g->next_slot, nl = (int)g->loc.size();
+    if ((rc = reserve_slot(g, s, plan))) return rc;
+    // 1. shard kernels: every local handle by its own resident thread
+    auto shard = [&](int i) { run_shard(g, plan, s, seed, rep_offset, i); };
     const auto t_a = std::chrono::steady_clock::now();
-    if (nl > 1 && g->crew) g->crew->run(run_shard);
-    else for (int i = 0; i < nl; ++i) run_shard(i);
+    if (nl > 1 && g->crew) g->crew->run(shard);
+    else for (int i = 0; i < nl; ++i) shard(i);
     const auto t_b = std::chrono::steady_clock::now();
-    // A failed shard (out of memory, an LDS limit, a read-back error of a non-metric model) must not keep this rank out of the
-    // collectives: the other ranks of the job are already inside them and would wait forever.  Its send buffer becomes NaN-status
-    // records (never counted as replicates) from the failed sub-batch on, every all-gather runs as planned, and the error is reported afterwards.
-    int first_bad = -1;
-    for (int i = 0; i < nl; ++i) {
-        if (!shard_rc[i]) continue;
-        if (first_bad < 0) first_bad = i;
-        Local& l = g->loc[i];
-        hipSetDevice(l.m->device);
-        (void)hipGetLastError();
-        const int k0 = shard_done[i];
-        hipMemsetAsync((double*)l.send[s].p + sub_off[k0] * RS, 0xFF, (size_t)(cap - sub_off[k0]) * RS * sizeof(double), l.m->stream);
-        for (int k = k0; k < K; ++k) hipEventRecord(l.computed[s][k], l.m->stream);
-    }
-    // 2. the collective of every sub-batch, on the gather streams behind that sub-batch's shard kernels
-    const bool root_only = g->opt_gather_root != 0 && g->nranks > 0;
-    int crc = 0;
-    std::string cwhy;
-    for (int k = 0; k < K; ++k) {
-        const size_t sub_doubles = (size_t)sub_cap[k] * RS, sub_bytes = sub_doubles * sizeof(double);
-        const size_t soff = (size_t)sub_off[k] * RS, roff = soff * g->nranks;       // (in doubles)
-        if (g->opt_skip_exchange) {
-            for (auto& l : g->loc) { hipSetDevice(l.m->device); hipStreamWaitEvent(l.cstream, l.computed[s][k], 0); }
-        } else if (g->use_rccl) {
-            const Rccl* r = &g_rccl;
-            for (auto& l : g->loc) {
-                hipError_t e = hipSetDevice(l.m->device);
-                if (e == hipSuccess) e = hipStreamWaitEvent(l.cstream, l.computed[s][k], 0);
-                if (e != hipSuccess && !crc) { crc = -(int)e; cwhy = std::string("hipStreamWaitEvent: ") + hipGetErrorString(e); }
-            }
-            ncclResult_t n = r->GroupStart();
-            if (n != ncclSuccess) { if (!crc) { crc = -(1000 + (int)n); cwhy = std::string("ncclGroupStart: ") + r->GetErrorString(n); } }
-            else {
-                // between GroupStart and GroupEnd nothing returns early: an open group call would poison every later RCCL call of the process
-                for (int i = 0; i < nl; ++i) {
-                    Local& l = g->loc[i];
-                    hipSetDevice(l.m->device);
-                    if (root_only) {
-                        // the gather SURVEY 8(e) names: every rank sends its shard to rank 0, rank 0 posts one receive per rank (its own included) -- one group call
-                        n = r->Send((const double*)l.send[s].p + soff, sub_doubles, ncclDouble, 0, l.comm, l.cstream);
-                        if (n == ncclSuccess && g->first_rank + i == 0)
-                            for (int src = 0; src < g->nranks && n == ncclSuccess; ++src)
-                                n = r->Recv((double*)l.recv[s].p + roff + (size_t)src * sub_doubles, sub_doubles, ncclDouble, src, l.comm, l.cstream);
-                        if (n != ncclSuccess && !crc) { crc = -(1000 + (int)n); cwhy = std::string("ncclSend / ncclRecv: ") + r->GetErrorString(n); }
-                        continue;
-                    }
-                    n = r->AllGather((const double*)l.send[s].p + soff, (double*)l.recv[s].p + roff, sub_doubles, ncclDouble, l.comm, l.cstream);
-                    if (n != ncclSuccess && !crc) { crc = -(1000 + (int)n); cwhy = std::string("ncclAllGather: ") + r->GetErrorString(n); }
-                }
-                n = r->GroupEnd();
-                if (n != ncclSuccess && !crc) { crc = -(1000 + (int)n); cwhy = std::string("ncclGroupEnd: ") + r->GetErrorString(n); }
-            }
-        } else if (one_device) {
-            Local& l0 = g->loc[0];
-            hipError_t e = hipSetDevice(l0.m->device);
-            const double* send[PLSPM_GATHER_LOCAL_MAX];
-            double* recv[PLSPM_GATHER_LOCAL_MAX];
-            for (int i = 0; i < nl; ++i) {
-                if (e == hipSuccess) e = hipStreamWaitEvent(l0.cstream, g->loc[i].computed[s][k], 0);
-                send[i] = (const double*)g->loc[i].send[s].p + soff; recv[i] = (double*)g->loc[i].recv[s].p + roff;
-            }
-            if (e == hipSuccess && plspm_detail_gather_local(l0.cstream, nl, send, recv, sub_doubles, root_only ? 1 : nl)) e = hipErrorLaunchFailure;
-            if (e != hipSuccess && !crc) { crc = -(int)e; cwhy = std::string("record exchange: ") + hipGetErrorString(e); }
-        } else {
-            // copy-engine exchange (single process, peer-mapped buffers; plspm_comm_create_ex transport 2): every rank PULLS the peers' shards with
-            // device-to-device copies on its own gather stream -- no kernel, no CU: the SDMA engines move the records over xGMI
-            for (int d = 0; d < (root_only ? 1 : nl); ++d) {      // (gather_root: only rank 0's copy engines pull)
-                Local& dst = g->loc[d];
-                hipSetDevice(dst.m->device);
-                for (int i = 0; i < nl; ++i) {
-                    hipError_t e = hipStreamWaitEvent(dst.cstream, g->loc[i].computed[s][k], 0);
-                    if (e == hipSuccess) e = hipMemcpyAsync((double*)dst.recv[s].p + roff + (size_t)i * sub_doubles, (const double*)g->loc[i].send[s].p + soff, sub_bytes, hipMemcpyDeviceToDevice, dst.cstream);
-                    if (e != hipSuccess && !crc) { crc = -(int)e; cwhy = std::string("record exchange: ") + hipGetErrorString(e); }
-                }
-            }
-        }
-    }
-    if (one_device) { for (int i = 0; i < nl; ++i) { hipError_t e = hipEventRecord(g->loc[i].gathered[s], g->loc[0].cstream); if (e != hipSuccess && !crc) { crc = -(int)e; cwhy = "hipEventRecord failed"; } } }
-    else for (auto& l : g->loc) { hipSetDevice(l.m->device); hipEventRecord(l.gathered[s], l.cstream); }
+    const int first_bad = void_failed_shards(g, plan, s);
+    // 2. the collective of every sub-batch, on the gather streams behind that sub-batch's shard kernels; errors are reported behind the last of them
+    const bool root_only = g->opt_gather_root != 0;
+    const Exchange exchange = g->opt_skip_exchange ? exchange_skip : g->use_rccl ? exchange_rccl : g->one_device ? exchange_one_launch : exchange_copies;
+    FirstError err;
+    for (int k = 0; k < plan.K; ++k) exchange(g, plan, s, k, root_only, err);
+    record_gathered(g, s, err);
     g->t_shards_ms = std::chrono::duration<double, std::milli>(t_b - t_a).count();
     g->t_exchange_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_b).count();
-    if (first_bad >= 0 || crc) {
+    if (first_bad >= 0 || err.code) {
         // the slot's buffers were handed to the collective: they count as in flight, but the call has no result
         g->pending[s] = true; g->next_slot = s ^ 1; g->last_slot = -1;
-        if (first_bad >= 0) return gfail(g, shard_rc[first_bad], "shard of rank " + std::to_string(g->first_rank + first_bad) + ": " + g->loc[first_bad].m->error);
-        return gfail(g, crc, cwhy);
+        if (first_bad >= 0) return gfail(g, g->loc[first_bad].shard_rc, "shard of rank " + std::to_string(g->first_rank + first_bad) + ": " + g->loc[first_bad].m->error);
+        return gfail(g, err.code, err.text);
     }
-    g->pending[s] = true; g->last_slot = s; g->next_slot = s ^ 1; g->last_B = B; g->last_cap = cap; g->peers_checked = -1;
+    g->pending[s] = true; g->last_slot = s; g->next_slot = s ^ 1; g->last = plan; g->peers_checked = -1;
     g->last_root_only = root_only;
-    g->last_K = K;
-    for (int k = 0; k < K; ++k) { g->sub_B[k] = sub_B[k]; g->sub_first[k] = sub_first[k]; g->sub_cap[k] = sub_cap[k]; g->sub_off[k] = sub_off[k]; }
     return 0;
-}
-
-// Segment (sub-batch k, rank r) of the gathered records of the last call: its first record in the receive buffer, the global id of its first
-// replicate within the call, and how many replicates it holds.
-static void segment_of(const plspm_group* g, int k, int r, int64_t* rec0, int64_t* first, int64_t* count) {
-    int64_t f = 0, c = 0;
-    shard_of(g->sub_B[k], g->nranks, r, &f, &c);
-    *rec0 = g->nranks * g->sub_off[k] + (int64_t)r * g->sub_cap[k];
-    *first = g->sub_first[k] + f; *count = c;
 }
 
 // A rank whose shard failed still joins every all-gather (its records are NaN-status filler from the failed sub-batch on, so the other ranks never
@@ -782,19 +787,14 @@ static int check_peer_shards(plspm_group* g) {
     Local& l = g->loc[0];
     const int RS = plspm_row_stride(l.m);
     double* h = l.h_word + 8;
-    const int kl = g->last_K - 1;
+    const int kl = g->last.K - 1;
     GHIP(g, hipStreamWaitEvent(l.cstream, l.gathered[s], 0));
-    for (int r = 0; r < g->nranks; ++r) {
-        int64_t rec0 = 0, first = 0, count = 0;
-        segment_of(g, kl, r, &rec0, &first, &count);
-        GHIP(g, hipMemcpyAsync(h + r, (const double*)l.recv[s].p + rec0 * RS + (RS - 2), sizeof(double), hipMemcpyDeviceToHost, l.cstream));
-    }
+    for (int r = 0; r < g->nranks; ++r)
+        GHIP(g, hipMemcpyAsync(h + r, (const double*)l.recv[s].p + group_segment(g->last, kl, r).rec0 * RS + (RS - 2), sizeof(double), hipMemcpyDeviceToHost, l.cstream));
     GHIP(g, hipStreamSynchronize(l.cstream));
     g->peers_checked = s; g->peers_rc = 0;
     for (int r = 0; r < g->nranks; ++r) {
-        int64_t rec0 = 0, first = 0, count = 0;
-        segment_of(g, kl, r, &rec0, &first, &count);
-        if (count > 0 && h[r] != h[r]) {
+        if (group_segment(g->last, kl, r).count > 0 && h[r] != h[r]) {
             g->peers_rc = PLSPM_E_STATE;
             return gfail(g, PLSPM_E_STATE, "the shard of rank " + std::to_string(r) + " failed on its rank (no replicates arrived from it): the bootstrap has no complete result");
         }
@@ -811,7 +811,7 @@ int plspm_group_records(plspm_group_t* g, int32_t local, void** d_records, int64
     GHIP(g, hipEventSynchronize(l.gathered[g->last_slot]));
     { int prc; GHIP(g, hipSetDevice(g->loc[0].m->device)); if ((prc = check_peer_shards(g))) return prc; GHIP(g, hipSetDevice(l.m->device)); }
     if (d_records) *d_records = l.recv[g->last_slot].p;
-    if (n_records) *n_records = g->last_cap * g->nranks;
+    if (n_records) *n_records = g->last.cap * g->nranks;
     if (stride) *stride = plspm_row_stride(l.m);
     return 0;
 }
@@ -827,14 +827,14 @@ int plspm_group_summary(plspm_group_t* g, const double* original, double* summar
         // broadcast -- every rank makes this call (as with the all-gather, where every rank computed the same table from its own copy)
         const int R = plspm_row_width(l.m);
         const size_t words = 2 + (size_t)R * 6, bytes = words * sizeof(double);
-        if (l.bcast.cap < bytes) { GHIP(g, hipStreamSynchronize(l.cstream)); int grc = grow(g, l, l.bcast, bytes); if (grc) return grc; }
+        if (l.bcast.cap < bytes) { GHIP(g, hipStreamSynchronize(l.cstream)); int grc = grow(g, l.bcast, bytes); if (grc) return grc; }
         std::vector<double> host(words, 0.0);
         int rc0 = 0;
         if (g->first_rank == 0) {
             GHIP(g, hipStreamWaitEvent(l.m->stream, l.gathered[g->last_slot], 0));
             int64_t used = 0;
             rc0 = check_peer_shards(g);
-            if (!rc0) { rc0 = plspm_detail_summary(l.m, (const double*)l.recv[g->last_slot].p, g->last_cap * g->nranks, plspm_row_stride(l.m), plspm_row_width(l.m), original, host.data() + 2, &used); if (rc0) g->error = l.m->error; }
+            if (!rc0) { rc0 = plspm_detail_summary(l.m, (const double*)l.recv[g->last_slot].p, g->last.cap * g->nranks, plspm_row_stride(l.m), plspm_row_width(l.m), original, host.data() + 2, &used); if (rc0) g->error = l.m->error; }
             host[0] = (double)rc0; host[1] = (double)used;
             GHIP(g, hipMemcpyAsync(l.bcast.p, host.data(), bytes, hipMemcpyHostToDevice, l.cstream));
         }
@@ -851,7 +851,7 @@ int plspm_group_summary(plspm_group_t* g, const double* original, double* summar
     GHIP(g, hipStreamWaitEvent(l.m->stream, l.gathered[g->last_slot], 0));
     int rc = check_peer_shards(g);
     if (rc) return rc;
-    rc = plspm_detail_summary(l.m, (const double*)l.recv[g->last_slot].p, g->last_cap * g->nranks, plspm_row_stride(l.m), plspm_row_width(l.m), original, summary, n_used);
+    rc = plspm_detail_summary(l.m, (const double*)l.recv[g->last_slot].p, g->last.cap * g->nranks, plspm_row_stride(l.m), plspm_row_width(l.m), original, summary, n_used);
     if (rc) return gfail(g, rc, l.m->error);
     return 0;
 }
@@ -866,13 +866,12 @@ int plspm_group_rows(plspm_group_t* g, double* out, int32_t* status, int32_t* it
     GHIP(g, hipStreamWaitEvent(l.m->stream, l.gathered[g->last_slot], 0));
     { int prc = check_peer_shards(g); if (prc) return prc; }
     const double* rec = (const double*)l.recv[g->last_slot].p;
-    for (int k = 0; k < g->last_K; ++k)
+    for (int k = 0; k < g->last.K; ++k)
         for (int r = 0; r < g->nranks; ++r) {
-            int64_t rec0 = 0, first = 0, count = 0;
-            segment_of(g, k, r, &rec0, &first, &count);
-            if (!count) continue;
-            int rc = plspm_detail_fetch_records(l.m, rec + (size_t)rec0 * RS, count, RS, out ? out + first * R : nullptr, status ? status + first : nullptr,
-                                                iters ? iters + first : nullptr);
+            const GroupSegment sg = group_segment(g->last, k, r);
+            if (!sg.count) continue;
+            int rc = plspm_detail_fetch_records(l.m, rec + (size_t)sg.rec0 * RS, sg.count, RS, out ? out + sg.first * R : nullptr, status ? status + sg.first : nullptr,
+                                                iters ? iters + sg.first : nullptr);
             if (rc) return gfail(g, rc, l.m->error);
         }
     return 0;
@@ -891,17 +890,16 @@ int plspm_group_adopt(plspm_group_t* g) {
     void_records(m, REC_ROWS);
     int rc = check_peer_shards(g);             // (no extra round trip in the Plspm flow: plspm_group_summary ran -- and waited -- before)
     if (rc) return rc;
-    rc = ensure(m, m->rows, (size_t)g->last_B * RS * sizeof(double));
+    rc = ensure(m, m->rows, (size_t)g->last.B * RS * sizeof(double));
     if (rc) return gfail(g, rc, m->error);
     GHIP(g, hipStreamWaitEvent(m->stream, l.gathered[g->last_slot], 0));
     const double* rec = (const double*)l.recv[g->last_slot].p;
-    for (int k = 0; k < g->last_K; ++k)
+    for (int k = 0; k < g->last.K; ++k)
         for (int r = 0; r < g->nranks; ++r) {
-            int64_t rec0 = 0, first = 0, count = 0;
-            segment_of(g, k, r, &rec0, &first, &count);
-            if (count) GHIP(g, hipMemcpyAsync((double*)m->rows.p + first * RS, rec + (size_t)rec0 * RS, (size_t)count * RS * sizeof(double), hipMemcpyDeviceToDevice, m->stream));
+            const GroupSegment sg = group_segment(g->last, k, r);
+            if (sg.count) GHIP(g, hipMemcpyAsync((double*)m->rows.p + sg.first * RS, rec + (size_t)sg.rec0 * RS, (size_t)sg.count * RS * sizeof(double), hipMemcpyDeviceToDevice, m->stream));
         }
-    m->rows_B = g->last_B;
+    m->rows_B = g->last.B;
     return 0;
 }
 

@@ -20,6 +20,7 @@
 #include "../../plspm-python_amd/csrc/nm_route.h"
 #include "../../plspm-python_amd/csrc/gram_route.h"
 #include "../../plspm-python_amd/csrc/batch_route.h"
+#include "../../plspm-python_amd/csrc/group_route.h"
 
 using namespace plspm;
 
@@ -668,6 +669,23 @@ void hostemu_batch_chunk(const long* sh, const int* boff, const long* nm1, const
     const long v[] = {k.f64_gram, k.counts8, k.build_lists, k.lists, k.dense_solver, k.route, k.solve, k.call.nproblems, k.call.counts8, k.call.lists_dcnt, k.call.counts16_ready, k.call.finish,
                       k.call2.nproblems, k.call2.counts8, k.call2.lists_dcnt, k.call2.counts16_ready, k.call2.finish};
     for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
+}
+
+// The plan of one call of the group driver (csrc/group_route.h group_plan).  in: B, nranks, RS, then the options chunks, ratio, align, then units (the alignment the ranks
+// agreed on) and nothing_to_hide.  out: K, cap, send_bytes, recv_bytes, group_consults_units, kBootChunksMax, then first, B, cap, off of each of the K sub-batches, then for every
+// (k, rank), k-major: group_segment's rec0, first, count, group_shard's first and whether the shard is full -- 6 + 4 K + 5 K nranks values (at most 6 + 32 + 40 nranks)
+void hostemu_group_plan(const long* in, long* out) {
+    const GroupOptions o{(int)in[3], (int)in[4], (int)in[5]};
+    const GroupPlan p = group_plan(in[0], (int)in[1], (int)in[2], o, in[6], in[7] != 0);
+    long* v = out;
+    *v++ = p.K; *v++ = p.cap; *v++ = (long)p.send_bytes; *v++ = (long)p.recv_bytes; *v++ = group_consults_units(o, in[7] != 0); *v++ = kBootChunksMax;
+    for (int k = 0; k < p.K; ++k) { *v++ = p.sub[k].first; *v++ = p.sub[k].B; *v++ = p.sub[k].cap; *v++ = p.sub[k].off; }
+    for (int k = 0; k < p.K; ++k)
+        for (int r = 0; r < p.nranks; ++r) {
+            const GroupSegment sg = group_segment(p, k, r);
+            const GroupShard sh = group_shard(p, k, r);
+            *v++ = sg.rec0; *v++ = sg.first; *v++ = sg.count; *v++ = sh.first; *v++ = group_shard_full(p, k, sh.count);
+        }
 }
 
 long hostemu_packed_index(int T, int p, int q) { return packed_index(T, p, q); }

@@ -197,6 +197,47 @@ def test_group_call_as_sub_batches_is_bit_identical(nranks, B, chunks):
     group.close(); comm.close()
 
 
+_SINGLE = {}
+
+
+def _single_stream(B):
+    """Rows, status and iteration counts of B replicates (seed 5, from replicate 7) of _model() on one handle: computed once, read by every case below."""
+    if B not in _SINGLE:
+        _SINGLE[B] = _model().bootstrap(B, seed=5, rep_offset=7)
+    return _SINGLE[B]
+
+
+@pytest.mark.parametrize("nranks", [1, 2, 3])
+def test_group_plan_is_the_emulated_plan_and_its_records_the_single_handle_stream(nranks):
+    """The plan a group reports (plspm_group_plan) is csrc/group_route.h's through the emulation build (helpers_group_route) for the handle's record stride -- in count
+    tiles ("chunk_align" 64) and in the handle's own rounds ("boot_round_units" where "chunk_align" is 0) -- and a call cut that way gives the single-handle stream bit
+    for bit: one replicate per rank and an EMPTY shard (B 2 on three ranks), ragged shards (B 7), and the one size here that "chunks" 3 cuts (1,537 on one rank: at
+    least 512 per part).  One rank is the RCCL transport, several on this GPU the one-launch exchange: both have nothing to hide, so "chunks" 0 is one sub-batch."""
+    from plspm import _native
+    import helpers_group_route as hg
+    emu = hg.load_emu()
+    models = [_model() for _ in range(nranks)]
+    comm = _native.NativeComm([0] * nranks)
+    group = _native.NativeGroup(comm, models)
+    RS = models[0].row_stride
+    for chunks in (0, 3):
+        group.set_option("chunks", chunks)
+        for B in (2, 7, 1537):
+            group.set_option("chunk_align", 0)
+            units = models[0].get_option("boot_round_units")
+            want = hg.plan(emu, B, nranks, RS, chunks=chunks, align=0, units=units, nothing_to_hide=1)
+            assert group.plan(B) == [s[:2] for s in want["subs"]], (chunks, B, units)
+            group.set_option("chunk_align", 64)
+            want = hg.plan(emu, B, nranks, RS, chunks=chunks, align=64, nothing_to_hide=1)
+            assert group.plan(B) == [s[:2] for s in want["subs"]] and want["K"] == (3 if (chunks, B, nranks) == (3, 1537, 1) else 1), (chunks, B)
+            group.bootstrap(B, seed=5, rep_offset=7)
+            rows, status, iters = group.rows()
+            ref_rows, ref_status, ref_iters = _single_stream(B)
+            assert np.array_equal(rows, ref_rows) and np.array_equal(status, ref_status) and np.array_equal(iters, ref_iters), (chunks, B)
+            assert group.records(0)[1] == nranks * want["cap"]
+    group.close(); comm.close()
+
+
 @pytest.mark.parametrize("max_channels", [1, 4])
 def test_rccl_communicator_with_a_channel_cap_and_its_split(max_channels):
     """plspm_comm_create_ex(max_channels) / plspm_comm_split: RCCL communicators whose collectives run at most that many workgroups
