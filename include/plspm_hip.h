@@ -45,7 +45,7 @@ enum {
     PLSPM_NOT_CONVERGED = 1, /* reference raises Exception("Could not converge ...") weights.py:185-186 */
     PLSPM_SINGULAR = 2,      /* a regression the reference cannot solve either (e.g. Mode B on a block with missing cells, mode.py:55-56) */
     PLSPM_NONFINITE = 3,     /* zero-variance MV or NaN input                                            */
-    PLSPM_INADMISSIBLE = 4   /* PLSc and model-fit records only (plspm_plsc_*, plspm_modelfit_*): a factor's rho_A is not positive and finite, or a corrected construct correlation is not below 1 in magnitude */
+    PLSPM_INADMISSIBLE = 4   /* PLSc, model-fit and geodesic records only (plspm_plsc_*, plspm_modelfit_*, plspm_geodesic_*; the last has causes of its own): a factor's rho_A is not positive and finite, or a corrected construct correlation is not below 1 in magnitude */
 };
 /* Argument errors returned by the API functions themselves. */
 enum { PLSPM_E_ARG = 100, PLSPM_E_STATE = 101, PLSPM_E_LIMIT = 102 };
@@ -611,6 +611,38 @@ int plspm_modelfit_fit(plspm_model_t* m, double* out, int32_t* status);
 int plspm_modelfit_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
 int plspm_modelfit_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
 int plspm_modelfit_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
+
+/*
+ * ---- model fit: the geodesic discrepancy d_G ------------------------------------------------------------------------------------
+ * The third discrepancy of the family, for every replicate of a plain bootstrap: one more kernel behind the model-fit kernel, which needs the replicate's
+ * indicator correlations while they are on the device.  This library's definition, with the quantities of the model-fit records above:
+ *     d_G(Sigma) = 1/2 sum_{k=1..P} (ln phi_k)^2,  phi_k the eigenvalues of R^-1 Sigma -- those of the symmetric G^-1 Sigma G^-T with R = G G' (Cholesky)
+ * Geodesic record, width 2:  d_g_sat | d_g_est;  device records carry a status and the replicate's iteration count behind it as doubles (pitch 4).  A
+ * replicate whose bootstrap status is not PLSPM_OK keeps that status and has NaN in both.  Otherwise the status is the model-fit record's; PLSPM_INADMISSIBLE
+ * (NaN in both, not counted in n_used) where that record is inadmissible, and in this record only where a Cholesky pivot of R is not above 1e-12, where an
+ * eigenvalue phi_k of either model is not positive (Sigma is not positive definite), and where a value is not finite.  Plain metric handles only:
+ * PLSPM_E_ARG otherwise; PLSPM_E_LIMIT from the call that launches the kernel where one replicate's two P x P triangles exceed a workgroup's 160 KiB of LDS.
+ *
+ * plspm_geodesic_enable: on != 0: every later plspm_bootstrap / plspm_bootstrap_device call on this handle also writes the geodesic records of its replicates
+ *   into a buffer of their own, indexed like the bootstrap's records -- and the assessment, PLSc and model-fit records as well, whether or not their own
+ *   switches are on; all of those, and the bootstrap's records, status and iteration counts, are bit for bit what they are without it.  factor: exactly
+ *   plspm_modelfit_enable's (the handle has one factor mask).  Off (the default): no launch, no allocation.  Permutation, stratified, cross-validation,
+ *   jackknife and group calls write none.
+ * plspm_geodesic_width: 2.
+ * plspm_geodesic_fit: the full-sample record, out [2]: the same four kernels on the moments of all uploaded rows and one solver problem (plspm_fit's);
+ *   *status (may be NULL): the record's status.
+ * plspm_geodesic_fetch: host copy of the records [first, first + count) of the last geodesic bootstrap: out [count*2], status [count] (may be NULL).
+ * plspm_geodesic_summary / plspm_geodesic_intervals: plspm_bootstrap_summary / plspm_bootstrap_intervals on the geodesic records (B: that bootstrap's, else
+ *   PLSPM_E_ARG): original [2] host, summary / out [2*6] host, *n_used (may be NULL).  Methods 0 (percentile), 1 (basic), 2 (bc); 3 (bca) is PLSPM_E_ARG.
+ * PLSPM_E_STATE from the last three without geodesic records on the handle (none written yet; whatever voids the PLSc records voids these; a jackknife leaves
+ * them alone).
+ */
+int plspm_geodesic_enable(plspm_model_t* m, int32_t on, const uint8_t* factor /*[L] or NULL = keep the handle's mask*/);
+int32_t plspm_geodesic_width(const plspm_model_t* m);
+int plspm_geodesic_fit(plspm_model_t* m, double* out, int32_t* status);
+int plspm_geodesic_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
+int plspm_geodesic_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
+int plspm_geodesic_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
 
 /*
  * ---- MICOM: permutation test of measurement invariance --------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// kernels_moments.h -- what the one-wave-per-problem kernels behind the solver open with (kernels_assess.h, kernels_plsc.h, kernels_modelfit.h, kernels_micom.h):
+// kernels_moments.h -- what the one-wave-per-problem kernels behind the solver open with (kernels_assess.h, kernels_plsc.h, kernels_modelfit.h, kernels_geodesic.h, kernels_micom.h):
 // where a problem's moment matrix lies, the per-MV statistics out of it, the record of a failed problem and the wave's LDS hand-over.
 #pragma once
 

@@ -145,7 +145,7 @@ struct plspm_model {
     // measurement-model assessment of a plain bootstrap's replicates (kernels_assess.h; plspm_assess_*): records [assess_B x (A + 2)] in a buffer of their own,
     // indexed by the replicate's position in the whole call
     bool assess_on = false;                  // plspm_assess_enable
-    Buf assess_rows, derived_fit;            // ... the replicates' records; the full-sample problem and its records of every stage (plspm_assess_fit, plspm_plsc_fit, plspm_modelfit_fit)
+    Buf assess_rows, derived_fit;            // ... the replicates' records; the full-sample problem and its records of every stage (plspm_assess_fit, plspm_plsc_fit, plspm_modelfit_fit, plspm_geodesic_fit)
     int64_t assess_B = 0;                    // ... the last plain bootstrap whose assessment records are on the handle (0: none)
     // consistent PLS of a plain bootstrap's replicates (kernels_plsc.h; plspm_plsc_*): records [plsc_B x (R + npairs + 2)] in a buffer of their own, indexed like
     // the assessment records, which are written whenever these are (the PLSc kernel reads them)
@@ -158,6 +158,11 @@ struct plspm_model {
     bool modelfit_on = false;                // plspm_modelfit_enable
     Buf modelfit_rows;                       // ... the replicates' records
     int64_t modelfit_B = 0;                  // ... the last plain bootstrap whose model-fit records are on the handle (0: none)
+    // geodesic discrepancy of a plain bootstrap's replicates (kernels_geodesic.h; plspm_geodesic_*): records [geodesic_B x 4] in a buffer of their own, indexed like
+    // the model-fit records, which are written whenever these are (the geodesic kernel reads their status); the factor mask is PLSc's
+    bool geodesic_on = false;                // plspm_geodesic_enable
+    Buf geodesic_rows;                       // ... the replicates' records
+    int64_t geodesic_B = 0;                  // ... the last plain bootstrap whose geodesic records are on the handle (0: none)
     // MICOM records of a permutation call's splits (kernels_micom.h; plspm_micom_*): records [micom_B x (3 L + 2)] in a buffer of their own, indexed by the
     // permutation's position in the call; the pooled inputs (u, the diagonal blocks of R_0; plspm_micom.hip micom_prepare) once per upload
     bool micom_on = false;                   // plspm_micom_enable
@@ -225,7 +230,7 @@ inline bool keeps_records(const BatchCall& c) { return c.kind == BatchCall::JACK
 inline bool pairs_problems(const BatchCall& c) { return c.kind == BatchCall::PERMUTATION; }
 // The handle kinds the two-group tests, the cross-validation, the jackknife, the assessment and MICOM cover.
 inline bool plain_metric(const plspm_model* m) { return !m->nonmetric && !m->categorical && !m->n_ind && !m->nmx_K && !m->stage1 && !m->stage2; }
-// (which plain bootstrap gets assessment, PLSc and model-fit records: plspm_derived.hip derived_begin)
+// (which plain bootstrap gets assessment, PLSc, model-fit and geodesic records: plspm_derived.hip derived_begin)
 
 // The records on a handle, and the one place that voids them.  A batch call voids whatever went with the bootstrap records it replaces (REC_ROWS itself only
 // when it writes the handle's own `rows`); plspm_bootstrap_store replaces the bootstrap records from the host; an upload voids everything.
@@ -236,7 +241,7 @@ inline void void_records(plspm_model* m, unsigned which) {
     if (which & REC_ASSESS) m->assess_B = 0;
     if (which & REC_MICOM) m->micom_B = 0;
     if (which & REC_JACK) m->jack_G = 0;
-    if (which & REC_PLSC) m->plsc_B = m->modelfit_B = 0;      // (the model-fit records go with the PLSc records they were computed from)
+    if (which & REC_PLSC) m->plsc_B = m->modelfit_B = m->geodesic_B = 0;      // (the model-fit and geodesic records go with the PLSc records they were computed from)
 }
 // (an entry point voids its own kind's records before it prepares the call -- plspm_cv_device REC_CV, plspm_jackknife_device REC_JACK -- and sets the count
 //  again behind the driver; so does plspm_bootstrap() with REC_ASSESS, which every one of its sub-batches voids here once more)

@@ -300,7 +300,7 @@ void plspm_model_destroy(plspm_model_t* m) {
                     m->nmw_maps.p, m->nmw_ints.p, m->nmw_vsum.p, m->zs.p, m->cd.p, m->cd1.p, m->codes.p, m->ind8.p, m->tab8.p, m->scl8.p, m->err2.p, m->pp_ctl.p, m->sk_partial.p, m->sk_flags.p, m->pair_tab.p, m->pair_scale.p, m->zs_stat.p,
                     m->perm_thr.p, m->perm_member.p, m->perm_io.p, m->strat_rows.p, m->strat_draws.p, m->strat_io.p, m->strat_u.p,
                     m->cv_fold.p, m->cv_thr.p, m->cv_idx.p, m->cv_off.p, m->cv_mom.p, m->cv_coef.p, m->cv_io.p, m->cv_pred.p, m->cv_tab.p,
-                    m->jack_rows.p, m->jack_status.p, m->jack_iters.p, m->jack_io.p, m->assess_rows.p, m->derived_fit.p, m->plsc_rows.p, m->plsc_side.p, m->plsc_mask.p, m->modelfit_rows.p, m->micom_rows.p, m->micom_pool.p, m->micom_io.p};
+                    m->jack_rows.p, m->jack_status.p, m->jack_iters.p, m->jack_io.p, m->assess_rows.p, m->derived_fit.p, m->plsc_rows.p, m->plsc_side.p, m->plsc_mask.p, m->modelfit_rows.p, m->geodesic_rows.p, m->micom_rows.p, m->micom_pool.p, m->micom_io.p};
     for (void* p : ptrs) if (p) plspm_dfree(p);
     for (void* p : m->blobs) if (p) plspm_dfree(p);
     if (m->h_stage) plspm_hfree(m->h_stage);

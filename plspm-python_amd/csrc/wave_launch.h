@@ -1,5 +1,5 @@
 // wave_launch.h -- host side: the one launch form of the kernels that give every problem of a batch one wave and a slice of dynamic LDS (assess_kernel,
-// plsc_kernel, modelfit_kernel: plspm_derived.hip; micom_kernel: plspm_micom.hip).
+// plsc_kernel, modelfit_kernel, geodesic_kernel: plspm_derived.hip; micom_kernel: plspm_micom.hip).
 #pragma once
 #include "host_internal.h"
 #include "kernels_moments.h"

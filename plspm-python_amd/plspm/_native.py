@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PLSPM_HIP_LIB", os.path.join(_HERE, "_lib", "libplspm
 ABI_VERSION = 4
 
 STATUS_OK, STATUS_NOT_CONVERGED, STATUS_SINGULAR, STATUS_NONFINITE = 0, 1, 2, 3
-STATUS_INADMISSIBLE = 4      # PLSc and model-fit records only (plspm_plsc_*, plspm_modelfit_*)
+STATUS_INADMISSIBLE = 4      # PLSc, model-fit and geodesic records only (plspm_plsc_*, plspm_modelfit_*, plspm_geodesic_*)
 KERNELS = {"resample": 0, "gram": 1, "solver": 2, "scores": 3, "pack": 4, "reduce": 5, "assess": 6}
 EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm_model_create", "plspm_model_destroy", "plspm_model_set_nonmetric", "plspm_model_set_categorical", "plspm_model_set_missing", "plspm_model_attach_second_stage", "plspm_model_set_incomplete_rows",
            "plspm_upload", "plspm_effect_pairs", "plspm_row_width", "plspm_row_stride", "plspm_fit", "plspm_bootstrap", "plspm_bootstrap_device", "plspm_bootstrap_summary",
@@ -35,6 +35,7 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_assess_enable", "plspm_assess_width", "plspm_assess_fit", "plspm_assess_fetch", "plspm_assess_summary", "plspm_assess_intervals",
            "plspm_plsc_enable", "plspm_plsc_width", "plspm_plsc_fit", "plspm_plsc_fetch", "plspm_plsc_summary", "plspm_plsc_intervals",
            "plspm_modelfit_enable", "plspm_modelfit_width", "plspm_modelfit_fit", "plspm_modelfit_fetch", "plspm_modelfit_summary", "plspm_modelfit_intervals",
+           "plspm_geodesic_enable", "plspm_geodesic_width", "plspm_geodesic_fit", "plspm_geodesic_fetch", "plspm_geodesic_summary", "plspm_geodesic_intervals",
            "plspm_micom_enable", "plspm_micom_width", "plspm_micom_fetch", "plspm_micom_summary", "plspm_micom_intervals", "plspm_micom_counts"]
 CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
 CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
@@ -127,9 +128,9 @@ def load():
     lib.plspm_jackknife_fetch.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.plspm_jackknife_stats.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_bootstrap_intervals.argtypes = [vp, vp, i64, i32, vp, vp, i32, dbl, vp, ctypes.POINTER(i64)]
-    # the four families of side records (assessment, PLSc, model fit, MICOM): one set of signatures; only the first three have a full-sample record
-    for family in ("assess", "plsc", "modelfit", "micom"):
-        getattr(lib, "plspm_%s_enable" % family).argtypes = [vp, i32, vp] if family in ("plsc", "modelfit") else [vp, i32]
+    # the five families of side records (assessment, PLSc, model fit, geodesic discrepancy, MICOM): one set of signatures; only MICOM has no full-sample record
+    for family in ("assess", "plsc", "modelfit", "geodesic", "micom"):
+        getattr(lib, "plspm_%s_enable" % family).argtypes = [vp, i32, vp] if family in ("plsc", "modelfit", "geodesic") else [vp, i32]
         getattr(lib, "plspm_%s_width" % family).restype = i32
         getattr(lib, "plspm_%s_width" % family).argtypes = [vp]
         if family != "micom":
@@ -672,6 +673,37 @@ class NativeModel:
     def modelfit_intervals(self, B, original, method="percentile", level=0.95):
         """``intervals`` on the model-fit records (plspm_modelfit_intervals; no bca): ([4, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
         return self._side_table("modelfit", "intervals", B, original, method, level)
+
+    def geodesic_enable(self, on=True, factor=None):
+        """Geodesic discrepancy (plspm_geodesic_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the record d_g_sat | d_g_est of every
+        replicate -- and the assessment, PLSc and model-fit records, which the geodesic kernel builds on; the bootstrap's own records do not change.
+        ``factor``: as in ``modelfit_enable`` (the handle has one factor mask)."""
+        mask = None
+        if factor is not None:
+            mask = np.ascontiguousarray(factor, dtype=np.uint8)
+            if mask.shape != (self.L,):
+                raise ValueError("factor must have one entry per latent variable")
+        self._check(self._lib.plspm_geodesic_enable(self._h, int(bool(on)), _ptr(mask) if mask is not None else None), "plspm_geodesic_enable")
+
+    @property
+    def geodesic_width(self):
+        return self._side_width("geodesic")
+
+    def geodesic_fit(self):
+        """The full-sample geodesic record (plspm_geodesic_fit): ([2] values, the record's status)."""
+        return self._side_fit("geodesic")
+
+    def geodesic_fetch(self, first=0, count=None):
+        """Host copy of the geodesic records [first, first + count) of the last geodesic bootstrap: (records [count, 2], status [count])."""
+        return self._side_fetch("geodesic", first, self.last_B - first if count is None else count)
+
+    def geodesic_summary(self, B, original):
+        """``summary`` on the geodesic records (plspm_geodesic_summary): ([2, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
+        return self._side_table("geodesic", "summary", B, original)
+
+    def geodesic_intervals(self, B, original, method="percentile", level=0.95):
+        """``intervals`` on the geodesic records (plspm_geodesic_intervals; no bca): ([2, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
+        return self._side_table("geodesic", "intervals", B, original, method, level)
 
     def micom_enable(self, on=True):
         """MICOM (plspm_micom_enable): every later ``permutation`` call also writes the record c | dmean | dlogvar [L each] of every permutation --

@@ -15,6 +15,10 @@ correlations; beta the PLSc path coefficients; the factor mask):
     d_uls             sum_{p<q} (r_pq - sigma_pq)^2 = 1/2 ||R - Sigma||_F^2            srmr    sqrt(2 d_uls / (P (P + 1)))
     record            srmr_sat | d_uls_sat | srmr_est | d_uls_est
     inadmissible      (status 4, NaN everywhere, not used) the PLSc record is, a column is constant, or a value is not finite
+    d_g               (``geodesic=True``; include/plspm_hip.h ``plspm_geodesic_*``) 1/2 sum_k (ln phi_k)^2 over the eigenvalues phi_k of
+                      R^-1 Sigma: the geodesic discrepancy, which weighs a residual by how well the data determine it and so need not agree with the
+                      other two.  Record d_g_sat | d_g_est; inadmissible where the model-fit record is, where R is singular (a Cholesky pivot not above
+                      1e-12), where Sigma is not positive definite (some phi_k <= 0), or where a value is not finite
 
 The test: the data are transformed once so that their correlation matrix is the implied one of the model under test (X~ = Z R^-1/2 Sigma^1/2), and
 the ordinary bootstrap runs on X~ with the model-fit kernel on; the observed discrepancy is held against the replicates'.  ``_model_fit`` below is
@@ -35,6 +39,8 @@ from plspm.scheme import Scheme
 from plspm.weights import NumericalConditionError
 
 STATISTICS = ["srmr", "d_uls"]
+GEODESIC = "d_g"
+GEODESIC_PIVOT_MIN = 1e-12      # a Cholesky pivot of R (unit diagonal) that is not above this: R is singular, d_G is inadmissible
 FIT_COLUMNS = ["saturated", "estimated", "hi95", "hi99", "p.value"]
 MODELS = ("saturated", "estimated")
 CONDITION_RTOL = 1e-10          # a correlation matrix whose smallest eigenvalue is not above this share of its largest has no Bollen-Stine transformation
@@ -100,6 +106,50 @@ def _model_fit(R, plsc_out, blocks, C, factor):
     return out
 
 
+def _geodesic(R, implied):
+    """The eigenvalues behind d_G of one implied matrix, the mirror of csrc/geodesic_core.h in NumPy: (status, phi) with phi the eigenvalues of R^-1 implied
+    in ascending order, computed as those of the symmetric G^-1 implied G^-T with R = G G' (cholesky, two triangular solves, eigvalsh).  Status 4 (inadmissible)
+    where a Cholesky pivot of R is not above GEODESIC_PIVOT_MIN (phi is None then), where some phi_k is not positive, and where something is not finite."""
+    R, implied = np.asarray(R, dtype=np.float64), np.asarray(implied, dtype=np.float64)
+    if not (np.all(np.isfinite(R)) and np.all(np.isfinite(implied))):
+        return STATUS_INADMISSIBLE, None
+    try:
+        G = np.linalg.cholesky(R)
+    except np.linalg.LinAlgError:
+        return STATUS_INADMISSIBLE, None
+    if not np.all(np.diag(G) ** 2 > GEODESIC_PIVOT_MIN):
+        return STATUS_INADMISSIBLE, None
+    half = np.linalg.solve(G, implied)                       # G^-1 Sigma
+    C = np.linalg.solve(G, half.T)                           # G^-1 (G^-1 Sigma)' = G^-1 Sigma G^-T
+    phi = np.linalg.eigvalsh(0.5 * (C + C.T))
+    admissible = np.all(np.isfinite(phi)) and np.all(phi > 0) and np.isfinite(_d_g(phi))
+    return (STATUS_OK if admissible else STATUS_INADMISSIBLE), phi
+
+
+def _d_g(phi):
+    """1/2 sum (ln phi_k)^2."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return 0.5 * float(np.sum(np.log(phi) ** 2))
+
+
+def _geodesic_fit(R, fit):
+    """The geodesic record of one data set from ``_model_fit``'s dict on it: {"status", "record" [d_g_sat, d_g_est], "phi": {model: eigenvalues}}.  Status: the
+    model fit's, or 4 with NaN in both values by ``_geodesic``'s rules for either model."""
+    out = {"status": fit["status"], "record": np.full(2, np.nan), "phi": {}}
+    if fit["status"] == STATUS_INADMISSIBLE:
+        return out
+    values = []
+    for model in MODELS:
+        status, phi = _geodesic(R, fit["implied"][model])
+        out["phi"][model] = phi
+        if status != STATUS_OK:
+            out["status"] = STATUS_INADMISSIBLE
+        values.append(np.nan if phi is None else _d_g(phi))
+    if out["status"] != STATUS_INADMISSIBLE:
+        out["record"] = np.array(values)
+    return out
+
+
 def _sqrt_pair(M, what):
     """(M^1/2, M^-1/2) of a correlation matrix by its eigendecomposition; NumericalConditionError unless its smallest eigenvalue is above CONDITION_RTOL of
     its largest."""
@@ -136,16 +186,21 @@ def _plsc_out_of_record(record, status, native, cm):
 
 class ModelFit:
     """``ModelFit(data, config, scheme=Scheme.CENTROID, iterations=5000, seed=None, factors=(), null="estimated", fit_iterations=100, tolerance=1e-6,
-    device_id=0, processes=1)`` -- ``iterations`` Bollen-Stine bootstrap replicates (0: the values without inference); ``factors``: the names of the LVs
+    device_id=0, processes=1, geodesic=False)`` -- ``iterations`` Bollen-Stine bootstrap replicates (0: the values without inference); ``factors``: the names of the LVs
     that are common factors (``()``: none, the composite model plain ``Plspm`` estimates; None: every Mode-A block of two items or more, PLSc's default);
     ``null``: the model whose exact fit is tested, "estimated" or "saturated".
 
     ``fit()``: index srmr, d_uls; columns saturated, estimated (the observed values), hi95, hi99 (the 95 % and 99 % quantiles of the ``null`` model's
     statistic under exact fit) and p.value ((1 + #{d* >= d_obs}) / (1 + used): never zero).  ``implied(model)``: the P x P implied correlations.
-    ``records()``, ``used()``, ``inadmissible()``, ``seed()``, ``replicates()``, ``status()``."""
+    ``records()``, ``used()``, ``inadmissible()``, ``seed()``, ``replicates()``, ``status()``.
+
+    ``geodesic=True`` adds the geodesic discrepancy: a third row ``d_g`` of ``fit()`` with the same five columns, from records of its own --
+    ``records(measure="d_g")`` [iterations, 2] d_g_sat | d_g_est, ``used(measure="d_g")``, ``inadmissible(measure="d_g")``: a replicate whose implied matrix
+    is not positive definite counts for srmr and d_uls and not for d_g.  A full sample that is inadmissible for d_g alone raises NumericalConditionError
+    when replicates are asked for (there is nothing to hold them against); with ``iterations=0`` its row is NaN."""
 
     def __init__(self, data: pd.DataFrame, config: c.Config, scheme: Scheme = Scheme.CENTROID, iterations: int = 5000, seed: int = None, factors=(),
-                 null: str = "estimated", fit_iterations: int = 100, tolerance: float = 0.000001, device_id: int = 0, processes: int = 1):
+                 null: str = "estimated", fit_iterations: int = 100, tolerance: float = 0.000001, device_id: int = 0, processes: int = 1, geodesic: bool = False):
         assert tolerance > 0
         assert scheme in Scheme
         if processes > 1:
@@ -167,10 +222,16 @@ class ModelFit:
         native, cm = whole.native, whole.compiled
         self._cm, self._null, self._iterations = cm, null, int(iterations)
         self._mask = _factor_mask(cm, factors)
-        native.modelfit_enable(True, self._mask)
+        self._geodesic = bool(geodesic)
+        self._g_observed, self._g_status, self._g_records, self._g_used = np.full(2, np.nan), STATUS_OK, None, 0
+        self._g_critical = np.full((2, 2), np.nan)
+        enable = native.geodesic_enable if self._geodesic else native.modelfit_enable
+        enable(True, self._mask)
         try:
             self._observed, self._status = native.modelfit_fit()
             plsc_record, plsc_status = native.plsc_fit()
+            if self._geodesic:
+                self._g_observed, self._g_status = native.geodesic_fit()
         except _native.NativeBackendError as err:
             raise NotImplementedError("no model fit on this handle: " + str(err))
         X = observations.values[:, cm.col_index].astype(np.float64)
@@ -183,11 +244,14 @@ class ModelFit:
             return
         if self._status == STATUS_INADMISSIBLE or self._mirror["status"] == STATUS_INADMISSIBLE:
             raise NumericalConditionError("the full-sample model fit is inadmissible (status 4): there is no implied correlation matrix to test against")
+        if self._geodesic and self._g_status == STATUS_INADMISSIBLE:
+            raise NumericalConditionError("the full-sample geodesic discrepancy d_g is inadmissible (status 4): the indicator correlation matrix is singular or "
+                                          "an implied correlation matrix is not positive definite; srmr and d_uls are available with geodesic=False")
         tilde = observations.copy().astype(np.float64)
         tilde.iloc[:, cm.col_index] = _bollen_stine(X, self._mirror["implied"][null])
         self._transformed = Estimator(config).run(calculator, tilde, want_scores=False)
         second = self._transformed.native
-        second.modelfit_enable(True, self._mask)
+        (second.geodesic_enable if self._geodesic else second.modelfit_enable)(True, self._mask)
         if seed is None:
             self._seed = int.from_bytes(os.urandom(8), "little")
         second.bootstrap_device(self._iterations, self._seed, 0)
@@ -196,6 +260,11 @@ class ModelFit:
         for column, level in enumerate((0.90, 0.98)):
             table, self._used = second.modelfit_intervals(self._iterations, original, "percentile", level)
             self._critical[:, column] = table[:, 1]
+        if self._geodesic:
+            self._g_records = second.geodesic_fetch(0, self._iterations)
+            for column, level in enumerate((0.90, 0.98)):
+                table, self._g_used = second.geodesic_intervals(self._iterations, self._g_observed, "percentile", level)
+                self._g_critical[:, column] = table[:, 1]
 
     def status(self) -> int:
         """Status of the full-sample record (0: fine; 4: inadmissible, every value NaN)."""
@@ -213,6 +282,16 @@ class ModelFit:
             ok = self.replicates()
             table[:, 2:4] = self._critical[first:first + 2]
             table[:, 4] = (1.0 + np.count_nonzero(ok[:, first:first + 2] >= obs[first:first + 2], axis=0)) / (1.0 + ok.shape[0])
+        if self._geodesic:
+            row = np.full((1, 5), np.nan)
+            row[0, :2] = self._g_observed
+            if self._g_records is not None:
+                which = MODELS.index(self._null)
+                records, status = self._g_records
+                ok = records[status == STATUS_OK]
+                row[0, 2:4] = self._g_critical[which]
+                row[0, 4] = (1.0 + np.count_nonzero(ok[:, which] >= self._g_observed[which])) / (1.0 + ok.shape[0])
+            return pd.DataFrame(np.vstack([table, row]), index=STATISTICS + [GEODESIC], columns=FIT_COLUMNS)
         return pd.DataFrame(table, index=STATISTICS, columns=FIT_COLUMNS)
 
     def implied(self, model="estimated") -> pd.DataFrame:
@@ -230,24 +309,33 @@ class ModelFit:
         """The LVs taken as common factors."""
         return [lv for lv, f in zip(self._cm.lvs, self._mask) if f]
 
-    def records(self):
-        """(records [iterations, 4], status [iterations]) of the Bollen-Stine replicates: srmr_sat | d_uls_sat | srmr_est | d_uls_est."""
-        if self._records is None:
+    def _is_geodesic(self, measure) -> bool:
+        if measure is not None and measure not in STATISTICS + [GEODESIC]:
+            raise ValueError("measure must be one of %s" % ", ".join(STATISTICS + [GEODESIC]))
+        if measure == GEODESIC and not self._geodesic:
+            raise ValueError("no d_g on this ModelFit: call it with geodesic=True")
+        return measure == GEODESIC
+
+    def records(self, measure=None):
+        """(records [iterations, 4], status [iterations]) of the Bollen-Stine replicates: srmr_sat | d_uls_sat | srmr_est | d_uls_est;
+        ``measure="d_g"``: the geodesic records [iterations, 2] d_g_sat | d_g_est and their status."""
+        records = self._g_records if self._is_geodesic(measure) else self._records
+        if records is None:
             raise Exception("No replicates: ModelFit was called with iterations=0")
-        return self._records
+        return records
 
     def replicates(self):
         """The used replicates' records [n_used, 4]."""
         records, status = self.records()
         return records[status == STATUS_OK]
 
-    def used(self) -> int:
-        """Number of replicates behind hi95, hi99 and p.value."""
-        return self._used
+    def used(self, measure=None) -> int:
+        """Number of replicates behind hi95, hi99 and p.value (of srmr and d_uls; ``measure="d_g"``: of d_g)."""
+        return self._g_used if self._is_geodesic(measure) else self._used
 
-    def inadmissible(self) -> int:
-        """Number of replicates with status 4."""
-        return int(np.count_nonzero(self.records()[1] == STATUS_INADMISSIBLE))
+    def inadmissible(self, measure=None) -> int:
+        """Number of replicates with status 4 (``measure="d_g"``: in the geodesic records)."""
+        return int(np.count_nonzero(self.records(measure)[1] == STATUS_INADMISSIBLE))
 
     def seed(self):
         return self._seed
