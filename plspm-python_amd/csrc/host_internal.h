@@ -1,5 +1,5 @@
 // host_internal.h -- what the translation units of libplspm_hip.so share on the HOST side (round 4: the former one-file host is split by
-// concern so that the units compile side by side): plspm_hip.hip (allocator, handles, options, upload, staging), plspm_fit.hip (fp64 Gram,
+// concern so that the units compile side by side): plspm_hip.hip (allocator, handles, options as options.h tabulates them, upload, staging), plspm_fit.hip (fp64 Gram,
 // solvers, non-metric iteration, single fit, operator seam), plspm_gram_i8.hip (digit planes + the int8 Gram of bootstrap batches),
 // plspm_bootstrap.hip (batch driver phase by phase as batch_route.h plans it, record download, summaries), plspm_derived.hip (the records derived from a plain bootstrap's replicates),
 // plspm_group.cpp (multi-GPU groups).  Every device kernel lives in

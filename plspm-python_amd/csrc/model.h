@@ -11,6 +11,7 @@
 #include "../../include/plspm_hip_test.h"
 #include "gram_route.h"
 #include "group_route.h"
+#include "options.h"
 
 inline thread_local std::string g_create_error;
 
@@ -48,11 +49,32 @@ struct plspm_model {
     int *d_boff = nullptr, *d_lvof = nullptr, *d_mode = nullptr, *d_chol_off = nullptr, *d_eff_from = nullptr, *d_eff_to = nullptr;
     int *d_pred_off = nullptr, *d_pred_idx = nullptr, *d_succ_off = nullptr, *d_succ_idx = nullptr;
     uint8_t* d_C = nullptr;
-    double* d_shift = nullptr;
     int64_t N = 0;
     double* d_Xa = nullptr;
-    // grow-only device scratch
-    struct Buf { void* p = nullptr; size_t cap = 0; };
+    // A device block and its owner: the block goes back to the allocator with the Buf, i.e. with `delete m` for a member of the handle -- behind the
+    // synchronisation of the handle's streams in plspm_model_destroy, as the allocator asks.  Grow-only through ensure() below.
+    struct Buf {
+        void* p = nullptr;
+        size_t cap = 0;
+        Buf() = default;
+        Buf(const Buf&) = delete;
+        Buf& operator=(const Buf&) = delete;
+        Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+        Buf& operator=(Buf&& o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+        ~Buf() { reset(); }
+        void reset() { if (p) plspm_dfree(p); p = nullptr; cap = 0; }
+        // at least `bytes` on the CURRENT device; a block that is too small is given back first, so the caller has made sure that nothing in flight uses it
+        hipError_t reserve(size_t bytes) {
+            if (bytes <= cap) return hipSuccess;
+            reset();
+            const hipError_t e = plspm_dmalloc(&p, bytes);
+            if (e == hipSuccess) cap = bytes;
+            return e;
+        }
+    };
+    // (a member x_buf owns the block that the typed pointer d_x points at: the other units, and the kernels' descriptors, read the pointer)
+    Buf shift_buf;
+    double* d_shift = nullptr;
     Buf ent, nent, gram, gram_partial, rows, status, iters, gS, gsmall, fitout, idx, err, ghist, nmstate, nmpartial, nmactive, nmlist, gK16, sum_buf, cols;
     int nonmetric = 0;           // Scale.NUM / Scale.RAW data: population-standardised MVs, score-based stop rule
     bool codes_valid = false;    // m->codes holds the category codes of the uploaded rows (nm_conv_codes_kernel)
@@ -74,13 +96,13 @@ struct plspm_model {
     int Pm = 0, cmax = 1, kmv = 1;
     std::vector<int> mv_off, mv_kind, lmv_off, mv_lv, no_chol, mv_base, mv_base2, lmv2_off;
     int *d_mv_off = nullptr, *d_mv_kind = nullptr, *d_lmv_off = nullptr, *d_mv_lv = nullptr, *d_no_chol = nullptr, *d_mv_base = nullptr, *d_mv_base2 = nullptr, *d_lmv2_off = nullptr;
-    Buf gSm;
+    Buf gSm, mv_base2_buf, lmv2_off_buf;      // (the last two: d_mv_base2, d_lmv2_off of an attached second stage)
     // metric data with missing values: Pg = P + n_ind device columns (data | missing indicators); PA / T describe the Gram of
     // those, PAs / Ts the P-column moment matrix the solver reads (impute_collapse maps one to the other).  Pg == P otherwise.
     int Pg = 0, PAs = 0, Ts = 0, n_ind = 0;
     std::vector<int> ind_of;
     int* d_ind_of = nullptr;
-    Buf gram2;
+    Buf gram2, ind_of_buf;
     // two-stage higher order constructs (solver_hoc.h): `stage2` of a data-holding handle / `stage1` of its attached second stage
     plspm_model* stage2 = nullptr;
     plspm_model* stage1 = nullptr;
@@ -96,6 +118,7 @@ struct plspm_model {
     int nmx_K = 0, nmx_raw = 0;
     double *d_Xk = nullptr, *d_Mk = nullptr;
     int* d_rowid = nullptr;
+    Buf Xk_buf, Mk_buf, rowid_buf;      // (plspm_hip.hip drop_incomplete_rows)
     int* h_flag = nullptr;        // pinned: active-problem counter of the non-metric iteration
     hipEvent_t ev_flag = nullptr;
     void* h_stage = nullptr;      // pinned host staging for plspm_fit results
@@ -105,9 +128,9 @@ struct plspm_model {
     Buf xa, up_raw, up_ci, up_partial;   // resident matrix (d_Xa points into `xa` while data are uploaded) and the upload staging
     int64_t rows_B = 0;           // number of valid records in `rows` (0: none)
     bool err_clean = false;       // the device error word is zero and no call since could have raised it (plspm_detail_bootstrap; batch_route.h batch_may_raise)
-    // launch-geometry options (plspm_model_set_option); validated there, never read from the environment
-    struct Tune { int wide_nw = 4, fit_chunks = 0, conv_pass = 0, conv_gy = 0, nm_threads = 0, solver_threads = 128, scores_tile = 0, gram_lds_kb = 0;
-                  int gram_path = 0, i8_slices = 0, i8_min_batch = 1, i8_waves = 8, i8_rt = 0, i8_short = -1, i8_cus = 0, upload_direct = 0, i8_dma = 0, i8_variant = -1, solver_rows = 1, solver_wave = 1, solver_quad = 1, nm_counts8 = 1, nm_fast_lds = 1, nm_k16 = 1, nm_codes = 1, i8_ind = 1, i8_shape = 16, resample_aux = 0, i8_sched = 0, i8_priv = 1, boot_chunks = 0, boot_ratio = 60, boot_align = 0, i8_persist = 0, i8_min_slices = 0, i8_nostore = 0, nm_wave = 1, nm_live = 1, nm_mfma = 1, nm_direct16 = 1, i8_nibbles = 1, nm_wave16 = 1, nm_verify_rows = 0, nm_bound_shift = 0, wide_ring = 4, nm_subset = 4, nm_cat_one = 1, nm_cpl = 0, nm_c10 = 1, nm_vlong = 1, strat_rows = 0, boot_pass = 0; } tune;
+    // launch-geometry options (plspm_model_set_option): defaults, accepted values and what a change voids in options.h
+    using Tune = plspm::Tune;
+    Tune tune;
     // int8 digit-plane Gram of bootstrap batches (kernels_gram_i8.h): per data set the digit planes `zs` of all pair products and the
     // pair tables (p, q, k, slot in the packed matrix | 2^-k); per call the dense int8 multiplicities `cd`
     Buf zs, cd, cd1, err2, pair_tab, pair_scale, zs_stat, codes, ind8, tab8, scl8, pp_ctl;      // pp_ctl: tile counters of the persistent Gram (kernels_gram_i8p.h GramI8PPCtl)
@@ -249,6 +272,18 @@ inline void void_records(plspm_model* m, const BatchCall& c) {
     if (!keeps_records(c)) void_records(m, REC_CV | REC_ASSESS | REC_PLSC | REC_MICOM | (c.rows_out ? 0u : REC_ROWS));
 }
 
+// What is derived from the resident rows, and the one place that voids it: the tiled copy, the category codes and indicator bytes, the digit planes and their
+// statistics.  replaced: plspm_upload brought new rows -- the records, the MICOM pool and an attached second stage's codes describe the old ones and go as well.
+// plspm_model_set_incomplete_rows rewrote some rows in place and voids none of those: it takes Scale.NUM handles outside a two-stage pair only, which have no
+// second stage and, not being plain metric, no MICOM pool and no records but the bootstrap's own.  That those (REC_ROWS) survive the call is inherited behaviour.
+inline void void_resident(plspm_model* m, bool replaced) {
+    m->Xt_valid = false; m->codes_valid = false; m->ind8_valid = false; m->zs_valid = false; m->zs_stats_ready = false;
+    if (!replaced) return;
+    if (m->stage2) { m->stage2->codes_valid = false; m->stage2->ind8_valid = false; }
+    void_records(m, REC_ALL);
+    m->micom_pool_valid = false;
+}
+
 // The batch driver (plspm_bootstrap.hip): enqueue the call's problems on the handle's stream.  No host synchronisation for metric models.
 int plspm_detail_bootstrap(plspm_model* m, BatchCall& call);
 // plspm_group.cpp: a handle that is destroyed while bound to a group takes the group's hold on every handle with it.
@@ -302,10 +337,8 @@ inline int fail(plspm_model* m, int code, const std::string& msg) {
 
 inline int ensure(plspm_model* m, plspm_model::Buf& b, size_t bytes) {
     if (bytes <= b.cap) return 0;
-    if (b.p) { HIPCHK(m, hipStreamSynchronize(m->stream)); plspm_dfree(b.p); }     // nothing of this handle may still be using the old block
-    b.p = nullptr; b.cap = 0;
-    HIPCHK(m, plspm_dmalloc(&b.p, bytes));
-    b.cap = bytes;
+    if (b.p) HIPCHK(m, hipStreamSynchronize(m->stream));     // nothing of this handle may still be using the old block
+    HIPCHK(m, b.reserve(bytes));      // (plspm_group.cpp calls reserve itself: it has synchronised every stream of the group, and its errors are the group's)
     return 0;
 }
 

@@ -224,15 +224,6 @@ struct FirstError {
     void nccl(ncclResult_t n, const char* what) { if (n != ncclSuccess && !code) set(-(1000 + (int)n), std::string(what) + g_rccl.GetErrorString(n)); }
 };
 
-int grow(plspm_group* g, plspm_model::Buf& b, size_t bytes) {
-    if (bytes <= b.cap) return 0;
-    if (b.p) plspm_dfree(b.p);                     // (the caller synchronised every stream of the group)
-    b.p = nullptr; b.cap = 0;
-    GHIP(g, plspm_dmalloc(&b.p, bytes));
-    b.cap = bytes;
-    return 0;
-}
-
 int sync_all(plspm_group* g) {
     for (auto& l : g->loc) {
         GHIP(g, hipSetDevice(l.m->device));
@@ -255,12 +246,11 @@ static void group_release(plspm_group* g) {
     for (auto& l : g->loc) {
         hipSetDevice(l.m->device);
         for (int s = 0; s < 2; ++s) {
-            if (l.send[s].p) plspm_dfree(l.send[s].p);
-            if (l.recv[s].p) plspm_dfree(l.recv[s].p);
+            l.send[s].reset(); l.recv[s].reset();
             for (auto& e : l.computed[s]) if (e) hipEventDestroy(e);
             if (l.gathered[s]) hipEventDestroy(l.gathered[s]);
         }
-        if (l.bcast.p) { plspm_dfree(l.bcast.p); l.bcast.p = nullptr; l.bcast.cap = 0; }
+        l.bcast.reset();
         if (l.d_word) plspm_dfree(l.d_word);
         if (l.h_word) plspm_hfree(l.h_word);
         if (l.cstream) plspm_stream_release(l.cstream);
@@ -348,7 +338,7 @@ int reserve_slot(plspm_group* g, int s, const GroupPlan& p) {
     g->pending[0] = g->pending[1] = false; g->last_slot = -1;
     for (auto& l : g->loc) {
         GHIP(g, hipSetDevice(l.m->device));
-        for (int k = 0; k < 2; ++k) if ((rc = grow(g, l.send[k], p.send_bytes)) || (rc = grow(g, l.recv[k], p.recv_bytes))) return rc;
+        for (int k = 0; k < 2; ++k) { GHIP(g, l.send[k].reserve(p.send_bytes)); GHIP(g, l.recv[k].reserve(p.recv_bytes)); }      // (reserve gives the old block back as it is: sync_all above)
     }
     return 0;
 }
@@ -827,7 +817,7 @@ int plspm_group_summary(plspm_group_t* g, const double* original, double* summar
         // broadcast -- every rank makes this call (as with the all-gather, where every rank computed the same table from its own copy)
         const int R = plspm_row_width(l.m);
         const size_t words = 2 + (size_t)R * 6, bytes = words * sizeof(double);
-        if (l.bcast.cap < bytes) { GHIP(g, hipStreamSynchronize(l.cstream)); int grc = grow(g, l.bcast, bytes); if (grc) return grc; }
+        if (l.bcast.cap < bytes) { GHIP(g, hipStreamSynchronize(l.cstream)); GHIP(g, l.bcast.reserve(bytes)); }
         std::vector<double> host(words, 0.0);
         int rc0 = 0;
         if (g->first_rank == 0) {

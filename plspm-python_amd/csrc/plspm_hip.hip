@@ -1,6 +1,6 @@
 // libplspm_hip.so -- MI355X (gfx950 / CDNA4) backend for the PLS-PM weight solver + bootstrap hot path.
 // C-ABI: include/plspm_hip.h.  Design, data layout and per-kernel rooflines: DESIGN.md.
-// This unit: caching allocator, stream cache, handles (create / destroy / options / model variants), upload, pinned staging, kernel timing.
+// This unit: caching allocator, stream cache, handles (create / destroy / options as options.h tabulates them / model variants), upload, pinned staging, kernel timing.
 // The other host units: plspm_fit.hip, plspm_gram_i8.hip, plspm_bootstrap.hip, plspm_group.cpp (host_internal.h names the seams).
 #include "host_internal.h"
 
@@ -163,9 +163,7 @@ void set_geometry(plspm_model* m) {
 
 // Side tables of plspm_model_set_incomplete_rows: freed (and nulled) on every re-upload and on a failed set call.
 static void drop_incomplete_rows(plspm_model* m) {
-    if (m->d_Xk) plspm_dfree(m->d_Xk);
-    if (m->d_Mk) plspm_dfree(m->d_Mk);
-    if (m->d_rowid) plspm_dfree(m->d_rowid);
+    m->Xk_buf.reset(); m->Mk_buf.reset(); m->rowid_buf.reset();
     m->d_Xk = m->d_Mk = nullptr; m->d_rowid = nullptr; m->nmx_K = 0;
 }
 
@@ -200,10 +198,12 @@ static int upload_blob(plspm_model* m, int slot, const std::vector<BlobPart>& pa
 template <class Tv> static BlobPart blob_part(Tv** dst, const std::vector<Tv>& v) { return BlobPart{(void**)dst, v.data(), v.size() * sizeof(Tv)}; }
 
 template <class Tv>
-static int upload_vec(plspm_model* m, Tv** dst, const std::vector<Tv>& v) {
+static int upload_vec(plspm_model* m, plspm_model::Buf& own, Tv** dst, const std::vector<Tv>& v) {
     const size_t bytes = std::max<size_t>(1, v.size()) * sizeof(Tv);
-    if (*dst) { HIPCHK(m, hipStreamSynchronize(m->stream)); plspm_dfree(*dst); *dst = nullptr; }      // a repeated call replaces its block
-    HIPCHK(m, plspm_dmalloc((void**)dst, bytes));
+    *dst = nullptr;
+    if (own.p) { HIPCHK(m, hipStreamSynchronize(m->stream)); own.reset(); }      // a repeated call replaces its block
+    HIPCHK(m, own.reserve(bytes));
+    *dst = (Tv*)own.p;
     // (on the handle's stream: its descriptor blocks travel there without a host wait, and a copy on the null stream is not ordered behind them)
     if (!v.empty()) { HIPCHK(m, hipMemcpyAsync(*dst, v.data(), v.size() * sizeof(Tv), hipMemcpyHostToDevice, m->stream)); HIPCHK(m, hipStreamSynchronize(m->stream)); }
     return 0;
@@ -277,7 +277,8 @@ plspm_model_t* plspm_model_create(int32_t P, int32_t L, const int32_t* block_off
                         blob_part(&m->d_eff_from, m->eff_from), blob_part(&m->d_eff_to, m->eff_to), blob_part(&m->d_C, m->C), blob_part(&m->d_pred_off, m->pred_off),
                         blob_part(&m->d_pred_idx, m->pred_idx), blob_part(&m->d_succ_off, m->succ_off), blob_part(&m->d_succ_idx, m->succ_idx)}))
         return bail("descriptor upload failed");
-    if (plspm_dmalloc((void**)&m->d_shift, sizeof(double) * P) != hipSuccess) return bail("hipMalloc failed");
+    if (m->shift_buf.reserve(sizeof(double) * P) != hipSuccess) return bail("hipMalloc failed");
+    m->d_shift = (double*)m->shift_buf.p;
     if (plspm_hmalloc((void**)&m->h_flag, 64) != hipSuccess || hipEventCreateWithFlags(&m->ev_flag, hipEventDisableTiming) != hipSuccess)
         return bail("pinned flag / event creation failed");
     return m;
@@ -292,16 +293,7 @@ void plspm_model_destroy(plspm_model_t* m) {
     if (m->aux) hipStreamSynchronize(m->aux);
     if (m->stream) hipStreamSynchronize(m->stream);
     prof_collect(m);
-    // (the descriptor arrays d_boff ... d_lv_cols are parts of the blobs below, not blocks of their own)
-    void* ptrs[] = {m->d_shift, m->xa.p, m->up_raw.p, m->up_ci.p, m->up_partial.p, m->scores.p,
-                    m->d_mv_base2, m->d_lmv2_off, m->gSm.p, m->d_ind_of, m->gram2.p, m->pseudo.p, m->d_Xk, m->d_Mk, m->d_rowid, m->dcnt.p, m->ctable.p, m->Xt.p,
-                    m->ent.p, m->nent.p, m->gram.p, m->gram_partial.p, m->rows.p, m->status.p, m->iters.p, m->gS.p, m->gsmall.p,
-                    m->fitout.p, m->idx.p, m->err.p, m->ghist.p, m->nmstate.p, m->nmpartial.p, m->nmactive.p, m->nmlist.p, m->gK16.p, m->sum_buf.p, m->cols.p,
-                    m->nmw_maps.p, m->nmw_ints.p, m->nmw_vsum.p, m->zs.p, m->cd.p, m->cd1.p, m->codes.p, m->ind8.p, m->tab8.p, m->scl8.p, m->err2.p, m->pp_ctl.p, m->sk_partial.p, m->sk_flags.p, m->pair_tab.p, m->pair_scale.p, m->zs_stat.p,
-                    m->perm_thr.p, m->perm_member.p, m->perm_io.p, m->strat_rows.p, m->strat_draws.p, m->strat_io.p, m->strat_u.p,
-                    m->cv_fold.p, m->cv_thr.p, m->cv_idx.p, m->cv_off.p, m->cv_mom.p, m->cv_coef.p, m->cv_io.p, m->cv_pred.p, m->cv_tab.p,
-                    m->jack_rows.p, m->jack_status.p, m->jack_iters.p, m->jack_io.p, m->assess_rows.p, m->derived_fit.p, m->plsc_rows.p, m->plsc_side.p, m->plsc_mask.p, m->modelfit_rows.p, m->geodesic_rows.p, m->micom_rows.p, m->micom_pool.p, m->micom_io.p};
-    for (void* p : ptrs) if (p) plspm_dfree(p);
+    // every Buf member gives its block back with `delete m` below; the descriptor arrays d_boff ... d_lv_cols are parts of the blobs, not blocks of their own
     for (void* p : m->blobs) if (p) plspm_dfree(p);
     if (m->h_stage) plspm_hfree(m->h_stage);
     if (m->h_pin) plspm_hfree(m->h_pin);
@@ -347,7 +339,8 @@ int plspm_upload(plspm_model_t* m, const double* X, int64_t N, int32_t src_cols,
     if (m->aux) HIPCHK(m, hipStreamSynchronize(m->aux));
     HIPCHK(m, hipStreamSynchronize(m->stream));
     // whatever was resident is gone from here on (a failed upload leaves an empty, re-usable handle)
-    m->N = 0; m->d_Xa = nullptr; m->Xt_valid = false; m->codes_valid = false; m->ind8_valid = false; if (m->stage2) { m->stage2->codes_valid = false; m->stage2->ind8_valid = false; } void_records(m, REC_ALL); m->micom_pool_valid = false; m->zs_valid = false; m->zs_stats_ready = false;
+    m->N = 0; m->d_Xa = nullptr;
+    void_resident(m, true);
     drop_incomplete_rows(m);
     // persistent grow-only buffers: a repeated upload of the same shape allocates nothing
     const size_t raw_bytes = (size_t)N * src_cols * sizeof(double);
@@ -407,16 +400,33 @@ int plspm_upload(plspm_model_t* m, const double* X, int64_t N, int32_t src_cols,
     // X may be released by the caller on return: the small path has copied it into the staging area (the pack kernels run behind the copies
     // on the handle's stream, like everything a later call enqueues); the chunked path waits for its last DMA
     if (!fast_upload) HIPCHK(m, hipStreamSynchronize(m->stream));
-    if (raw_bytes > ((size_t)1 << 30)) {                 // do not keep a multi-GB staging copy alive next to the resident matrix
-        plspm_dfree(m->up_raw.p);
-        m->up_raw.p = nullptr; m->up_raw.cap = 0;
-    }
+    if (raw_bytes > ((size_t)1 << 30)) m->up_raw.reset();      // do not keep a multi-GB staging copy alive next to the resident matrix
     m->d_Xa = d_Xa;
     m->N = N;
     return 0;
 }
 
 }  // extern "C"
+
+// ---- options: names, accepted values and effects of the settable ones in options.h kOptions
+// measured-neutral / slower kernel variants and timing probes exist in the experiments build only (make -C plspm-python_amd/csrc experiments)
+#ifdef PLSPM_I8_EXPERIMENTS
+static constexpr bool kExperiments = true;
+#else
+static constexpr bool kExperiments = false;
+#endif
+// The names plspm_model_get_option answers beside the options themselves: what the last call did, and two facts about the handle and the build.
+struct ReadOut { const char* name; int32_t (*get)(const plspm_model*); };
+#define LAST(what) {"last_" #what, [](const plspm_model* m) -> int32_t { return m->last_##what; }}
+static const ReadOut kReadOuts[] = {
+    {"last_i8_slices", [](const plspm_model* m) -> int32_t { return m->zs_valid ? m->zs_S : 0; }},
+    {"last_i8_ratio", [](const plspm_model* m) -> int32_t { return (m->zs_valid && m->zs_ratio < 9e18) ? (int32_t)(int64_t)m->zs_ratio : 0; }},      // floor of the smallest sum|z| / max|z| (automatic plane count)
+    LAST(i8_rt), LAST(i8_short), LAST(i8_mt), LAST(i8_nibbles), LAST(i8_dma), LAST(i8_priv), LAST(i8_persist), LAST(gram_path), LAST(solver), LAST(boot_passes), LAST(strat_rows), LAST(micom_layout),
+    LAST(nm_codes), LAST(nm_mfma), LAST(nm_direct16), LAST(nm_one), LAST(nm_exact), LAST(nm_wave), LAST(nm_wave16), LAST(nm_flagged), LAST(nm_replayed),
+    {"boot_round_units", [](const plspm_model* m) -> int32_t { return (int32_t)plspm_detail_round_units_peek(m); }},      // (64 until the digit planes of this upload exist: a query builds nothing)
+    {"build_experiments", [](const plspm_model*) -> int32_t { return kExperiments; }},
+};
+#undef LAST
 
 extern "C" {
 
@@ -433,157 +443,24 @@ void* plspm_stream(plspm_model_t* m) { return m ? (void*)m->stream : nullptr; }
 int plspm_model_set_option(plspm_model_t* m, const char* key, int32_t value) {
     if (!m || !key) return fail(m, PLSPM_E_ARG, "plspm_model_set_option: bad arguments");
     const std::string k(key);
-    auto bad = [&]() { return fail(m, PLSPM_E_ARG, "plspm_model_set_option: value out of range for '" + k + "'"); };
-    // measured-neutral / slower kernel variants and timing probes exist in the experiments build only (make -C plspm-python_amd/csrc experiments)
-#ifdef PLSPM_I8_EXPERIMENTS
-    const bool experiments = true;
-#else
-    const bool experiments = false;
-#endif
-    auto exp_only = [&]() { return fail(m, PLSPM_E_ARG, "plspm_model_set_option: this value of '" + k + "' names a variant of the experiments build (make experiments; PLSPM_HIP_LIB)"); };
-    if (k == "solver_threads") { if (value != 64 && value != 128 && value != 256) return bad(); m->tune.solver_threads = value; }
-    else if (k == "nm_threads") { if (value != 0 && value != 64 && value != 128 && value != 256) return bad(); m->tune.nm_threads = value; }
-    else if (k == "fit_chunks") { if (value < 0 || value > 65535) return bad(); m->tune.fit_chunks = value; }
-    else if (k == "wide_ring") { if (value != 0 && value != 4 && value != 6) return bad(); m->tune.wide_ring = value; }      // row buffers of the dense wide Gram's ring (0: two-stage ping-pong)
-    else if (k == "wide_nw") { if (value != 4 && value != 8 && value != 16) return bad(); m->tune.wide_nw = value; }
-    else if (k == "conv_pass") { if (value < 0 || value > 2) return bad(); m->tune.conv_pass = value; }
-    else if (k == "scores_tile") { if (value != 0 && value != 16 && value != 32) return bad(); m->tune.scores_tile = value; }
-    else if (k == "gram_lds_kb") { if (value < 0 || value > 160) return bad(); m->tune.gram_lds_kb = value; }
-    else if (k == "gram_path") { if (value < 0 || value > 2) return bad(); m->tune.gram_path = value; }
-    else if (k == "i8_slices") { if (value < 0 || value > 8) return bad(); if (value != m->tune.i8_slices) m->zs_valid = false; m->tune.i8_slices = value; }
-    else if (k == "i8_min_slices") { if (value != 0 && (value < 6 || value > 8)) return bad(); if (value != m->tune.i8_min_slices) { m->zs_valid = false; m->zs_stats_ready = false; } m->tune.i8_min_slices = value; }
-    else if (k == "i8_min_batch") { if (value < 1) return bad(); m->tune.i8_min_batch = value; }
-    else if (k == "i8_waves") { if (value != 4 && value != 8) return bad(); if (value != 8 && !experiments) return exp_only(); m->tune.i8_waves = value; }
-    else if (k == "nm_fast_lds") { if (value < 0 || value > 1) return bad(); m->tune.nm_fast_lds = value; }
-    else if (k == "nm_k16") { if (value < 0 || value > 1) return bad(); m->tune.nm_k16 = value; }
-    else if (k == "nm_codes") { if (value < 0 || value > 1) return bad(); m->tune.nm_codes = value; }
-    else if (k == "nm_mfma") { if (value < 0 || value > 1) return bad(); m->tune.nm_mfma = value; }
-    else if (k == "nm_direct16") { if (value < 0 || value > 1) return bad(); m->tune.nm_direct16 = value; }
-    else if (k == "i8_nibbles") { if (value < 0 || value > 2) return bad(); m->tune.i8_nibbles = value; }
-    else if (k == "strat_rows") { if (value < 0 || value > 2) return bad(); m->tune.strat_rows = value; }
-    else if (k == "nm_wave") { if (value < 0 || value > 1) return bad(); m->tune.nm_wave = value; }
-    else if (k == "i8_ind") { if (value < 0 || value > 1) return bad(); if (value != m->tune.i8_ind) m->zs_valid = false; m->tune.i8_ind = value; }
-    else if (k == "upload_direct") { if (value < 0 || value > 1) return bad(); m->tune.upload_direct = value; }
-    else if (k == "i8_short_rows") { if (value < -1 || value > 4096) return bad(); m->tune.i8_short = value; }
-    else if (k == "i8_cus") { if (value != 0 && (value < 8 || value > 4096)) return bad(); m->tune.i8_cus = value; }
-    else if (k == "i8_rt") { if (value != 0 && value != 16 && value != 8 && value != 20) return bad(); if (value == 8 && !experiments) return exp_only(); m->tune.i8_rt = value; }
-    else if (k == "solver_rows") { if (value != 0 && value != 1) return bad(); m->tune.solver_rows = value; }
-    else if (k == "solver_wave") { if (value < 0 || value > 3) return bad(); m->tune.solver_wave = value; }
-    else if (k == "solver_quad") { if (value != 0 && value != 1) return bad(); m->tune.solver_quad = value; }
-    else if (k == "nm_live") { if (value != 0 && value != 1) return bad(); m->tune.nm_live = value; }
-    else if (k == "nm_wave16") { if (value != 0 && value != 1) return bad(); m->tune.nm_wave16 = value; }            // 0: Scale.NUM / RAW batches on the per-iteration launches of rounds 1-5
-    else if (k == "nm_subset") { if (value < 0 || value > 100) return bad(); m->tune.nm_subset = value; }      // categorical wave step: 0 every stop-rule pass over all rows (rounds 1-5) | n >= 1: the step stops on its own upper bound and its pass reads n tol / bound of the rows (lower bound; default 4)
-    else if (k == "nm_cpl") { if (value != 0 && value != 8 && value != 6) return bad(); m->tune.nm_cpl = value; }      // categorical wave step: 0 automatic (six aug columns per lane where they cover the model) | 8 eight per lane (round 5) | 6 six wherever the layout allows (probes: plspm_nonmetric.hip `cpl6`)
-    else if (k == "nm_c10") { if (value != 0 && value != 1) return bad(); m->tune.nm_c10 = value; }      // categorical wave step, items of nine / ten categories: 1 the ten-category instantiation (two waves per SIMD) | 0 the sixteen-category one
-    else if (k == "nm_vlong") { if (value != 0 && value != 1) return bad(); m->tune.nm_vlong = value; }      // one-launch categorical batch, verification: 1 one long round for the stragglers behind the fourth short one
-    else if (k == "nm_cat_one") { if (value != 0 && value != 1) return bad(); m->tune.nm_cat_one = value; }      // 0: the categorical wave step launch by launch (round 5 / the bound + row-subset form of round 6)
-    else if (k == "nm_bound_shift") { if (value < 0 || value > 200) return bad(); m->tune.nm_bound_shift = value; }     // test seam: the solver's stop bound times 2^value (solver_wave16.h NmWaveIo)
-    else if (k == "nm_verify_rows") { if (value < 0 || value > 100) return bad(); m->tune.nm_verify_rows = value; }  // percent of the rows the lower-bound pass reads (0: an eighth)
-    else if (k == "nm_counts8") { if (value != 0 && value != 1) return bad(); m->tune.nm_counts8 = value; }
-    else if (k == "resample_aux") { if (value < 0 || value > 3) return bad(); if (value && !experiments) return exp_only(); m->tune.resample_aux = value; }
-    else if (k == "i8_sched") { if (value != 0 && value != 1) return bad(); if (value && !experiments) return exp_only(); m->tune.i8_sched = value; }
-    else if (k == "i8_priv") { if (value < 0 || value > 1) return bad(); m->tune.i8_priv = value; }
-    else if (k == "i8_persist") { if (value < 0 || value > 1) return bad(); m->tune.i8_persist = value; }
-    else if (k == "i8_nostore") { if (value < 0 || value > 1) return bad(); if (value && !experiments) return exp_only(); m->tune.i8_nostore = value; }
-    else if (k == "i8_shape") { if (value != 16 && value != 32) return bad(); if (value != 16 && !experiments) return exp_only(); if (value != m->tune.i8_shape) m->zs_valid = false; m->tune.i8_shape = value; }
-    else if (k == "i8_variant") { if (value < -1 || value > 899) return bad(); if (value >= 0 && !experiments) return exp_only(); m->tune.i8_variant = value; }
-    else if (k == "i8_dma") { if (value < 0 || value > 2) return bad(); m->tune.i8_dma = value; }
-    else if (k == "conv_gy") { if (value < 0 || value > 65535) return bad(); m->tune.conv_gy = value; }
-    else if (k == "boot_chunks") { if (value < 0 || value > kBootChunksMax) return bad(); m->tune.boot_chunks = value; }
-    else if (k == "boot_ratio") { if (value < 10 || value > 100) return bad(); m->tune.boot_ratio = value; }
-    else if (k == "boot_align") { if (value < 0 || value > (1 << 20)) return bad(); m->tune.boot_align = value; }
-    else if (k == "boot_pass") { if (value < 0 || value > (1 << 30) || (value & 255)) return bad(); m->tune.boot_pass = value; }      // test seam: cap on the replicates per pass (plspm_detail_bootstrap)
-    else return fail(m, PLSPM_E_ARG, "plspm_model_set_option: unknown option '" + k + "'");
+    OptionEffect voids;
+    switch (option_set(m->tune, key, value, kExperiments, &voids)) {
+        case OPTION_OK: break;
+        case OPTION_OUT_OF_RANGE: return fail(m, PLSPM_E_ARG, "plspm_model_set_option: value out of range for '" + k + "'");
+        case OPTION_EXPERIMENTS_ONLY: return fail(m, PLSPM_E_ARG, "plspm_model_set_option: this value of '" + k + "' names a variant of the experiments build (make experiments; PLSPM_HIP_LIB)");
+        case OPTION_UNKNOWN: return fail(m, PLSPM_E_ARG, "plspm_model_set_option: unknown option '" + k + "'");
+    }
+    if (voids & OPTION_VOIDS_PLANES) m->zs_valid = false;
+    if (voids & OPTION_VOIDS_STATS) m->zs_stats_ready = false;
     if (m->group) plspm_detail_group_plan_changed(m->group);
     return 0;
 }
 
 int plspm_model_get_option(const plspm_model_t* m, const char* key, int32_t* value) {
     if (!m || !key || !value) return PLSPM_E_ARG;
-    const std::string k(key);
-    if (k == "solver_threads") *value = m->tune.solver_threads;
-    else if (k == "nm_threads") *value = m->tune.nm_threads;
-    else if (k == "fit_chunks") *value = m->tune.fit_chunks;
-    else if (k == "wide_nw") *value = m->tune.wide_nw;
-    else if (k == "wide_ring") *value = m->tune.wide_ring;
-    else if (k == "conv_pass") *value = m->tune.conv_pass;
-    else if (k == "scores_tile") *value = m->tune.scores_tile;
-    else if (k == "gram_lds_kb") *value = m->tune.gram_lds_kb;
-    else if (k == "conv_gy") *value = m->tune.conv_gy;
-    else if (k == "gram_path") *value = m->tune.gram_path;
-    else if (k == "i8_slices") *value = m->tune.i8_slices;
-    else if (k == "last_i8_slices") *value = m->zs_valid ? m->zs_S : 0;
-    else if (k == "last_i8_rt") *value = m->last_i8_rt;
-    else if (k == "last_i8_short") *value = m->last_i8_short;
-    else if (k == "last_i8_mt") *value = m->last_i8_mt;
-    else if (k == "last_i8_ratio") *value = (m->zs_valid && m->zs_ratio < 9e18) ? (int64_t)m->zs_ratio : 0;      // floor of the smallest sum|z| / max|z| (automatic plane count)
-    else if (k == "i8_min_batch") *value = m->tune.i8_min_batch;
-    else if (k == "i8_waves") *value = m->tune.i8_waves;
-    else if (k == "nm_fast_lds") *value = m->tune.nm_fast_lds;
-    else if (k == "nm_k16") *value = m->tune.nm_k16;
-    else if (k == "nm_codes") *value = m->tune.nm_codes;
-    else if (k == "last_nm_codes") *value = m->last_nm_codes;
-    else if (k == "nm_mfma") *value = m->tune.nm_mfma;
-    else if (k == "last_nm_mfma") *value = m->last_nm_mfma;
-    else if (k == "nm_direct16") *value = m->tune.nm_direct16;
-    else if (k == "last_nm_direct16") *value = m->last_nm_direct16;
-    else if (k == "i8_nibbles") *value = m->tune.i8_nibbles;
-    else if (k == "strat_rows") *value = m->tune.strat_rows;
-    else if (k == "last_strat_rows") *value = m->last_strat_rows;
-    else if (k == "last_i8_nibbles") *value = m->last_i8_nibbles;
-    else if (k == "i8_ind") *value = m->tune.i8_ind;
-    else if (k == "i8_rt") *value = m->tune.i8_rt;
-    else if (k == "i8_short_rows") *value = m->tune.i8_short;
-    else if (k == "i8_cus") *value = m->tune.i8_cus;
-    else if (k == "upload_direct") *value = m->tune.upload_direct;
-    else if (k == "i8_dma") *value = m->tune.i8_dma;
-    else if (k == "last_i8_dma") *value = m->last_i8_dma;
-    else if (k == "solver_rows") *value = m->tune.solver_rows;
-    else if (k == "solver_wave") *value = m->tune.solver_wave;
-    else if (k == "solver_quad") *value = m->tune.solver_quad;
-    else if (k == "nm_live") *value = m->tune.nm_live;
-    else if (k == "nm_wave16") *value = m->tune.nm_wave16;
-    else if (k == "nm_verify_rows") *value = m->tune.nm_verify_rows;
-    else if (k == "nm_bound_shift") *value = m->tune.nm_bound_shift;
-    else if (k == "nm_subset") *value = m->tune.nm_subset;
-    else if (k == "nm_cat_one") *value = m->tune.nm_cat_one;
-    else if (k == "nm_cpl") *value = m->tune.nm_cpl;
-    else if (k == "nm_c10") *value = m->tune.nm_c10;
-    else if (k == "nm_vlong") *value = m->tune.nm_vlong;
-    else if (k == "last_nm_one") *value = m->last_nm_one;
-    else if (k == "last_nm_exact") *value = m->last_nm_exact;
-    else if (k == "last_nm_wave16") *value = m->last_nm_wave16;
-    else if (k == "last_nm_flagged") *value = m->last_nm_flagged;
-    else if (k == "last_nm_replayed") *value = m->last_nm_replayed;
-    else if (k == "nm_counts8") *value = m->tune.nm_counts8;
-    else if (k == "last_solver") *value = m->last_solver;
-    else if (k == "resample_aux") *value = m->tune.resample_aux;
-    else if (k == "i8_sched") *value = m->tune.i8_sched;
-    else if (k == "i8_priv") *value = m->tune.i8_priv;
-    else if (k == "last_i8_priv") *value = m->last_i8_priv;
-    else if (k == "i8_persist") *value = m->tune.i8_persist;
-    else if (k == "nm_wave") *value = m->tune.nm_wave;
-    else if (k == "last_nm_wave") *value = m->last_nm_wave;
-    else if (k == "i8_min_slices") *value = m->tune.i8_min_slices;
-    else if (k == "last_i8_persist") *value = m->last_i8_persist;
-    else if (k == "i8_shape") *value = m->tune.i8_shape;
-    else if (k == "boot_chunks") *value = m->tune.boot_chunks;
-    else if (k == "boot_ratio") *value = m->tune.boot_ratio;
-    else if (k == "boot_align") *value = m->tune.boot_align;
-    else if (k == "boot_round_units") *value = (int32_t)plspm_detail_round_units_peek(m);      // (64 until the digit planes of this upload exist: a query builds nothing)
-    else if (k == "boot_pass") *value = m->tune.boot_pass;
-    else if (k == "last_boot_passes") *value = m->last_boot_passes;
-    else if (k == "last_gram_path") *value = m->last_gram_path;
-    else if (k == "last_micom_layout") *value = m->last_micom_layout;
-    else if (k == "build_experiments") {
-#ifdef PLSPM_I8_EXPERIMENTS
-        *value = 1;
-#else
-        *value = 0;
-#endif
-    }
-    else return PLSPM_E_ARG;
-    return 0;
+    if (option_get(m->tune, key, value)) return 0;
+    for (const ReadOut& r : kReadOuts) if (!strcmp(r.name, key)) { *value = r.get(m); return 0; }
+    return PLSPM_E_ARG;
 }
 
 int plspm_model_set_categorical(plspm_model_t* m, int32_t Pm, const int32_t* mv_off, const int32_t* mv_kind) {
@@ -639,12 +516,13 @@ int plspm_model_set_missing(plspm_model_t* m, int32_t n_ind, const int32_t* ind_
     for (char f : seen) if (!f) return fail(m, PLSPM_E_ARG, "ind_of: every indicator column needs a data column");
     HIPCHK(m, hipSetDevice(m->device));
     m->ind_of.assign(ind_of, ind_of + m->P);
-    if (upload_vec(m, &m->d_ind_of, m->ind_of)) return fail(m, PLSPM_E_STATE, "descriptor upload failed");
+    if (upload_vec(m, m->ind_of_buf, &m->d_ind_of, m->ind_of)) return fail(m, PLSPM_E_STATE, "descriptor upload failed");
     m->n_ind = n_ind; m->Pg = m->P + n_ind;
     set_geometry(m);
-    plspm_dfree(m->d_shift);
     m->d_shift = nullptr;
-    HIPCHK(m, plspm_dmalloc((void**)&m->d_shift, sizeof(double) * m->Pg));
+    m->shift_buf.reset();
+    HIPCHK(m, m->shift_buf.reserve(sizeof(double) * m->Pg));
+    m->d_shift = (double*)m->shift_buf.p;
     return 0;
 }
 
@@ -689,7 +567,7 @@ int plspm_model_attach_second_stage(plspm_model_t* first, plspm_model_t* second,
             base2[p] = lv_cols[l2];
         }
         m2->mv_base2 = base2; m2->lmv2_off = lmv2;
-        if (upload_vec(m2, &m2->d_mv_base2, m2->mv_base2) || upload_vec(m2, &m2->d_lmv2_off, m2->lmv2_off)) return fail(m1, PLSPM_E_STATE, "descriptor upload failed: " + m2->error);
+        if (upload_vec(m2, m2->mv_base2_buf, &m2->d_mv_base2, m2->mv_base2) || upload_vec(m2, m2->lmv2_off_buf, &m2->d_lmv2_off, m2->lmv2_off)) return fail(m1, PLSPM_E_STATE, "descriptor upload failed: " + m2->error);
     }
     HIPCHK(m1, hipMemsetAsync(m2->d_shift, 0, sizeof(double) * m2->P, m2->stream));
     HIPCHK(m1, hipStreamSynchronize(m2->stream));
@@ -721,9 +599,10 @@ int plspm_model_set_incomplete_rows(plspm_model_t* m, int32_t K, const int32_t* 
     // any failure below leaves the handle as it was before the call: no side tables, nmx_K == 0
 #define NMXCHK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { if (d_mask) plspm_dfree(d_mask); drop_incomplete_rows(m); \
         return fail(m, -(int)e__, std::string(#call) + ": " + hipGetErrorString(e__)); } } while (0)
-    NMXCHK(plspm_dmalloc((void**)&m->d_Xk, cells * sizeof(double)));
-    NMXCHK(plspm_dmalloc((void**)&m->d_Mk, cells * sizeof(double)));
-    NMXCHK(plspm_dmalloc((void**)&m->d_rowid, (size_t)K * sizeof(int)));
+    NMXCHK(m->Xk_buf.reserve(cells * sizeof(double)));
+    NMXCHK(m->Mk_buf.reserve(cells * sizeof(double)));
+    NMXCHK(m->rowid_buf.reserve((size_t)K * sizeof(int)));
+    m->d_Xk = (double*)m->Xk_buf.p; m->d_Mk = (double*)m->Mk_buf.p; m->d_rowid = (int*)m->rowid_buf.p;
     NMXCHK(plspm_dmalloc((void**)&d_mask, cells));
     NMXCHK(hipMemcpyAsync(m->d_rowid, row_index, (size_t)K * sizeof(int), hipMemcpyHostToDevice, m->stream));
     NMXCHK(hipMemcpyAsync(d_mask, present, cells, hipMemcpyHostToDevice, m->stream));
@@ -734,7 +613,8 @@ int plspm_model_set_incomplete_rows(plspm_model_t* m, int32_t K, const int32_t* 
 #undef NMXCHK
     plspm_dfree(d_mask);
     // the rows of Xa were rewritten: everything derived from them is stale (a caller may have run plspm_bootstrap_prepare before this call)
-    m->nmx_K = K; m->nmx_raw = raw_scale ? 1 : 0; m->Xt_valid = false; m->zs_valid = false; m->zs_stats_ready = false; m->codes_valid = false; m->ind8_valid = false;
+    m->nmx_K = K; m->nmx_raw = raw_scale ? 1 : 0;
+    void_resident(m, false);
     return 0;
 }
 

@@ -21,6 +21,7 @@
 #include "../../plspm-python_amd/csrc/gram_route.h"
 #include "../../plspm-python_amd/csrc/batch_route.h"
 #include "../../plspm-python_amd/csrc/group_route.h"
+#include "../../plspm-python_amd/csrc/options.h"
 
 using namespace plspm;
 
@@ -687,6 +688,26 @@ void hostemu_group_plan(const long* in, long* out) {
             *v++ = sg.rec0; *v++ = sg.first; *v++ = sg.count; *v++ = sh.first; *v++ = group_shard_full(p, k, sh.count);
         }
 }
+
+// The option table (csrc/options.h) over a bare Tune of default options.  set: `name` = `value` on a Tune that holds `start` in that option (-1 << 31: its default) and
+// defaults elsewhere; out: option_set's result (0 ok, 1 out of range, 2 experiments only, 3 unknown name), the effect bits it reported (1 planes, 2 statistics), how many
+// fields of the Tune differ from before the call, what option_get reads afterwards.  get: 1 and the default of `name`, or 0 for a name the table does not have.
+void hostemu_option_set(const char* name, int start, int value, int experiments, int* out) {
+    Tune t;
+    if (start != INT32_MIN && option_set(t, name, start, true, nullptr) != OPTION_OK) { out[0] = -1; return; }
+    const Tune before = t;
+    OptionEffect effect = OPTION_VOIDS_PLANES_AND_STATS;
+    out[0] = option_set(t, name, value, experiments != 0, &effect);
+    out[1] = (int)effect;
+    out[2] = 0;
+    static_assert(sizeof(Tune) % sizeof(int) == 0, "Tune holds ints only");
+    for (size_t i = 0; i < sizeof(Tune) / sizeof(int); ++i) out[2] += ((const int*)&t)[i] != ((const int*)&before)[i];
+    out[3] = INT32_MIN;
+    option_get(t, name, &out[3]);
+}
+int hostemu_option_get(const char* name, int* value) { const Tune t; return option_get(t, name, value); }
+int hostemu_option_count() { return (int)(sizeof(kOptions) / sizeof(kOptions[0])); }
+const char* hostemu_option_name(int i) { return kOptions[i].name; }
 
 long hostemu_packed_index(int T, int p, int q) { return packed_index(T, p, q); }
 long hostemu_packed_size(int T) { return packed_size(T); }
