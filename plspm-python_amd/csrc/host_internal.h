@@ -1,8 +1,9 @@
 // host_internal.h -- what the translation units of libplspm_hip.so share on the HOST side (round 4: the former one-file host is split by
-// concern so that the units compile side by side): plspm_hip.hip (allocator, handles, options as options.h tabulates them, upload, staging), plspm_fit.hip (fp64 Gram,
-// solvers, non-metric iteration, single fit, operator seam), plspm_gram_i8.hip (digit planes + the int8 Gram of bootstrap batches),
-// plspm_bootstrap.hip (batch driver phase by phase as batch_route.h plans it, record download, summaries), plspm_derived.hip (the records derived from a plain bootstrap's replicates),
-// plspm_group.cpp (multi-GPU groups).  Every device kernel lives in
+// concern so that the units compile side by side): plspm_hip.hip (allocator, handles, options as options.h tabulates them, upload, staging),
+// plspm_fit.hip (fp64 Gram, metric solvers, the single fit phase by phase as fit_route.h plans it, operator seam), plspm_nonmetric.hip (the
+// non-metric iteration), plspm_gram_i8.hip (digit planes + the int8 Gram of bootstrap batches), plspm_bootstrap.hip (batch driver phase by phase
+// as batch_route.h plans it, record download, summaries), plspm_derived.hip (the records derived from a plain bootstrap's replicates),
+// plspm_group.cpp (multi-GPU groups); the units of one call kind each are listed further down.  Every device kernel lives in
 // exactly one unit's headers; the functions below are the seams between them.  Nothing here is part of the C-ABI (include/plspm_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +34,7 @@
 #include "solver_route.h"
 #include "nm_route.h"
 #include "batch_route.h"
+#include "fit_route.h"
 
 using namespace plspm;
 
@@ -78,6 +80,10 @@ inline BatchOptions batch_options(const plspm_model* m) {
 }
 inline BatchKind batch_kind(const BatchCall& c) {
     return {c.B, brings_counts(c), pairs_problems(c), c.kind == BatchCall::STRATIFIED, c.d_idx != nullptr, c.moments_out != nullptr, c.rows_out != nullptr};
+}
+// fit_route.h: the shape of a single fit on this handle
+inline FitShape fit_shape(const plspm_model* m) {
+    return {(long)m->N, m->P, m->categorical ? m->Pm : m->P, m->L, m->n_eff, m->PA, m->T, m->kmax, m->n_chol, (int)m->pred_idx.size(), m->categorical != 0};
 }
 inline bool gram_i8_closed(const plspm_model* m, int slices) { return gram_i8_closed(batch_shape(m), batch_options(m), slices); }
 inline int choose_gram_path(const plspm_model* m, int64_t B) { return choose_gram_path(batch_shape(m), batch_options(m), B); }

@@ -51,27 +51,31 @@ struct plspm_model {
     uint8_t* d_C = nullptr;
     int64_t N = 0;
     double* d_Xa = nullptr;
-    // A device block and its owner: the block goes back to the allocator with the Buf, i.e. with `delete m` for a member of the handle -- behind the
-    // synchronisation of the handle's streams in plspm_model_destroy, as the allocator asks.  Grow-only through ensure() below.
-    struct Buf {
+    // A block of the caching allocator and its owner: the block goes back to the allocator with the owner, i.e. with `delete m` for a member of the handle -- behind
+    // the synchronisation of the handle's streams in plspm_model_destroy, as the allocator asks.  Buf: device memory, grow-only through ensure() below; Pin: pinned
+    // host memory.
+    template <hipError_t (*ALLOC)(void**, size_t), void (*FREE)(void*)>
+    struct Block {
         void* p = nullptr;
         size_t cap = 0;
-        Buf() = default;
-        Buf(const Buf&) = delete;
-        Buf& operator=(const Buf&) = delete;
-        Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-        Buf& operator=(Buf&& o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
-        ~Buf() { reset(); }
-        void reset() { if (p) plspm_dfree(p); p = nullptr; cap = 0; }
-        // at least `bytes` on the CURRENT device; a block that is too small is given back first, so the caller has made sure that nothing in flight uses it
+        Block() = default;
+        Block(const Block&) = delete;
+        Block& operator=(const Block&) = delete;
+        Block(Block&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+        Block& operator=(Block&& o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+        ~Block() { reset(); }
+        void reset() { if (p) FREE(p); p = nullptr; cap = 0; }
+        // at least `bytes` (device memory: on the CURRENT device); a block that is too small is given back first, so the caller has made sure that nothing in flight uses it
         hipError_t reserve(size_t bytes) {
             if (bytes <= cap) return hipSuccess;
             reset();
-            const hipError_t e = plspm_dmalloc(&p, bytes);
+            const hipError_t e = ALLOC(&p, bytes);
             if (e == hipSuccess) cap = bytes;
             return e;
         }
     };
+    using Buf = Block<plspm_dmalloc, plspm_dfree>;
+    using Pin = Block<plspm_hmalloc, plspm_hfree>;
     // (a member x_buf owns the block that the typed pointer d_x points at: the other units, and the kernels' descriptors, read the pointer)
     Buf shift_buf;
     double* d_shift = nullptr;
@@ -119,10 +123,10 @@ struct plspm_model {
     double *d_Xk = nullptr, *d_Mk = nullptr;
     int* d_rowid = nullptr;
     Buf Xk_buf, Mk_buf, rowid_buf;      // (plspm_hip.hip drop_incomplete_rows)
-    int* h_flag = nullptr;        // pinned: active-problem counter of the non-metric iteration
+    Pin flag_pin;
+    int* h_flag = nullptr;        // pinned (a view of flag_pin): active-problem counter of the non-metric iteration
     hipEvent_t ev_flag = nullptr;
-    void* h_stage = nullptr;      // pinned host staging for plspm_fit results
-    size_t h_stage_cap = 0;
+    Pin h_stage;                  // pinned host staging for plspm_fit results (fit_route.h stage_need)
     // result bookkeeping: `rows` holds the records of the last plspm_bootstrap(_device) only (the fit's scores have their own buffer)
     Buf scores;
     Buf xa, up_raw, up_ci, up_partial;   // resident matrix (d_Xa points into `xa` while data are uploaded) and the upload staging
@@ -151,8 +155,7 @@ struct plspm_model {
     bool zs_valid = false;
     bool zs_stats_ready = false;  // phase 1 of the digit planes is enqueued (pair tables, column statistics on their way to h_zstat): plspm_gram_i8.hip prepare_zs_stats
     int zs_stats_S = 0;           // ... for this value of the "i8_slices" option
-    void* h_zstat = nullptr;      // pinned copy of the column statistics (automatic plane count)
-    size_t h_zstat_cap = 0;
+    Pin h_zstat;                  // pinned copy of the column statistics (automatic plane count)
     hipEvent_t ev_zstat = nullptr;
     int zs_S = 0, zs_KB = 0, zs_NT = 0, zs_npair = 0, zs_npg = 0;
     int zs_floor = 0;           // the plane floor the current planes were cut under (prepare_zs: 0 = the handle's own choice, 7 = a permutation call)
@@ -204,8 +207,7 @@ struct plspm_model {
     int last_i8_short = 0;        // ... and, with 20, how many of its tile rows were short ones (16 count tiles: gram_route.h i8_mix_plan)
     int last_solver = 0;          // the SolverRoute (solver_route.h) of the last metric or Scale.NUM / RAW bootstrap batch
     // grow-only pinned host staging for uploads / row downloads (two halves: copy-in of chunk k+1 overlaps the DMA of chunk k)
-    void* h_pin = nullptr;
-    size_t h_pin_cap = 0;
+    Pin h_pin;
     hipEvent_t ev_pin[2] = {nullptr, nullptr};
     hipEvent_t ev_pin_async = nullptr;   // behind copies that left the staging area without a host wait (plspm_hip.hip pin_leave_async)
     bool pin_pending = false;

@@ -461,7 +461,7 @@ static int fetch_segments(plspm_model* m, hipStream_t cs, const double* d_record
     struct Session { bool on = false; ~Session() { if (on) unpack_crew().end(); } } crew;
     if ((size_t)B_total * stride * sizeof(double) >= ((size_t)1 << 20)) crew.on = unpack_crew().begin();
     auto unpack = [&](int h, int64_t b0, int64_t nb) {
-        Job j{(const double*)((const char*)m->h_pin + h * kPinHalf), b0, nb, stride, R, out, status, iters};
+        Job j{(const double*)((const char*)m->h_pin.p + h * kPinHalf), b0, nb, stride, R, out, status, iters};
         if (crew.on) unpack_crew().run(unpack_part, &j); else unpack_part(&j, 0, 1);
     };
     int64_t prev_b0 = 0, prev_nb = 0;
@@ -472,7 +472,7 @@ static int fetch_segments(plspm_model* m, hipStream_t cs, const double* d_record
             const int h = k & 1;
             const int64_t nb = std::min<int64_t>(per, segs[sg].b0 + segs[sg].nb - b0);
             // (half h was unpacked before the piece before this one was waited for: free)
-            HIPCHK(m, hipMemcpyAsync((char*)m->h_pin + h * kPinHalf, d_records + b0 * stride, (size_t)nb * stride * sizeof(double), hipMemcpyDeviceToHost, cs));
+            HIPCHK(m, hipMemcpyAsync((char*)m->h_pin.p + h * kPinHalf, d_records + b0 * stride, (size_t)nb * stride * sizeof(double), hipMemcpyDeviceToHost, cs));
             HIPCHK(m, hipEventRecord(m->ev_pin[h], cs));
             if (prev_nb) { HIPCHK(m, hipEventSynchronize(m->ev_pin[h ^ 1])); unpack(h ^ 1, prev_b0, prev_nb); }
             prev_b0 = b0; prev_nb = nb;
@@ -495,11 +495,11 @@ int plspm_detail_summary(plspm_model* m, const double* rows, int64_t B, int32_t 
     const bool in_lds = (size_t)npad * sizeof(double) <= (size_t)128 * 1024;
     int rc;
     if ((rc = pin_ready(m))) return rc;
-    if ((size_t)R * 7 * sizeof(double) + 64 > m->h_pin_cap) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_summary: record too wide for the staging area");
+    if ((size_t)R * 7 * sizeof(double) + 64 > m->h_pin.cap) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_summary: record too wide for the staging area");
     if (!in_lds && (rc = ensure(m, m->sum_buf, (size_t)R * npad * sizeof(double)))) return rc;
     // [original R | summary 6R | n_used] in the handle's pinned staging area, read and written by the kernel itself (R + 6R + 1 words
     // across the host link): no copy engine operation in front of or behind the kernel, whose scheduling gaps cost more than the bytes
-    double* h_io = (double*)m->h_pin;
+    double* h_io = (double*)m->h_pin.p;
     memcpy(h_io, original, sizeof(double) * R);
     // the records column-major first (values + status: R + 1 columns of B, one small tiled transpose): read in place, every value of a
     // column costs the summary workgroup a 128-byte line of its own (2 x B L1 fills per column were 40 % of the kernel)
@@ -547,10 +547,10 @@ int plspm_detail_intervals(plspm_model* m, const double* rows, int64_t B, int32_
     const bool in_lds = npad <= CI_LDS_VALUES;
     int rc;
     if ((rc = pin_ready(m))) return rc;
-    if ((size_t)R * 8 * sizeof(double) + 64 > m->h_pin_cap) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: record too wide for the staging area");
+    if ((size_t)R * 8 * sizeof(double) + 64 > m->h_pin.cap) return fail(m, PLSPM_E_ARG, "plspm_bootstrap_intervals: record too wide for the staging area");
     if (!in_lds && (rc = ensure(m, m->sum_buf, (size_t)R * npad * sizeof(double)))) return rc;
     // [original R | accel R | intervals 6R | n_used] in the handle's pinned staging area, read and written by the kernel itself (plspm_detail_summary)
-    double* h_io = (double*)m->h_pin;
+    double* h_io = (double*)m->h_pin.p;
     memcpy(h_io, original, sizeof(double) * R);
     if (accel) memcpy(h_io + R, accel, sizeof(double) * R);
     const long cols_ld = (long)((B + 63) & ~(int64_t)63);

@@ -1,5 +1,5 @@
-// plspm_fit.hip -- host side, part 2: the fp64 MFMA Gram launches, the metric solvers, the single fit (plspm_fit) and the operator seam
-// (plspm_op_*).  Kernels: kernels_gram.h, kernels_solver.h, kernels_scores.h.  (The non-metric iteration: plspm_nonmetric.hip.)
+// plspm_fit.hip -- host side, part 2: the fp64 MFMA Gram launches, the metric solvers, the single fit (plspm_fit, phase by phase as fit_route.h plans it) and the
+// operator seam (plspm_op_*).  Kernels: kernels_gram.h, kernels_solver.h, kernels_scores.h.  (The non-metric iteration: plspm_nonmetric.hip.)
 #include "host_internal.h"
 #include <hip/hip_ext.h>
 
@@ -32,12 +32,12 @@ static int launch_gram(plspm_model* m, long nproblems, int nchunks, const int2* 
         case 7: WIDE(7, 4, 4) break;
         case 9: WIDE(9, 4, 4) break;
         case 11: WIDE(11, 4, 4) break;
-        case 13:
+        case 13: {
             // (configs[4]: the dense walk on a ring of row buffers -- kernels_gram.h gram_walk_dense_ring; option wide_ring 0: the two-stage ping-pong)
-            if (DENSE && m->tune.wide_ring == 4) { hipLaunchKernelGGL((gram_wide_kernel<13, 4, 4, DENSE, DENSE ? 4 : 0>), dim3(nchunks, (unsigned)nproblems, 1), dim3(256), 0, s, m->d_Xa, N, ent, nent, ent_stride, out); }
-            else if (DENSE && m->tune.wide_ring >= 5) { hipLaunchKernelGGL((gram_wide_kernel<13, 4, 4, DENSE, DENSE ? 6 : 0>), dim3(nchunks, (unsigned)nproblems, 1), dim3(256), 0, s, m->d_Xa, N, ent, nent, ent_stride, out); }
-            else WIDE(13, 4, 4)
-            break;
+            const int ring = !DENSE ? 0 : m->tune.wide_ring == 4 ? 4 : m->tune.wide_ring >= 5 ? 6 : 0;
+            const auto k = ring == 4 ? gram_wide_kernel<13, 4, 4, DENSE, DENSE ? 4 : 0> : ring == 6 ? gram_wide_kernel<13, 4, 4, DENSE, DENSE ? 6 : 0> : gram_wide_kernel<13, 4, 4, DENSE>;
+            hipLaunchKernelGGL(k, dim3(nchunks, (unsigned)nproblems, 1), dim3(256), 0, s, m->d_Xa, N, ent, nent, ent_stride, out);
+        } break;
         case 15: WIDE(15, 4, 4) break;
         case 8: WIDE(8, 4, 4) break;
         case 10: WIDE(10, 4, 4) break;
@@ -74,45 +74,31 @@ int run_impute(plspm_model* m, long nproblems, const double* Min, const double**
 }
 
 int launch_solver(plspm_model* m, long nproblems, const double* Mp, long mp_stride, const SolverOut& so, int threads) {
-    const int P = m->P, L = m->L;
-    const size_t s_bytes = (size_t)cov_doubles(P) * sizeof(double);
-    const size_t small_bytes = (size_t)workspace_small_doubles(P, L, m->kmax, m->n_chol) * sizeof(double);
-    const size_t lds_budget = (nproblems == 1) ? kMaxLds : 64 * 1024;   // batched: keep >= 2 workgroups per CU
-    int s_in_lds = 0, small_in_lds = 0;
-    size_t lds = desc_lds_bytes(P, L, m->n_eff, (int)m->pred_idx.size());
-    if (lds + small_bytes <= lds_budget) { small_in_lds = 1; lds += small_bytes; }
-    if (small_in_lds && lds + s_bytes <= lds_budget) { s_in_lds = 1; lds += s_bytes; }
-    if (!s_in_lds) { int rc = ensure(m, m->gS, (size_t)nproblems * s_bytes); if (rc) return rc; }
-    if (!small_in_lds) { int rc = ensure(m, m->gsmall, (size_t)nproblems * small_bytes); if (rc) return rc; }
-#define SOLVER_LAUNCH(A, B)                                                                                                        \
-    {                                                                                                                              \
-        int rc = allow_lds(m, (const void*)solver_kernel<A, B>, lds);                                                               \
-        if (rc) return rc;                                                                                                         \
-        hipLaunchKernelGGL((solver_kernel<A, B>), dim3((unsigned)nproblems), dim3(threads), lds, m->stream, make_desc(m), Mp, mp_stride, so, \
-                           (double*)m->gS.p, (double*)m->gsmall.p);                                                                \
-    }
-    if (s_in_lds && small_in_lds) SOLVER_LAUNCH(true, true)
-    else if (small_in_lds) SOLVER_LAUNCH(false, true)
-    else SOLVER_LAUNCH(false, false)
-#undef SOLVER_LAUNCH
+    const SolverLds pl = solver_lds(route_shape(m), nproblems);      // (solver_route.h: what of the workspace lives in LDS)
+    int rc;
+    if (!pl.s_in_lds && (rc = ensure(m, m->gS, (size_t)nproblems * pl.s_bytes))) return rc;
+    if (!pl.small_in_lds && (rc = ensure(m, m->gsmall, (size_t)nproblems * pl.small_bytes))) return rc;
+    const auto k = pl.s_in_lds ? solver_kernel<true, true> : pl.small_in_lds ? solver_kernel<false, true> : solver_kernel<false, false>;
+    if ((rc = allow_lds(m, (const void*)k, pl.lds))) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)nproblems), dim3(threads), pl.lds, m->stream, make_desc(m), Mp, mp_stride, so, (double*)m->gS.p, (double*)m->gsmall.p);
     HIPCHK(m, hipGetLastError());
     return 0;
+}
+
+// The full sample's metric solve behind dense_moments(): the single fit's and solve_full_sample's.
+static int solve_metric_moments(plspm_model* m, const SolverOut& so) {
+    const double* Mp; long mp_stride;
+    if (int rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride)) return rc;
+    ProfScope ps(m, PLSPM_K_SOLVER);
+    return launch_solver(m, 1, Mp, mp_stride, so, 256);
 }
 
 
 // Moment matrix of ALL uploaded rows (single fit, operator seam): the dense MFMA Gram split over row chunks + the fixed-order
 // reduce -> m->gram (tile-packed, of the shifted columns + ones).
 int dense_moments(plspm_model* m) {
-    const long N = m->N;
     const long psize = packed_size(m->T);
-    const long ng = (N + 3) / 4;
-    // row chunks (workgroups) of the dense Gram: enough k-groups per wave to amortise the pipeline prologue; at most two workgroups
-    // per CU for the rows kernel (every wave holds all tiles), ONE for the tile-split kernels (a wave per SIMD already fills the
-    // register file; measured on 1M x 200: 256 chunks 0.941 + reduce 0.027 ms, 512: 0.939 + 0.063, 1024: 0.954 + 0.132)
-    const int waves_per_wg = (m->T <= 4) ? 4 : 1;
-    const long per_wave = 16;
-    const long max_chunks = (m->T <= 4) ? 512 : 256;
-    const int nchunks = m->tune.fit_chunks > 0 ? m->tune.fit_chunks : (int)std::max<long>(1, std::min<long>(max_chunks, (ng + waves_per_wg * per_wave - 1) / (waves_per_wg * per_wave)));
+    const int nchunks = fit_gram_chunks(m->N, m->T, m->tune.fit_chunks);      // (fit_route.h: the row chunks, one workgroup each)
     int rc;
     if ((rc = ensure(m, m->gram_partial, (size_t)nchunks * psize * sizeof(double)))) return rc;
     if ((rc = ensure(m, m->gram, (size_t)psize * sizeof(double)))) return rc;
@@ -134,10 +120,7 @@ int solve_full_sample(plspm_model* m, double* record, int* status_iters) {
     if ((rc = dense_moments(m))) return rc;
     SolverOut so{};
     so.row = record; so.row_stride = 0; so.status = status_iters; so.iters = status_iters + 1;
-    const double* Mp; long mp_stride;
-    if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;
-    ProfScope ps(m, PLSPM_K_SOLVER);
-    return launch_solver(m, 1, Mp, mp_stride, so, 256);
+    return solve_metric_moments(m, so);
 }
 
 int launch_gram_lists(plspm_model* m, long nproblems, const int2* ent, const int* nent, long ent_stride, double* out) {
@@ -254,106 +237,108 @@ int launch_batch_solver(plspm_model* m, long nb, SolverRoute route, const Solver
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ the single fit, phase by phase as fit_route.h plans it
+// The device result block as the plan lays it out, and where the solver writes into it.
+static int fit_reserve(plspm_model* m, const FitPlan& pl, SolverOut* so) {
+    if (int rc = ensure(m, m->fitout, pl.fit_bytes)) return rc;
+    double* d = (double*)m->fitout.p;
+    int* d_int = (int*)(d + pl.o_end);
+    *so = SolverOut{};
+    so->row = d + pl.o_row; so->row_stride = 0; so->status = d_int + FIT_INT_STATUS; so->iters = d_int + FIT_INT_ITERS;
+    so->fit.weights = d + pl.o_w; so->fit.loadings = d + pl.o_ld; so->fit.crossloadings = d + pl.o_cl; so->fit.path_coef = d + pl.o_pc; so->fit.r2 = d + pl.o_r2;
+    so->fit.lv_cov = d + pl.o_lc; so->fit.indirect = d + pl.o_ind; so->fit.score_w = d + pl.o_sw; so->fit.score_c = d + pl.o_sc;
+    so->fit.cov = pl.call.want_cov ? d + pl.o_cov : nullptr; so->fit.mean = d + pl.o_mean; so->fit.sign = (int8_t*)(d_int + FIT_INT_SIGN);
+    return 0;
+}
+
+// The one problem on the moments at m->gram.
+static int fit_solve(plspm_model* m, const SolverOut& so) {
+    if (!m->nonmetric) return solve_metric_moments(m, so);
+    return run_nonmetric(m, plan_nonmetric(m, NmCall{1, false, false, false, true}), NmInputs{(const double*)m->gram.p, packed_size(m->T), nullptr, nullptr, 0, nullptr, 0, 256}, so);
+}
+
+// (tile rows, chunk class) of the plan -> the instantiation
+typedef void (*ScoresFn)(const double*, long, int, int, int, const int*, const double*, const double*, double*);
+static ScoresFn scores_fn(int tile_rows, int cls) {
+    static const ScoresFn table[2][5] = {{scores_kernel<16, 2>, scores_kernel<16, 4>, scores_kernel<16, 6>, scores_kernel<16, 8>, scores_kernel<16, 0>},
+                                         {scores_kernel<32, 2>, scores_kernel<32, 4>, scores_kernel<32, 6>, scores_kernel<32, 8>, scores_kernel<32, 0>}};
+    return table[tile_rows == 32][cls ? cls / 2 - 1 : 4];
+}
+
+// Scores of all rows -> m->scores, from the score map the solver left in the block.
+static int fit_scores(plspm_model* m, const FitPlan& pl) {
+    const ScoresLaunch& k = pl.scores;
+    const double* d = (const double*)m->fitout.p;
+    int rc;
+    if ((rc = ensure(m, m->scores, pl.score_bytes))) return rc;
+    const ScoresFn fn = scores_fn(k.tile_rows, k.cls);
+    if ((rc = allow_lds(m, (const void*)fn, k.lds))) return rc;
+    ProfScope ps(m, PLSPM_K_SCORES);
+    hipLaunchKernelGGL(fn, dim3(k.grid), dim3(256), k.lds, m->stream, (const double*)m->d_Xa, (long)m->N, m->PA, m->P, m->L, (const int*)m->d_boff, d + pl.o_sw, d + pl.o_sc, (double*)m->scores.p);
+    if (m->nmx_K) {                                     // the incomplete rows' scores are not affine in the columns: take them from the state
+        const int P = m->P, L = m->L;
+        const double* Yn = (const double*)m->nmstate.p + nm_state_doubles(P, L, m->n_chol) + m->nmx_K + 2L * P + (long)m->nmx_K * P + (long)m->nmx_K * L;
+        hipLaunchKernelGGL(patch_scores_kernel, dim3((unsigned)m->nmx_K), dim3(64), 0, m->stream, (double*)m->scores.p, L, (const int*)m->d_rowid, Yn);
+    }
+    return 0;
+}
+
+// ONE device->host copy of the whole result block into the pinned staging block (15 separate small copies cost more than the four kernels of a 10k x 60 fit);
+// small score matrices ride it too, large ones go to the caller's array.  Returns with the stream drained.
+static int fit_download(plspm_model* m, const FitPlan& pl, double* scores_out) {
+    HIPCHK(m, m->h_stage.reserve(pl.stage_need));
+    char* hs = (char*)m->h_stage.p;
+    const double* d = (const double*)m->fitout.p;
+    HIPCHK(m, hipMemcpyAsync(hs, d, pl.block_bytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipMemcpyAsync(hs + (size_t)pl.o_end * sizeof(double), d + pl.o_end, pl.tail_bytes, hipMemcpyDeviceToHost, m->stream));
+    if (pl.stage_scores) HIPCHK(m, hipMemcpyAsync(hs + pl.fit_bytes, m->scores.p, pl.score_bytes, hipMemcpyDeviceToHost, m->stream));
+    else if (pl.call.want_scores) HIPCHK(m, hipMemcpyAsync(scores_out, m->scores.p, pl.score_bytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return 0;
+}
+
+// The pinned copy -> the caller's arrays (any may be null).
+static void fit_scatter(const plspm_model* m, const FitPlan& pl, const plspm_fit_result_t* out) {
+    const char* hs = (const char*)m->h_stage.p;
+    if (pl.stage_scores) memcpy(out->scores, hs + pl.fit_bytes, pl.score_bytes);
+    const double* h = (const double*)hs;
+    const int* h_int = (const int*)(h + pl.o_end);
+    auto put = [&](void* dst, const void* src, size_t bytes) { if (dst) memcpy(dst, src, bytes); };
+    const int P = m->P, L = m->L, ne = m->n_eff, Po = pl.Po;
+    put(out->weights, h + pl.o_w, sizeof(double) * Po);
+    put(out->loadings, h + pl.o_ld, sizeof(double) * Po);
+    put(out->crossloadings, h + pl.o_cl, sizeof(double) * Po * L);
+    put(out->path_coef, h + pl.o_pc, sizeof(double) * L * L);
+    put(out->r2, h + pl.o_r2, sizeof(double) * L);
+    put(out->lv_cov, h + pl.o_lc, sizeof(double) * L * L);
+    put(out->total, h + pl.h_total, sizeof(double) * ne);
+    put(out->direct, h + pl.h_direct, sizeof(double) * ne);
+    put(out->indirect, h + pl.o_ind, sizeof(double) * ne);
+    put(out->cov, h + pl.o_cov, sizeof(double) * Po * Po);
+    if (m->categorical) { if (out->mean) memset(out->mean, 0, sizeof(double) * Po); }
+    else put(out->mean, h + pl.o_mean, sizeof(double) * P);
+    put(out->sign, h_int + FIT_INT_SIGN, (size_t)L);
+    put(out->iterations, h_int + FIT_INT_ITERS, sizeof(int));
+    put(out->status, h_int + FIT_INT_STATUS, sizeof(int));
+}
+
 extern "C" {
 
 int plspm_fit(plspm_model_t* m, const plspm_fit_result_t* out) {
     if (!m || !out) return PLSPM_E_ARG;
     if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_fit: no data uploaded");
     HIPCHK(m, hipSetDevice(m->device));
-    const int P = m->P, L = m->L, ne = m->n_eff;
-    const long N = m->N;
-    const long psize = packed_size(m->T);
+    const FitPlan pl = fit_plan(fit_shape(m), FitCall{out->scores != nullptr, out->cov != nullptr}, FitOptions{m->tune.fit_chunks, m->tune.scores_tile});
+    SolverOut so;
     int rc;
-    // device-side result block
-    const long o_w = 0, o_ld = o_w + P, o_cl = o_ld + P, o_pc = o_cl + (long)P * L, o_r2 = o_pc + (long)L * L, o_lc = o_r2 + L,
-               o_row = o_lc + (long)L * L, o_ind = o_row + (2L * P + L + 2L * ne + 2), o_sw = o_ind + std::max(ne, 1), o_sc = o_sw + P, o_mean = o_sc + L,
-               o_cov = o_mean + P, o_end = o_cov + (long)P * P;
-    const size_t fit_bytes = (size_t)o_end * sizeof(double) + 64 + (size_t)L + 16;
-    if ((rc = ensure(m, m->fitout, fit_bytes))) return rc;
-    double* d = (double*)m->fitout.p;
-    int* d_int = (int*)(d + o_end);           // [0] iters, [1] status
-    int8_t* d_sign = (int8_t*)(d_int + 4);
-    if ((rc = dense_moments(m))) return rc;
-    SolverOut so{};
-    so.row = d + o_row; so.row_stride = 0; so.status = d_int + 1; so.iters = d_int;
-    so.fit.weights = d + o_w; so.fit.loadings = d + o_ld; so.fit.crossloadings = d + o_cl; so.fit.path_coef = d + o_pc; so.fit.r2 = d + o_r2;
-    so.fit.lv_cov = d + o_lc; so.fit.indirect = d + o_ind; so.fit.score_w = d + o_sw; so.fit.score_c = d + o_sc;
-    so.fit.cov = out->cov ? d + o_cov : nullptr; so.fit.mean = d + o_mean; so.fit.sign = d_sign;
-    if (m->nonmetric) {
-        if ((rc = run_nonmetric(m, plan_nonmetric(m, NmCall{1, false, false, false, true}), NmInputs{(const double*)m->gram.p, psize, nullptr, nullptr, 0, nullptr, 0, 256}, so))) return rc;
-    } else {
-        const double* Mp; long mp_stride;
-        if ((rc = run_impute(m, 1, (const double*)m->gram.p, &Mp, &mp_stride))) return rc;
-        ProfScope ps(m, PLSPM_K_SOLVER);
-        if ((rc = launch_solver(m, 1, Mp, mp_stride, so, 256))) return rc;
-    }
-    if (out->scores) {
-        if ((rc = ensure(m, m->scores, (size_t)N * L * sizeof(double)))) return rc;
-        // tile rows: 32 while two workgroups of them fit one CU's LDS, else 16 (wide models; option "scores_tile" overrides);
-        // chunk count per thread selects the prefetching instantiation (PA <= 256), wider matrices take the plain one
-        auto lds_of = [&](int tr) { return ((size_t)tr * (m->PA + 1) + P + L + (size_t)tr * L) * sizeof(double) + (size_t)(L + 2) * sizeof(int); };
-        const bool tr32 = m->tune.scores_tile ? (m->tune.scores_tile == 32) : (lds_of(32) <= 72 * 1024);
-        const int TRows = tr32 ? 32 : 16;
-        const size_t lds = lds_of(TRows);
-        const int nch = (m->PA / 2 + 15) / 16;
-        typedef void (*ScoresFn)(const double*, long, int, int, int, const int*, const double*, const double*, double*);
-        ScoresFn fn;
-        if (tr32) fn = nch <= 2 ? scores_kernel<32, 2> : nch <= 4 ? scores_kernel<32, 4> : nch <= 6 ? scores_kernel<32, 6> : nch <= 8 ? scores_kernel<32, 8> : scores_kernel<32, 0>;
-        else fn = nch <= 2 ? scores_kernel<16, 2> : nch <= 4 ? scores_kernel<16, 4> : nch <= 6 ? scores_kernel<16, 6> : nch <= 8 ? scores_kernel<16, 8> : scores_kernel<16, 0>;
-        if ((rc = allow_lds(m, (const void*)fn, lds))) return rc;
-        const long ntl = (N + TRows - 1) / TRows;
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, kMaxLds / lds));
-        const int grid = (int)std::min<long>(256L * per_cu, ntl);         // resident workgroups only: each walks its tiles with the prefetch running
-        ProfScope ps(m, PLSPM_K_SCORES);
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, m->stream, (const double*)m->d_Xa, N, m->PA, P, L, (const int*)m->d_boff, (const double*)(d + o_sw), (const double*)(d + o_sc), (double*)m->scores.p);
-        if (m->nmx_K) {                                     // the incomplete rows' scores are not affine in the columns: take them from the state
-            const double* Yn = (const double*)m->nmstate.p + nm_state_doubles(P, L, m->n_chol) + m->nmx_K + 2L * P + (long)m->nmx_K * P + (long)m->nmx_K * L;
-            hipLaunchKernelGGL(patch_scores_kernel, dim3((unsigned)m->nmx_K), dim3(64), 0, m->stream, (double*)m->scores.p, L, (const int*)m->d_rowid, Yn);
-        }
-    }
+    if ((rc = fit_reserve(m, pl, &so)) || (rc = dense_moments(m)) || (rc = fit_solve(m, so))) return rc;
+    if (pl.call.want_scores && (rc = fit_scores(m, pl))) return rc;
     HIPCHK(m, hipGetLastError());
-    // ONE device->host copy of the whole result block into a pinned staging buffer, then scatter on the host
-    // (15 separate small copies cost more than the four kernels of a 10k x 60 fit).
-    const size_t block_bytes = (size_t)(out->cov ? o_end : o_cov) * sizeof(double);
-    const size_t tail_bytes = 64 + (size_t)L + 16;
-    const size_t score_bytes = out->scores ? sizeof(double) * (size_t)N * L : 0;
-    const bool stage_scores = score_bytes > 0 && score_bytes <= ((size_t)8 << 20);      // small score matrices ride the pinned buffer too
-    const size_t stage_need = fit_bytes + (stage_scores ? score_bytes : 0);
-    if (m->h_stage_cap < stage_need) {
-        if (m->h_stage) plspm_hfree(m->h_stage);
-        m->h_stage = nullptr; m->h_stage_cap = 0;
-        HIPCHK(m, plspm_hmalloc(&m->h_stage, stage_need));
-        m->h_stage_cap = stage_need;
-    }
-    char* hs = (char*)m->h_stage;
-    HIPCHK(m, hipMemcpyAsync(hs, d, block_bytes, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(m, hipMemcpyAsync(hs + (size_t)o_end * sizeof(double), d + o_end, tail_bytes, hipMemcpyDeviceToHost, m->stream));
-    if (stage_scores) HIPCHK(m, hipMemcpyAsync(hs + fit_bytes, m->scores.p, score_bytes, hipMemcpyDeviceToHost, m->stream));
-    else if (out->scores) HIPCHK(m, hipMemcpyAsync(out->scores, m->scores.p, score_bytes, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(m, hipStreamSynchronize(m->stream));
+    if ((rc = fit_download(m, pl, out->scores))) return rc;
     // plspm_bootstrap_prepare ran before this fit: its column statistics are on the host now, so the digit planes are cut (enqueue only)
     // while the caller unpacks the fit -- the first bootstrap call finds them ready.  (A failure here is reported by that call, which retries.)
     if (m->zs_stats_ready && !m->zs_valid) { const std::string keep = m->error; if (prepare_zs(m)) { (void)hipGetLastError(); m->error = keep; } }
-    if (stage_scores) memcpy(out->scores, hs + fit_bytes, score_bytes);
-    const double* h = (const double*)hs;
-    const int* h_int = (const int*)(h + o_end);
-    auto put = [&](void* dst, const void* src, size_t bytes) { if (dst) memcpy(dst, src, bytes); };
-    const int Po = m->categorical ? m->Pm : P;             // categorical handles report per logical MV, not per aug column
-    put(out->weights, h + o_w, sizeof(double) * Po);
-    put(out->loadings, h + o_ld, sizeof(double) * Po);
-    put(out->crossloadings, h + o_cl, sizeof(double) * Po * L);
-    put(out->path_coef, h + o_pc, sizeof(double) * L * L);
-    put(out->r2, h + o_r2, sizeof(double) * L);
-    put(out->lv_cov, h + o_lc, sizeof(double) * L * L);
-    put(out->total, h + o_row + Po + L, sizeof(double) * ne);
-    put(out->direct, h + o_row + Po + L + ne, sizeof(double) * ne);
-    put(out->indirect, h + o_ind, sizeof(double) * ne);
-    put(out->cov, h + o_cov, sizeof(double) * Po * Po);
-    if (m->categorical) { if (out->mean) memset(out->mean, 0, sizeof(double) * Po); }
-    else put(out->mean, h + o_mean, sizeof(double) * P);
-    put(out->sign, h_int + 4, (size_t)L);
-    put(out->iterations, h_int, sizeof(int));
-    put(out->status, h_int + 1, sizeof(int));
+    fit_scatter(m, pl, out);
     return 0;
 }
 

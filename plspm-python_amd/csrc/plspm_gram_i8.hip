@@ -97,14 +97,9 @@ int prepare_zs_stats(plspm_model* m) {
                            (const unsigned long long*)d_max, d_max + npair, d_max + 2 * npair);
         HIPCHK(m, hipGetLastError());
         const size_t bytes = 3 * (size_t)npair * sizeof(unsigned long long);
-        if (m->h_zstat_cap < bytes) {
-            if (m->h_zstat) plspm_hfree(m->h_zstat);
-            m->h_zstat = nullptr; m->h_zstat_cap = 0;
-            HIPCHK(m, plspm_hmalloc(&m->h_zstat, bytes));
-            m->h_zstat_cap = bytes;
-        }
+        HIPCHK(m, m->h_zstat.reserve(bytes));
         if (!m->ev_zstat) HIPCHK(m, hipEventCreateWithFlags(&m->ev_zstat, hipEventDisableTiming));
-        HIPCHK(m, hipMemcpyAsync(m->h_zstat, d_max, bytes, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(m, hipMemcpyAsync(m->h_zstat.p, d_max, bytes, hipMemcpyDeviceToHost, m->stream));
         HIPCHK(m, hipEventRecord(m->ev_zstat, m->stream));
     }
     HIPCHK(m, hipGetLastError());
@@ -134,7 +129,7 @@ int prepare_zs(plspm_model* m, int floor) {
     ProfScope ps(m, PLSPM_K_PACK);
     if (S == 0) {
         HIPCHK(m, hipEventSynchronize(m->ev_zstat));          // (long done when a fit ran behind plspm_bootstrap_prepare)
-        if ((rc = choose_slices(m, (const unsigned long long*)m->h_zstat, npair, &S, floor))) return rc;
+        if ((rc = choose_slices(m, (const unsigned long long*)m->h_zstat.p, npair, &S, floor))) return rc;
     }
     hipLaunchKernelGGL(zs_scale_kernel, dim3((unsigned)((npair + 255) / 256)), dim3(256), 0, m->stream, d_max, (int)npair, S, d_k, (double*)m->pair_scale.p);
     // one plane (0/1 data): the product runs through the seven-plane main loop with the planes of a wave standing for seven consecutive

@@ -183,7 +183,7 @@ static int upload_blob(plspm_model* m, int slot, const std::vector<BlobPart>& pa
     if (rc) return rc;
     void* blob = nullptr;
     HIPCHK(m, plspm_dmalloc(&blob, total));
-    char* host = (char*)m->h_pin;
+    char* host = (char*)m->h_pin.p;
     memset(host, 0, total);
     for (size_t i = 0; i < parts.size(); ++i)
         if (parts[i].bytes) memcpy(host + off[i], parts[i].src, parts[i].bytes);
@@ -279,8 +279,9 @@ plspm_model_t* plspm_model_create(int32_t P, int32_t L, const int32_t* block_off
         return bail("descriptor upload failed");
     if (m->shift_buf.reserve(sizeof(double) * P) != hipSuccess) return bail("hipMalloc failed");
     m->d_shift = (double*)m->shift_buf.p;
-    if (plspm_hmalloc((void**)&m->h_flag, 64) != hipSuccess || hipEventCreateWithFlags(&m->ev_flag, hipEventDisableTiming) != hipSuccess)
+    if (m->flag_pin.reserve(64) != hipSuccess || hipEventCreateWithFlags(&m->ev_flag, hipEventDisableTiming) != hipSuccess)
         return bail("pinned flag / event creation failed");
+    m->h_flag = (int*)m->flag_pin.p;
     return m;
 }
 
@@ -293,17 +294,13 @@ void plspm_model_destroy(plspm_model_t* m) {
     if (m->aux) hipStreamSynchronize(m->aux);
     if (m->stream) hipStreamSynchronize(m->stream);
     prof_collect(m);
-    // every Buf member gives its block back with `delete m` below; the descriptor arrays d_boff ... d_lv_cols are parts of the blobs, not blocks of their own
+    // every Buf and Pin member gives its block back with `delete m` below; the descriptor arrays d_boff ... d_lv_cols are parts of the blobs, not blocks of their own
     for (void* p : m->blobs) if (p) plspm_dfree(p);
-    if (m->h_stage) plspm_hfree(m->h_stage);
-    if (m->h_pin) plspm_hfree(m->h_pin);
     for (int k = 0; k < 2; ++k) if (m->ev_pin[k]) hipEventDestroy(m->ev_pin[k]);
     for (auto& e : m->ev_part) if (e) hipEventDestroy(e);
     if (m->dl) { hipStreamSynchronize(m->dl); plspm_stream_release(m->dl); }
     if (m->ev_pin_async) hipEventDestroy(m->ev_pin_async);
     for (int k = 0; k < PLSPM_K_COUNT; ++k) for (auto& pr : m->prof[k].pool) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-    if (m->h_flag) plspm_hfree(m->h_flag);
-    if (m->h_zstat) plspm_hfree(m->h_zstat);
     if (m->ev_zstat) hipEventDestroy(m->ev_zstat);
     if (m->ev_flag) hipEventDestroy(m->ev_flag);
     for (int k = 0; k < 2; ++k) { if (m->ev_counts[k]) hipEventDestroy(m->ev_counts[k]); if (m->ev_cdfree[k]) hipEventDestroy(m->ev_cdfree[k]); }
@@ -363,7 +360,7 @@ int plspm_upload(plspm_model_t* m, const double* X, int64_t N, int32_t src_cols,
         // small data sets (the 4.8 MB of the 10k x 60 headline): matrix and column index through ONE staging half, both copies enqueued without a
         // host wait -- the synchronise at the end of this call is the only round trip of the upload (it also covers the staging area's re-use)
         if ((rc = pin_ready(m))) return rc;
-        char* stage = (char*)m->h_pin;
+        char* stage = (char*)m->h_pin.p;
         const size_t ci_off = (raw_bytes + 63) & ~(size_t)63;
         memcpy(stage, X, raw_bytes);
         memcpy(stage + ci_off, ci.data(), ci_bytes);
@@ -630,9 +627,8 @@ int plspm_sync(plspm_model_t* m) {
 
 // ---- pinned staging: pageable host buffers never meet the DMA engines directly --------------------------------------------------
 int pin_ready(plspm_model* m) {
-    if (!m->h_pin) {
-        HIPCHK(m, plspm_hmalloc(&m->h_pin, 2 * kPinHalf));
-        m->h_pin_cap = 2 * kPinHalf;
+    if (!m->h_pin.p) {
+        HIPCHK(m, m->h_pin.reserve(2 * kPinHalf));
         for (int k = 0; k < 2; ++k) HIPCHK(m, hipEventCreateWithFlags(&m->ev_pin[k], hipEventDisableTiming));
         HIPCHK(m, hipEventCreateWithFlags(&m->ev_pin_async, hipEventDisableTiming));
     }
@@ -707,7 +703,7 @@ int plspm_detail_h2d(plspm_model* m, void* dst, const void* src, size_t bytes) {
     // copy enqueue, the crew's hand-shake -- are ~30 us against 0.15 ms of DMA per 8 MB)
     struct Big { void* p = nullptr; ~Big() { if (p) plspm_hfree(p); } } big;
     size_t half = kPinHalf;
-    char* base = (char*)m->h_pin;
+    char* base = (char*)m->h_pin.p;
     // ... and on a stream of their own: behind a kernel on the handle's stream the runtime moves host -> device copies at about half the
     // rate it reaches on a stream that only ever copied (configs[4]'s upload right after a fit: 54 ms against 29.5; tools/experiments/upload_seq.py)
     struct Lane { hipStream_t s = nullptr; ~Lane() { if (s) { (void)hipStreamSynchronize(s); plspm_stream_release(s); } } } lane;      // (error paths: no copy may still read the halves freed below)

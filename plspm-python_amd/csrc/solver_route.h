@@ -24,6 +24,21 @@ PLSPM_HD size_t desc_lds_bytes(int P, int L, int ne, int nedge) {
 // As plspm_model_create derives it: kmax = most predecessors of one LV, n_chol = doubles of the Mode-B factors, n_eff = effect pairs, nedge = path edges
 struct RouteShape { int P, L, kmax, n_chol, n_eff, nedge; const int* boff; };
 
+// Where solver_kernel (ROUTE_LDS, and the single fit) keeps its workspace: the small workspace goes in LDS behind the descriptors if it fits the budget -- all of a
+// CU's LDS for one problem, 64 KiB for a batch (>= 2 workgroups per CU) -- and the covariance matrix S too if it then still fits; what does not lives in global
+// scratch (s_bytes / small_bytes per problem).  lds: the launch's dynamic LDS.
+struct SolverLds { bool s_in_lds, small_in_lds; size_t lds, s_bytes, small_bytes; };
+PLSPM_HD SolverLds solver_lds(const RouteShape& s, long nproblems) {
+    SolverLds k{};
+    k.s_bytes = (size_t)cov_doubles(s.P) * sizeof(double);
+    k.small_bytes = (size_t)workspace_small_doubles(s.P, s.L, s.kmax, s.n_chol) * sizeof(double);
+    const size_t budget = nproblems == 1 ? kMaxLds : 64 * 1024;
+    k.lds = desc_lds_bytes(s.P, s.L, s.n_eff, s.nedge);
+    if (k.lds + k.small_bytes <= budget) { k.small_in_lds = true; k.lds += k.small_bytes; }
+    if (k.small_in_lds && k.lds + k.s_bytes <= budget) { k.s_in_lds = true; k.lds += k.s_bytes; }
+    return k;
+}
+
 // A metric batch's solver on the dense moment matrices the int8 Gram can write, or ROUTE_LDS (packed matrices) where no dense solver takes the model.  solver_wave:
 // 0 none, 1 / 2 the wave16 form at <= 8 LVs, 3 the round-3 kernel there; solver_quad 0: split rows instead; solver_rows 0: no dense solver.  (A model of the
 // <= 8 LV wave forms always passes the rows test below: at most 37 KB.)

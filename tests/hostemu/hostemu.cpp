@@ -20,6 +20,7 @@
 #include "../../plspm-python_amd/csrc/nm_route.h"
 #include "../../plspm-python_amd/csrc/gram_route.h"
 #include "../../plspm-python_amd/csrc/batch_route.h"
+#include "../../plspm-python_amd/csrc/fit_route.h"
 #include "../../plspm-python_amd/csrc/group_route.h"
 #include "../../plspm-python_amd/csrc/options.h"
 
@@ -687,6 +688,20 @@ void hostemu_group_plan(const long* in, long* out) {
             const GroupShard sh = group_shard(p, k, r);
             *v++ = sg.rec0; *v++ = sg.first; *v++ = sg.count; *v++ = sh.first; *v++ = group_shard_full(p, k, sh.count);
         }
+}
+
+// The plan of one single fit (csrc/fit_route.h fit_plan).  sh: N, P, Po, L, n_eff, PA, T, kmax, n_chol, nedge, categorical; call: want_scores, want_cov, then the options
+// fit_chunks, scores_tile.  out: the offsets o_w, o_ld, o_cl, o_pc, o_r2, o_lc, o_row, o_ind, o_sw, o_sc, o_mean, o_cov, o_end, then h_total, h_direct, tail_bytes, fit_bytes,
+// block_bytes, nchunks, the scores launch tile_rows, cls, lds, ntl, per_cu, grid, then score_bytes, stage_scores, stage_need, then the solver's placement (solver_route.h
+// solver_lds) s_in_lds, small_in_lds, lds as the plan has it for one problem and the same three for a batch, then the tail's named ints: iterations, status, signs
+void hostemu_fit_plan(const long* sh, const long* call, long* out) {
+    const FitShape s{sh[0], (int)sh[1], (int)sh[2], (int)sh[3], (int)sh[4], (int)sh[5], (int)sh[6], (int)sh[7], (int)sh[8], (int)sh[9], sh[10] != 0};
+    const FitPlan p = fit_plan(s, FitCall{call[0] != 0, call[1] != 0}, FitOptions{(int)call[2], (int)call[3]});
+    const SolverLds b = solver_lds(RouteShape{s.P, s.L, s.kmax, s.n_chol, s.n_eff, s.nedge, nullptr}, 2);
+    const long v[] = {p.o_w, p.o_ld, p.o_cl, p.o_pc, p.o_r2, p.o_lc, p.o_row, p.o_ind, p.o_sw, p.o_sc, p.o_mean, p.o_cov, p.o_end, p.h_total, p.h_direct, (long)p.tail_bytes, (long)p.fit_bytes,
+                      (long)p.block_bytes, p.nchunks, p.scores.tile_rows, p.scores.cls, (long)p.scores.lds, p.scores.ntl, p.scores.per_cu, p.scores.grid, (long)p.score_bytes, p.stage_scores,
+                      (long)p.stage_need, p.solver.s_in_lds, p.solver.small_in_lds, (long)p.solver.lds, b.s_in_lds, b.small_in_lds, (long)b.lds, FIT_INT_ITERS, FIT_INT_STATUS, FIT_INT_SIGN};
+    for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
 }
 
 // The option table (csrc/options.h) over a bare Tune of default options.  set: `name` = `value` on a Tune that holds `start` in that option (-1 << 31: its default) and
