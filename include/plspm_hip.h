@@ -645,6 +645,51 @@ int plspm_geodesic_summary(plspm_model_t* m, int64_t B, const double* original, 
 int plspm_geodesic_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
 
 /*
+ * ---- Structural-model assessment of the bootstrap -------------------------------------------------------------------------------
+ * The f2 effect size and the inner VIF of every direct path, and every specific indirect effect, for every replicate: one more kernel behind the assessment
+ * kernel, beside PLSc and what follows it.  This library's definitions, for one data set: rc [L x L] its construct correlation matrix -- the
+ * assessment record's signed lv_cor, diagonal 1 --, pred(j) the predecessors of LV j, and R2(j | S) the R squared of regressing j on the LVs in S on rc with the
+ * solver's own regression (Cholesky pivots above 1e-13 of the diagonal, else the minimum-norm solution; R2 = beta' rc_Sj; exactly 0 for an empty S).
+ *   per direct path i -> j, in the order of plspm_effect_pairs restricted to the pairs with a path of their own, with S = pred(j) without i
+ *     f2        (R2(j | pred(j)) - R2(j | S)) / (1 - R2(j | pred(j)))
+ *     vif       1 / (1 - R2(i | S))                                         (exactly 1 for an empty S)
+ *   per specific indirect effect -- a directed chain i -> m_1 -> ... -> j with at least one mediator --, ordered by effect pair, then lexicographically by
+ *   node sequence
+ *     specific  the product of the replicate's own `direct` entries along the chain, multiplied left to right
+ * Structural record, width S = 2 n_dir + n_spec:  f2[n_dir] | vif[n_dir] | specific[n_spec];  device records carry a status and the replicate's iteration count
+ * behind it as doubles (pitch S + 2).  A replicate whose bootstrap status is not PLSPM_OK keeps that status and has NaN in all S values.  Otherwise
+ * PLSPM_SINGULAR where a regression reports failure and PLSPM_NONFINITE where an f2 or vif is not finite (an R squared of 1); the values stand.  Plain metric
+ * handles only (no non-metric scales, no missing values, not part of a two-stage pair): PLSPM_E_ARG otherwise.  A path model with more than 4,096 specific
+ * indirect effects is PLSPM_E_LIMIT from the first of these calls that lists them (the chains are counted before they are enumerated; the message names the
+ * count), and so is a model whose rc and one regression's scratch exceed a workgroup's 160 KiB of LDS.
+ *
+ * plspm_structural_enable: on != 0: every later plspm_bootstrap / plspm_bootstrap_device call on this handle also writes the structural records of its
+ *   replicates into a buffer of their own, indexed like the bootstrap's records -- and the assessment records, which the kernel reads, whether or not
+ *   plspm_assess_enable was called.  The stage is a branch behind the assessment: it runs whether or not PLSc, model fit and the geodesic discrepancy do, and
+ *   the records of all of those, the assessment records and the bootstrap's records, status and iteration counts are bit for bit what they are without it.
+ *   Off (the default): no launch, no allocation.  Permutation, stratified, cross-validation, jackknife and group calls write none.
+ * plspm_structural_width: S (0 before the paths were listed: plspm_structural_enable, plspm_structural_paths or plspm_structural_fit).
+ * plspm_structural_paths: the direct paths and the chains in record order: *n_dir, dir_from [n_dir], dir_to [n_dir], *n_spec, chain_off [n_spec + 1] (offsets
+ *   into chain_nodes), chain_nodes [chain_off[n_spec]] (every chain's LVs from its first to its last).  Any pointer may be NULL: ask for the sizes first
+ *   (chain_off alone gives the length of chain_nodes).
+ * plspm_structural_fit: the full-sample record, out [S]: the same two kernels on the moments of all uploaded rows and one solver problem (plspm_fit's); *status
+ *   (may be NULL): the record's status.  Needs no plspm_structural_enable.
+ * plspm_structural_fetch: host copy of the records [first, first + count) of the last structural bootstrap: out [count*S], status [count] (may be NULL).
+ * plspm_structural_summary / plspm_structural_intervals: plspm_bootstrap_summary / plspm_bootstrap_intervals on the structural records (B: that bootstrap's,
+ *   else PLSPM_E_ARG): original [S] host, summary / out [S*6] host, *n_used (may be NULL).  Methods 0 (percentile), 1 (basic), 2 (bc); 3 (bca) is PLSPM_E_ARG:
+ *   the jackknife writes no structural records.
+ * PLSPM_E_STATE from the last three without structural records on the handle (none written yet; whatever voids the assessment records voids these; a jackknife
+ * leaves them alone).
+ */
+int plspm_structural_enable(plspm_model_t* m, int32_t on);
+int32_t plspm_structural_width(const plspm_model_t* m);
+int plspm_structural_paths(plspm_model_t* m, int32_t* n_dir, int32_t* dir_from, int32_t* dir_to, int32_t* n_spec, int32_t* chain_off, int32_t* chain_nodes);
+int plspm_structural_fit(plspm_model_t* m, double* out, int32_t* status);
+int plspm_structural_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
+int plspm_structural_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
+int plspm_structural_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
+
+/*
  * ---- MICOM: permutation test of measurement invariance --------------------------------------------------------------------------
  * Measurement invariance of composite models (Henseler, Ringle and Sarstedt 2016), steps 2 and 3, for every permutation of plspm_permutation_device: one more
  * kernel behind the solver reads both halves' moment matrices and records.  Per group g of a permutation (problem 2r: a, 2r + 1: b), from its

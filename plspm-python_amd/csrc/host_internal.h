@@ -163,8 +163,9 @@ int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, d
 // plspm_nonmetric.hip: a Scale.NUM / RAW batch as one solver launch + verification (pl.num_one); reads in.cd8 / in.cd8_MT and the dense moment matrices at m->gram
 int run_nonmetric_wave(plspm_model* m, const NmPlan& pl, const NmInputs& in, const SolverOut& so);
 
-// ---- plspm_derived.hip: the chain assessment -> PLSc -> model fit -> geodesic discrepancy behind a plain metric bootstrap's solver, as the batch driver sees it
-// Once per call: *depth = the deepest stage that applies (0 none, 1 assessment, 2 + PLSc, 3 + model fit, 4 + geodesic discrepancy) -- a plain call on a plain metric handle, no moments seam,
+// ---- plspm_derived.hip: the chain assessment -> PLSc -> model fit -> geodesic discrepancy, and the structural branch behind the assessment, behind a plain metric
+// bootstrap's solver, as the batch driver sees it.  `depth` is the call's chain value: zero for no stage, otherwise opaque to the driver (plspm_derived.hip takes it apart).
+// Once per call: *depth = the deepest stage that applies (0 none, 1 assessment, 2 + PLSc, 3 + model fit, 4 + geodesic discrepancy; the branch is a flag beside it) -- a plain call on a plain metric handle, no moments seam,
 // whose owner takes the records: a call into the handle's own `rows` does (and its record buffers are reserved here for call.B replicates), a sub-batch of
 // plspm_bootstrap() does (call.chain_off; that function reserved them for the whole call with this same function), a group's shard does not.
 int derived_begin(plspm_model* m, const BatchCall& call, int* depth);

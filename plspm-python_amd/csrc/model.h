@@ -189,6 +189,14 @@ struct plspm_model {
     bool geodesic_on = false;                // plspm_geodesic_enable
     Buf geodesic_rows;                       // ... the replicates' records
     int64_t geodesic_B = 0;                  // ... the last plain bootstrap whose geodesic records are on the handle (0: none)
+    // structural-model assessment of a plain bootstrap's replicates (kernels_structural.h; plspm_structural_*): records [structural_B x (2 n_dir + n_spec + 2)] in a
+    // buffer of their own, indexed like the assessment records, which are written whenever these are (the structural kernel reads their lv_cor); a branch of its own
+    // behind the assessment, beside PLSc and what follows it.  The direct paths and the chains are enumerated once, at plspm_structural_enable
+    bool structural_on = false;              // plspm_structural_enable
+    bool structural_listed = false;          // ... the lists below describe this handle's path matrix
+    std::vector<int> struct_dir_from, struct_dir_to, struct_chain_off, struct_chain_nodes;      // [n_dir] x 2, [n_spec + 1], [chain_off[n_spec]]
+    Buf structural_rows, structural_desc;    // ... the replicates' records; dir_from | dir_to | chain_off | chain_eff on the device (structural_core.h StructDesc)
+    int64_t structural_B = 0;                // ... the last plain bootstrap whose structural records are on the handle (0: none)
     // MICOM records of a permutation call's splits (kernels_micom.h; plspm_micom_*): records [micom_B x (3 L + 2)] in a buffer of their own, indexed by the
     // permutation's position in the call; the pooled inputs (u, the diagonal blocks of R_0; plspm_micom.hip micom_prepare) once per upload
     bool micom_on = false;                   // plspm_micom_enable
@@ -263,7 +271,7 @@ enum : unsigned { REC_ROWS = 1, REC_CV = 2, REC_ASSESS = 4, REC_MICOM = 8, REC_J
 inline void void_records(plspm_model* m, unsigned which) {
     if (which & REC_ROWS) m->rows_B = 0;
     if (which & REC_CV) m->cv_reps = 0;
-    if (which & REC_ASSESS) m->assess_B = 0;
+    if (which & REC_ASSESS) m->assess_B = m->structural_B = 0;      // (the structural records go with the assessment records they were computed from)
     if (which & REC_MICOM) m->micom_B = 0;
     if (which & REC_JACK) m->jack_G = 0;
     if (which & REC_PLSC) m->plsc_B = m->modelfit_B = m->geodesic_B = 0;      // (the model-fit and geodesic records go with the PLSc records they were computed from)

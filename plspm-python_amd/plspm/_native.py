@@ -36,6 +36,8 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_plsc_enable", "plspm_plsc_width", "plspm_plsc_fit", "plspm_plsc_fetch", "plspm_plsc_summary", "plspm_plsc_intervals",
            "plspm_modelfit_enable", "plspm_modelfit_width", "plspm_modelfit_fit", "plspm_modelfit_fetch", "plspm_modelfit_summary", "plspm_modelfit_intervals",
            "plspm_geodesic_enable", "plspm_geodesic_width", "plspm_geodesic_fit", "plspm_geodesic_fetch", "plspm_geodesic_summary", "plspm_geodesic_intervals",
+           "plspm_structural_enable", "plspm_structural_width", "plspm_structural_paths", "plspm_structural_fit", "plspm_structural_fetch", "plspm_structural_summary",
+           "plspm_structural_intervals",
            "plspm_micom_enable", "plspm_micom_width", "plspm_micom_fetch", "plspm_micom_summary", "plspm_micom_intervals", "plspm_micom_counts"]
 CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
 CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
@@ -128,8 +130,10 @@ def load():
     lib.plspm_jackknife_fetch.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.plspm_jackknife_stats.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_bootstrap_intervals.argtypes = [vp, vp, i64, i32, vp, vp, i32, dbl, vp, ctypes.POINTER(i64)]
-    # the five families of side records (assessment, PLSc, model fit, geodesic discrepancy, MICOM): one set of signatures; only MICOM has no full-sample record
-    for family in ("assess", "plsc", "modelfit", "geodesic", "micom"):
+    # the six families of side records (assessment, PLSc, model fit, geodesic discrepancy, structural assessment, MICOM): one set of signatures; only MICOM has no
+    # full-sample record
+    lib.plspm_structural_paths.argtypes = [vp, ctypes.POINTER(i32), vp, vp, ctypes.POINTER(i32), vp, vp]
+    for family in ("assess", "plsc", "modelfit", "geodesic", "structural", "micom"):
         getattr(lib, "plspm_%s_enable" % family).argtypes = [vp, i32, vp] if family in ("plsc", "modelfit", "geodesic") else [vp, i32]
         getattr(lib, "plspm_%s_width" % family).restype = i32
         getattr(lib, "plspm_%s_width" % family).argtypes = [vp]
@@ -611,6 +615,42 @@ class NativeModel:
     def assess_intervals(self, B, original, method="percentile", level=0.95):
         """``intervals`` on the assessment records (plspm_assess_intervals; no bca): ([A, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
         return self._side_table("assess", "intervals", B, original, method, level)
+
+    def structural_enable(self, on=True):
+        """Structural-model assessment (plspm_structural_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the record f2 [n_dir] |
+        vif [n_dir] | specific [n_spec] of every replicate -- and the assessment records, which the kernel reads; no other record changes."""
+        self._side_call("structural", "enable", int(bool(on)))
+
+    @property
+    def structural_width(self):
+        return self._side_width("structural")
+
+    def structural_paths(self):
+        """The direct paths and the chains in record order (plspm_structural_paths): (dir_from [n_dir], dir_to [n_dir], chain_off [n_spec + 1], chain_nodes)."""
+        n_dir, n_spec = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._side_call("structural", "paths", ctypes.byref(n_dir), None, None, ctypes.byref(n_spec), None, None)
+        dir_from, dir_to = np.empty(n_dir.value, dtype=np.int32), np.empty(n_dir.value, dtype=np.int32)
+        chain_off = np.empty(n_spec.value + 1, dtype=np.int32)
+        self._side_call("structural", "paths", None, _ptr(dir_from), _ptr(dir_to), None, _ptr(chain_off), None)
+        chain_nodes = np.empty(max(int(chain_off[-1]), 1), dtype=np.int32)
+        self._side_call("structural", "paths", None, None, None, None, None, _ptr(chain_nodes))
+        return dir_from, dir_to, chain_off, chain_nodes[:int(chain_off[-1])]
+
+    def structural_fit(self):
+        """The full-sample structural record (plspm_structural_fit): ([S] values, the record's status)."""
+        return self._side_fit("structural")
+
+    def structural_fetch(self, first=0, count=None):
+        """Host copy of the structural records [first, first + count) of the last structural bootstrap: (records [count, S], status [count])."""
+        return self._side_fetch("structural", first, self.last_B - first if count is None else count)
+
+    def structural_summary(self, B, original):
+        """``summary`` on the structural records (plspm_structural_summary): ([S, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
+        return self._side_table("structural", "summary", B, original)
+
+    def structural_intervals(self, B, original, method="percentile", level=0.95):
+        """``intervals`` on the structural records (plspm_structural_intervals; no bca): ([S, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
+        return self._side_table("structural", "intervals", B, original, method, level)
 
     def plsc_enable(self, on=True, factor=None):
         """Consistent PLS (plspm_plsc_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the PLSc record weights | r2 | total | direct |

@@ -6,7 +6,8 @@ over once the caller NAMES GPUs (``devices=[...]`` or the ``PLSPM_DEVICES`` allo
 ``parallel.MIN_REPLICATES_PER_GPU`` replicates per GPU; ONE RCCL all-gather merges the shards; the rows do not depend on it).
 Without named GPUs everything runs on ``device_id``.  Keyword extensions: ``seed`` (reproducible bootstrap), ``device_id``, ``devices``,
 ``quality`` (with ``bootstrap=True``: the measurement-model assessment of every replicate, ``quality()``), ``consistent`` / ``factors`` (with ``bootstrap=True``:
-consistent PLS of the full sample and of every replicate, ``plsc()``; ``factors``: the LVs that are common factors, None = every Mode-A block of two items or more), ``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
+consistent PLS of the full sample and of every replicate, ``plsc()``; ``factors``: the LVs that are common factors, None = every Mode-A block of two items or more),
+``structural`` (with ``bootstrap=True``: f2, inner VIF and the specific indirect effects of every replicate, ``structural()``), ``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
 reference's own fp64 accumulation on the data at hand; "strict": always seven planes = correctly rounded sums, ~20 % slower).
 """
 import time
@@ -68,7 +69,7 @@ class Plspm:
     def __init__(self, data: pd.DataFrame, config: c.Config, scheme: Scheme = Scheme.CENTROID, iterations: int = 100,
                  tolerance: float = 0.000001, bootstrap: bool = False, bootstrap_iterations: int = 100, processes: int = 2,
                  seed: int = None, device_id: int = 0, devices=None, precision: str = "auto", quality: bool = False,
-                 consistent: bool = False, factors=None):
+                 consistent: bool = False, factors=None, structural: bool = False):
         iterations, bootstrap_iterations = _normalise_arguments(scheme, iterations, tolerance, bootstrap_iterations, processes)
         t_start = time.perf_counter()
         estimator = Estimator(config)
@@ -106,6 +107,15 @@ class Plspm:
                 pc._check_factor_names(config, factors)
                 plsc_mask = pc._factor_mask(boot_on.compiled, factors)
                 boot_on.native.plsc_enable(True, plsc_mask)
+            if structural:
+                # the structural kernel runs behind the assessment kernel of every replicate batch on this handle (plspm.structural)
+                from plspm import quality as pq
+                from plspm import structural as pst
+                why = pq._unsupported(config, observations)
+                if why is not None:
+                    raise NotImplementedError("the structural assessment covers metric data without missing cells and without higher-order constructs: this model has " + why)
+                pst._check_chain_count(boot_on.compiled.path)
+                boot_on.native.structural_enable(True)
             pending = launch_bootstrap(boot_on, bootstrap_iterations, processes, seed, devices=devices)
         self._result = fit
         # The report frames only re-label / post-process the device outputs already on the host (fit.raw); they are built on first
@@ -141,6 +151,11 @@ class Plspm:
             if self._bootstrap.ranks() != 1:
                 raise NotImplementedError("PLSc runs on one GPU: this bootstrap was sharded over %d" % self._bootstrap.ranks())
             self._plsc = pc.PLSc.of_bootstrap(fit.native, fit.compiled, bootstrap_iterations, plsc_mask)
+        self._structural = None
+        if bootstrap and structural:
+            if self._bootstrap.ranks() != 1:
+                raise NotImplementedError("the structural assessment runs on one GPU: this bootstrap was sharded over %d" % self._bootstrap.ranks())
+            self._structural = pst.Structural.of_bootstrap(fit.native, fit.compiled, bootstrap_iterations)
         # fit_s: filter + upload + device fit; bootstrap_s: what the bootstrap adds (the wait for the replicates + the device summaries);
         # bootstrap_latency_s: enqueue of the replicates -> summaries on the host
         self._timings = {"fit_s": t_fit - t_start, "bootstrap_s": time.perf_counter() - t_fit,
@@ -212,6 +227,12 @@ class Plspm:
         if self._plsc is None:
             raise Exception("To get consistent PLS estimates, set the parameters bootstrap and consistent to True when calling Plspm")
         return self._plsc
+
+    def structural(self):
+        """The :class:`plspm.structural.Structural` assessment of the bootstrap; raises unless bootstrap=True and structural=True were requested."""
+        if self._structural is None:
+            raise Exception("To assess the structural model, set the parameters bootstrap and structural to True when calling Plspm")
+        return self._structural
 
     # --- extension: solver diagnostics -------------------------------------------------------------------
     def timings(self) -> dict:
