@@ -2,7 +2,7 @@
 // concern so that the units compile side by side): plspm_hip.hip (allocator, handles, options as options.h tabulates them, upload, staging),
 // plspm_fit.hip (fp64 Gram, metric solvers, the single fit phase by phase as fit_route.h plans it, operator seam), plspm_nonmetric.hip (the
 // non-metric iteration), plspm_gram_i8.hip (digit planes + the int8 Gram of bootstrap batches), plspm_bootstrap.hip (batch driver phase by phase
-// as batch_route.h plans it, record download, summaries), plspm_derived.hip (the records derived from a plain bootstrap's replicates),
+// as batch_route.h plans it, record download, summaries), plspm_derived.hip (the records derived from a plain bootstrap's replicates, stage by stage as derived_route.h tabulates and plans them),
 // plspm_group.cpp (multi-GPU groups); the units of one call kind each are listed further down.  Every device kernel lives in
 // exactly one unit's headers; the functions below are the seams between them.  Nothing here is part of the C-ABI (include/plspm_hip.h).
 #pragma once
@@ -163,17 +163,19 @@ int run_gram_i8(plspm_model* m, const BatchCall& call, int64_t nb, int64_t b0, d
 // plspm_nonmetric.hip: a Scale.NUM / RAW batch as one solver launch + verification (pl.num_one); reads in.cd8 / in.cd8_MT and the dense moment matrices at m->gram
 int run_nonmetric_wave(plspm_model* m, const NmPlan& pl, const NmInputs& in, const SolverOut& so);
 
-// ---- plspm_derived.hip: the chain assessment -> PLSc -> model fit -> geodesic discrepancy, and the structural branch behind the assessment, behind a plain metric
-// bootstrap's solver, as the batch driver sees it.  `depth` is the call's chain value: zero for no stage, otherwise opaque to the driver (plspm_derived.hip takes it apart).
-// Once per call: *depth = the deepest stage that applies (0 none, 1 assessment, 2 + PLSc, 3 + model fit, 4 + geodesic discrepancy; the branch is a flag beside it) -- a plain call on a plain metric handle, no moments seam,
-// whose owner takes the records: a call into the handle's own `rows` does (and its record buffers are reserved here for call.B replicates), a sub-batch of
-// plspm_bootstrap() does (call.chain_off; that function reserved them for the whole call with this same function), a group's shard does not.
-int derived_begin(plspm_model* m, const BatchCall& call, int* depth);
-// Once per chunk, behind its solver: the chain's launches on `nb` problems whose records start at position `pos` of the record buffers.  gram: their moment matrices
-// (dense: [(P+1) x cov_ld(P)] upper triangles; else tile-packed); rows: their bootstrap records, status included (pitch row_stride).
-int derived_launch(plspm_model* m, int depth, long nb, int64_t pos, bool dense, const double* gram, const double* rows, long row_stride);
+// ---- plspm_derived.hip: the records derived from a plain metric bootstrap's replicates behind its solver -- assessment, structural assessment, PLSc, model fit,
+// geodesic discrepancy: the stages of derived_route.h's table --, as the batch driver sees them.  `runs` is the call's value: the stages that run, one bit each
+// (derived_route.h stage_bit); zero: nothing to do.
+// Once per call: *runs = the enabled stages and what they read (derived_route.h derived_plan), or zero unless this is a plain call on a plain metric handle, no moments
+// seam, whose owner takes the records: a call into the handle's own `rows` does (and the running stages' record buffers are reserved here for call.B replicates), a
+// sub-batch of plspm_bootstrap() does (call.chain_off; that function reserved them for the whole call with this same function), a group's shard does not.  A stage
+// whose one wave the LDS does not hold is refused here, before anything of the call runs (PLSPM_E_LIMIT).
+int derived_begin(plspm_model* m, const BatchCall& call, int* runs);
+// Once per chunk, behind its solver: the running stages' launches on `nb` problems whose records start at position `pos` of the record buffers.  gram: their moment
+// matrices (dense: [(P+1) x cov_ld(P)] upper triangles; else tile-packed); rows: their bootstrap records, status included (pitch row_stride).
+int derived_launch(plspm_model* m, int runs, long nb, int64_t pos, bool dense, const double* gram, const double* rows, long row_stride);
 // The owner of the record buffers, behind the last chunk: B records of every stage that ran are valid.
-void derived_commit(plspm_model* m, int depth, int64_t B);
+void derived_commit(plspm_model* m, int runs, int64_t B);
 
 // ---- plspm_bootstrap.hip: side records -- a buffer of records [count x (width + 2)] (values | status | iterations) beside the bootstrap records, valid while
 // `count` is non-zero: the records of every stage of plspm_derived.hip, the MICOM records of a permutation call.  One description, and the entry points all share.

@@ -34,8 +34,7 @@ struct AssessArgs {
 
 constexpr int ASSESS_ROWS = 16;                    // rows of a block whose loads are in flight together (one memory round trip per batch, not per row)
 
-// doubles of one wave's LDS slice: 1 / s, mu, v, lambda [P] | m, g, v'Rv, sign [L] | the three pair sums of the current block [L] | one window of three columns [64]
-__host__ __device__ inline long assess_wave_doubles(int P, int L) { return 4L * P + 7L * L + 3 * 64; }
+// (doubles of one wave's LDS slice: solver_core.h assess_wave_doubles, where the launch plan sees it too)
 
 // sum of log |r| over a column as ONE logarithm: the factors are multiplied up, and after every fourth the product's exponent moves into an integer (|r| <= 1
 // up to rounding and >= 1e-19 or so unless it is exactly 0, so four factors neither overflow nor underflow; a zero stays a zero: log 0 = -inf, exp(-inf) = 0)
@@ -58,7 +57,7 @@ __global__ void __launch_bounds__(64 * ASSESS_WAVES) assess_kernel(const AssessA
     const double st = rec[a.R];
     if (!(st == 0.0)) { wave_void_record(out, A, st, rec[a.R + 1], lane); return; }
     if (lane == 0) { out[A] = st; out[A + 1] = rec[a.R + 1]; }
-    double* isd = assess_lds + (long)wave * assess_wave_doubles(P, L);
+    double* isd = assess_lds + (long)wave * plspm::assess_wave_doubles(P, L);
     double *mu = isd + P, *v = mu + P, *lam = v + P, *bm = lam + P, *bg = bm + L, *bt = bg + L, *bs = bt + L, *pa = bs + L, *pg = pa + L, *pt = pg + L, *win = pt + L;
     const double* __restrict__ M = a.mom.gram + b * a.mom.gstride;
     ASSESS_MARK(0);

@@ -10,6 +10,7 @@
 
 #include "../../include/plspm_hip_test.h"
 #include "gram_route.h"
+#include "derived_route.h"
 #include "group_route.h"
 #include "options.h"
 
@@ -168,35 +169,19 @@ struct plspm_model {
     int64_t cv_reps = 0; int cv_k = 0;       // ... the last plspm_cv_device call whose folds, moments and records are on the handle (0: none)
     Buf jack_rows, jack_status, jack_iters, jack_io;      // plspm_jackknife_device: its records, status and iteration counts (buffers of their own: the bootstrap's survive the call), the statistics' out block
     int64_t jack_G = 0;                      // ... the last plspm_jackknife_device call whose records are on the handle (0: none)
-    // measurement-model assessment of a plain bootstrap's replicates (kernels_assess.h; plspm_assess_*): records [assess_B x (A + 2)] in a buffer of their own,
-    // indexed by the replicate's position in the whole call
-    bool assess_on = false;                  // plspm_assess_enable
-    Buf assess_rows, derived_fit;            // ... the replicates' records; the full-sample problem and its records of every stage (plspm_assess_fit, plspm_plsc_fit, plspm_modelfit_fit, plspm_geodesic_fit)
-    int64_t assess_B = 0;                    // ... the last plain bootstrap whose assessment records are on the handle (0: none)
-    // consistent PLS of a plain bootstrap's replicates (kernels_plsc.h; plspm_plsc_*): records [plsc_B x (R + npairs + 2)] in a buffer of their own, indexed like
-    // the assessment records, which are written whenever these are (the PLSc kernel reads them)
-    bool plsc_on = false;                    // plspm_plsc_enable
+    // The records derived from a plain bootstrap's replicates (plspm_derived.hip; the stages, what each reads and its record: derived_route.h kDerivedStage): per stage
+    // its switch (plspm_<stage>_enable), the replicates' records [B x (width + 2)] in a buffer of their own, indexed by the replicate's position in the whole call, and
+    // the last plain bootstrap whose records of the stage are on the handle (0: none).  A stage's records are written whenever those of a stage that reads them are.
+    struct DerivedRecords { bool on = false; Buf rows; int64_t B = 0; };
+    DerivedRecords derived[plspm::kDerivedStages];
+    Buf derived_fit;                         // the full-sample problem and its records of the stages one plspm_<stage>_fit takes (derived_route.h derived_fit_layout)
+    // consistent PLS, and the model fit and geodesic discrepancy behind it: one factor mask for the three
     std::vector<uint8_t> plsc_factor;        // ... the factor mask [L] it was enabled with (the default mask until then)
-    Buf plsc_rows, plsc_side, plsc_mask;     // ... the replicates' records; a pass's side output of assess_kernel [nb x 3 L]; the mask on the device
-    int64_t plsc_B = 0;                      // ... the last plain bootstrap whose PLSc records are on the handle (0: none)
-    // model fit of a plain bootstrap's replicates (kernels_modelfit.h; plspm_modelfit_*): records [modelfit_B x 6] in a buffer of their own, indexed like the PLSc
-    // records, which are written whenever these are (the model-fit kernel reads them); the factor mask is PLSc's
-    bool modelfit_on = false;                // plspm_modelfit_enable
-    Buf modelfit_rows;                       // ... the replicates' records
-    int64_t modelfit_B = 0;                  // ... the last plain bootstrap whose model-fit records are on the handle (0: none)
-    // geodesic discrepancy of a plain bootstrap's replicates (kernels_geodesic.h; plspm_geodesic_*): records [geodesic_B x 4] in a buffer of their own, indexed like
-    // the model-fit records, which are written whenever these are (the geodesic kernel reads their status); the factor mask is PLSc's
-    bool geodesic_on = false;                // plspm_geodesic_enable
-    Buf geodesic_rows;                       // ... the replicates' records
-    int64_t geodesic_B = 0;                  // ... the last plain bootstrap whose geodesic records are on the handle (0: none)
-    // structural-model assessment of a plain bootstrap's replicates (kernels_structural.h; plspm_structural_*): records [structural_B x (2 n_dir + n_spec + 2)] in a
-    // buffer of their own, indexed like the assessment records, which are written whenever these are (the structural kernel reads their lv_cor); a branch of its own
-    // behind the assessment, beside PLSc and what follows it.  The direct paths and the chains are enumerated once, at plspm_structural_enable
-    bool structural_on = false;              // plspm_structural_enable
+    Buf plsc_side, plsc_mask;                // ... a pass's side output of assess_kernel [nb x 3 L]; the mask on the device
+    // structural-model assessment: the direct paths and the chains are enumerated once, at plspm_structural_enable
     bool structural_listed = false;          // ... the lists below describe this handle's path matrix
     std::vector<int> struct_dir_from, struct_dir_to, struct_chain_off, struct_chain_nodes;      // [n_dir] x 2, [n_spec + 1], [chain_off[n_spec]]
-    Buf structural_rows, structural_desc;    // ... the replicates' records; dir_from | dir_to | chain_off | chain_eff on the device (structural_core.h StructDesc)
-    int64_t structural_B = 0;                // ... the last plain bootstrap whose structural records are on the handle (0: none)
+    Buf structural_desc;                     // ... dir_from | dir_to | chain_off | chain_eff on the device (structural_core.h StructDesc)
     // MICOM records of a permutation call's splits (kernels_micom.h; plspm_micom_*): records [micom_B x (3 L + 2)] in a buffer of their own, indexed by the
     // permutation's position in the call; the pooled inputs (u, the diagonal blocks of R_0; plspm_micom.hip micom_prepare) once per upload
     bool micom_on = false;                   // plspm_micom_enable
@@ -263,7 +248,7 @@ inline bool keeps_records(const BatchCall& c) { return c.kind == BatchCall::JACK
 inline bool pairs_problems(const BatchCall& c) { return c.kind == BatchCall::PERMUTATION; }
 // The handle kinds the two-group tests, the cross-validation, the jackknife, the assessment and MICOM cover.
 inline bool plain_metric(const plspm_model* m) { return !m->nonmetric && !m->categorical && !m->n_ind && !m->nmx_K && !m->stage1 && !m->stage2; }
-// (which plain bootstrap gets assessment, PLSc, model-fit and geodesic records: plspm_derived.hip derived_begin)
+// (which plain bootstrap gets derived records: plspm_derived.hip derived_begin)
 
 // The records on a handle, and the one place that voids them.  A batch call voids whatever went with the bootstrap records it replaces (REC_ROWS itself only
 // when it writes the handle's own `rows`); plspm_bootstrap_store replaces the bootstrap records from the host; an upload voids everything.
@@ -271,10 +256,15 @@ enum : unsigned { REC_ROWS = 1, REC_CV = 2, REC_ASSESS = 4, REC_MICOM = 8, REC_J
 inline void void_records(plspm_model* m, unsigned which) {
     if (which & REC_ROWS) m->rows_B = 0;
     if (which & REC_CV) m->cv_reps = 0;
-    if (which & REC_ASSESS) m->assess_B = m->structural_B = 0;      // (the structural records go with the assessment records they were computed from)
     if (which & REC_MICOM) m->micom_B = 0;
     if (which & REC_JACK) m->jack_G = 0;
-    if (which & REC_PLSC) m->plsc_B = m->modelfit_B = m->geodesic_B = 0;      // (the model-fit and geodesic records go with the PLSc records they were computed from)
+    // REC_ASSESS / REC_PLSC: that stage's records, and with them those of every stage that was computed from them (derived_route.h kDerivedStage: a stage's
+    // records go when a stage it reads goes, and a row reads rows before it).  PLSc reads the assessment, so REC_ASSESS takes every derived record with it and
+    // REC_PLSC those from PLSc on; every caller names the two together.
+    static_assert(plspm::kDerivedStage[plspm::STAGE_PLSC].reads & plspm::stage_bit(plspm::STAGE_ASSESS), "REC_ASSESS voids the PLSc records and what follows them");
+    int gone = (which & REC_ASSESS ? plspm::stage_bit(plspm::STAGE_ASSESS) : 0) | (which & REC_PLSC ? plspm::stage_bit(plspm::STAGE_PLSC) : 0);
+    for (int s = 0; s < plspm::kDerivedStages; ++s)
+        if (gone & (plspm::stage_bit(s) | plspm::kDerivedStage[s].reads)) { gone |= plspm::stage_bit(s); m->derived[s].B = 0; }
 }
 // (an entry point voids its own kind's records before it prepares the call -- plspm_cv_device REC_CV, plspm_jackknife_device REC_JACK -- and sets the count
 //  again behind the driver; so does plspm_bootstrap() with REC_ASSESS, which every one of its sub-batches voids here once more)

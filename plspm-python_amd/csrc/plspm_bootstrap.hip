@@ -25,7 +25,7 @@ struct BatchRun {
     BatchCall& call;
     BatchShape shape; BatchOptions opts; BatchPlan plan;
     int R;                                               // record pitch
-    int chain; int64_t chain_base;                       // the derived records (plspm_derived.hip): depth of the chain, position of the call's first record
+    int chain; int64_t chain_base;                       // the derived records (plspm_derived.hip): the stages that run, position of the call's first record
     double* rows_out; plspm_model::Buf *status_buf, *iters_buf;
 };
 // ... and of one pass: problems [b0, b0 + nb), what the int8 Gram left, what batch_chunk made of it, where the solver writes

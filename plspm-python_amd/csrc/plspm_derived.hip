@@ -1,11 +1,12 @@
-// plspm_derived.hip -- host side, part 10: the records derived from a plain bootstrap's replicates.  One chain of per-replicate kernels behind the metric
-// solver, each stage reading the replicate's moment matrix, its bootstrap record and the record the stage before it wrote:
+// plspm_derived.hip -- host side, part 10: the records derived from a plain bootstrap's replicates.  Per-replicate kernels behind the metric solver, each stage
+// reading the replicate's moment matrix, its bootstrap record and the records of the stages derived_route.h's table says it reads:
 //     assessment (plspm_assess_*)  ->  consistent PLS (plspm_plsc_*, 5o)  ->  model fit (plspm_modelfit_*, 5p)  ->  geodesic discrepancy (plspm_geodesic_*, 5q)
 //                                                \->  structural-model assessment (plspm_structural_*, 5r)
-// A call runs the chain to the depth of the deepest stage that is enabled; the structural stage is a branch off the assessment: it needs depth 1 and nothing else, runs
-// whether or not the deeper stages do, and touches no record of theirs.  The batch driver carries one opaque int per call: the depth, and kBranchStructural for the
-// branch (chain_depth / chain_branch below take it apart).  The batch driver (plspm_bootstrap.hip) sees three calls -- derived_begin,
-// derived_launch, derived_commit (host_internal.h) --; the full-sample records (plspm_*_fit) are the same chain on one problem.
+// derived_route.h decides -- derived_plan once per call and per pass: the stages that run (the enabled ones and what they read), each one's record pitch, waves,
+// LDS and grid, what the LDS refuses --; this unit only carries it out.  The batch driver (plspm_bootstrap.hip) carries the set of running stages as one int
+// through three calls -- derived_begin, derived_launch, derived_commit (host_internal.h) --; the full-sample records (plspm_*_fit) are the same launches on one
+// problem, laid out by derived_fit_layout.  The handle keeps a stage's switch, records and count in m->derived[stage] (model.h).
+// A further stage is a row of kDerivedStage, a launcher in kLaunch, and a block of entry points at the end.
 // Kernels: kernels_assess.h, kernels_plsc.h, kernels_modelfit.h, kernels_geodesic.h (their shared opening: kernels_moments.h), kernels_structural.h.
 #include "wave_launch.h"
 
@@ -16,27 +17,32 @@
 #include "kernels_geodesic.h"
 #include "kernels_structural.h"
 
-static int assess_width(const plspm_model* m) { return 4 * m->L + 3 * (m->L * (m->L - 1) / 2); }
-static int plsc_width(const plspm_model* m) { return plspm_row_width(m) + m->L * (m->L - 1) / 2; }
-static int modelfit_width(const plspm_model*) { return MODELFIT_WIDTH; }
-static int geodesic_width(const plspm_model*) { return GEODESIC_WIDTH; }
-static int structural_width(const plspm_model* m) { return m->structural_listed ? 2 * (int)m->struct_dir_from.size() + (int)m->struct_chain_off.size() - 1 : 0; }
+static_assert(kDerivedStage[STAGE_ASSESS].waves == ASSESS_WAVES && kDerivedStage[STAGE_STRUCTURAL].waves == STRUCTURAL_WAVES && kDerivedStage[STAGE_PLSC].waves == PLSC_WAVES &&
+                  kDerivedStage[STAGE_MODELFIT].waves == MODELFIT_WAVES && kDerivedStage[STAGE_GEODESIC].waves == GEODESIC_WAVES,
+              "derived_route.h plans the workgroups the kernels are compiled for");
 
-// The stages in chain order, then the branch: the replicates' records [count x (width + 2)].  A further stage is a row here, a launcher and its place in chain_launch.
-constexpr int kStages = 5, kStructural = 4;                     // stages 0 .. 3 are the chain (depth 1 .. 4), kStructural the branch off stage 0
-constexpr int kBranchStructural = 8;                            // the call's opaque chain value: depth | kBranchStructural
-static inline int chain_depth(int chain) { return chain & (kBranchStructural - 1); }
-static inline bool chain_branch(int chain) { return (chain & kBranchStructural) != 0; }
-static const struct Stage { plspm_model::Buf plspm_model::*rows; int64_t plspm_model::*count; int (*width)(const plspm_model*); } kStage[kStages] = {
-    {&plspm_model::assess_rows, &plspm_model::assess_B, assess_width},
-    {&plspm_model::plsc_rows, &plspm_model::plsc_B, plsc_width},
-    {&plspm_model::modelfit_rows, &plspm_model::modelfit_B, modelfit_width},
-    {&plspm_model::geodesic_rows, &plspm_model::geodesic_B, geodesic_width},
-    {&plspm_model::structural_rows, &plspm_model::structural_B, structural_width},
-};
-static inline int stage_stride(const plspm_model* m, int s) { return kStage[s].width(m) + 2; }
+static const char kPlainOnly[] = ": plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)";
 
-// ---- the launchers: `nb` problems, their moment matrices `mom` (dense, or tile-packed), their bootstrap records at `rows` (row_stride 0: one problem).  One wave per problem.
+static DerivedShape derived_shape(const plspm_model* m) {
+    const bool listed = m->structural_listed;
+    return {m->P, m->L, m->kmax, plspm_row_width(m), listed ? (int)m->struct_dir_from.size() : 0, listed ? (int)m->struct_chain_off.size() - 1 : 0};
+}
+static int derived_enabled(const plspm_model* m) {
+    int on = 0;
+    for (int s = 0; s < kDerivedStages; ++s) on |= m->derived[s].on ? stage_bit(s) : 0;
+    return on;
+}
+static int stage_width(const plspm_model* m, int s) { return m ? kDerivedStage[s].width(derived_shape(m)) : 0; }      // (plspm_*_width of no handle: 0)
+
+// ---- the launchers: the problems of one ChainCall -- their moment matrices `mom` (dense, or tile-packed), their bootstrap records at `rows` (row_stride 0: one
+// problem), stage s's records at out[s] [nb x (width + 2)], `side`: null, or [nb x 3 L] for the assessment's hand-over to PLSc.  One wave per problem, as `pl` has it.
+struct ChainCall { long nb; bool dense; MomentLayout mom; const double* rows; long row_stride; double* out[kDerivedStages]; double* side; };
+// one stage's launch as the plan has it; nclocks / print: its phase clocks (wave_launch.h)
+template <class Args>
+static int launch_stage(plspm_model* m, void (*k)(Args), Args& a, const DerivedLaunch& g, int nclocks, void (*print)(const long long*)) {
+    return launch_wave_per_problem(m, k, a, g.waves, g.lds, g.grid, &a.marks, nclocks, print);
+}
+
 static void print_assess_clocks(const long long* h) {
     fprintf(stderr, "[plspm assess clocks] per-MV values %lld  diagonal blocks %lld  block pairs %lld  total %lld\n", h[1] - h[0], h[2] - h[1], h[3] - h[2], h[3] - h[0]);
 }
@@ -57,121 +63,102 @@ static void print_geodesic_clocks(const long long* h) {      // (reduction, trid
             h[1] - h[0], h[2] - h[1], (h[3] - h[2]) + (h[6] - h[5]), (h[4] - h[3]) + (h[7] - h[6]), (h[5] - h[4]) + (h[8] - h[7]), h[9] - h[8], h[9] - h[0]);
 }
 
-// -> out [nb x (A + 2)]; side: null, or [nb x 3 L] for the PLSc kernel (kernels_assess.h)
-static int launch_assess(plspm_model* m, long nb, bool dense, const MomentLayout& mom, const double* rows, long row_stride, double* out, double* side) {
+// -> out [nb x (A + 2)], and the hand-over where PLSc runs (kernels_assess.h)
+static int launch_assess(plspm_model* m, const DerivedPlan& pl, const ChainCall& c) {
     AssessArgs a{};
-    a.mom = mom;
+    a.mom = c.mom;
     a.L = m->L; a.R = plspm_row_width(m);
     a.boff = m->d_boff; a.lvof = m->d_lvof; a.mode = m->d_mode;
-    a.rows = rows; a.row_stride = row_stride; a.out = out; a.nb = nb; a.side = side;
-    return launch_wave_per_problem(m, dense ? assess_kernel<true> : assess_kernel<false>, a, nb, ASSESS_WAVES, assess_wave_doubles(m->P, m->L), &a.marks, 4, print_assess_clocks);
+    a.rows = c.rows; a.row_stride = c.row_stride; a.out = c.out[STAGE_ASSESS]; a.nb = c.nb; a.side = c.side;
+    return launch_stage(m, c.dense ? assess_kernel<true> : assess_kernel<false>, a, pl.stage[STAGE_ASSESS], 4, print_assess_clocks);
 }
 
-// the assessment records `assess` and the side output `side` that launch_assess wrote -> out [nb x (W + 2)] (kernels_plsc.h)
-static int launch_plsc(plspm_model* m, long nb, bool dense, const MomentLayout& mom, const double* rows, long row_stride, const double* assess, const double* side, double* out) {
-    PlscArgs a{};
-    a.mom = mom;
-    a.R = plspm_row_width(m); a.A = assess_width(m);
-    a.md = make_desc(m);
-    a.factor = (const unsigned char*)m->plsc_mask.p;
-    a.rows = rows; a.row_stride = row_stride; a.assess = assess; a.side = side; a.out = out; a.nb = nb;
-    return launch_wave_per_problem(m, dense ? plsc_kernel<true> : plsc_kernel<false>, a, nb, PLSC_WAVES, plsc_ws_doubles(m->P, m->L, m->kmax), &a.marks, 16, print_plsc_clocks);
-}
-
-// the PLSc records `plsc` that launch_plsc wrote -> out [nb x 6] (kernels_modelfit.h)
-static int launch_modelfit(plspm_model* m, long nb, bool dense, const MomentLayout& mom, const double* rows, long row_stride, const double* plsc, double* out) {
-    ModelfitArgs a{};
-    a.mom = mom;
-    a.R = plspm_row_width(m);
-    a.md = make_desc(m);
-    a.factor = (const unsigned char*)m->plsc_mask.p;
-    a.rows = rows; a.row_stride = row_stride; a.plsc = plsc; a.out = out; a.nb = nb;
-    return launch_wave_per_problem(m, dense ? modelfit_kernel<true> : modelfit_kernel<false>, a, nb, MODELFIT_WAVES, modelfit_ws_doubles(m->P, m->L), &a.marks, 8, print_modelfit_clocks);
-}
-
-// the PLSc records `plsc` and the model-fit records `modelfit` before it -> out [nb x 4] (kernels_geodesic.h).  A wave's LDS slice grows with P^2: four waves per
-// workgroup where four slices fit, fewer beyond that, down to one.
-static int launch_geodesic(plspm_model* m, long nb, bool dense, const MomentLayout& mom, const double* rows, long row_stride, const double* plsc, const double* modelfit, double* out) {
-    GeodesicArgs a{};
-    a.mom = mom;
-    a.R = plspm_row_width(m);
-    a.md = make_desc(m);
-    a.factor = (const unsigned char*)m->plsc_mask.p;
-    a.rows = rows; a.row_stride = row_stride; a.plsc = plsc; a.modelfit = modelfit; a.out = out; a.nb = nb;
-    const long doubles = geodesic_ws_doubles(m->P, m->L);
-    const int waves = (int)std::max<long>(1, std::min<long>(GEODESIC_WAVES, (long)(kMaxLds / sizeof(double)) / doubles));
-    return launch_wave_per_problem(m, dense ? geodesic_kernel<true> : geodesic_kernel<false>, a, nb, waves, doubles, &a.marks, 16, print_geodesic_clocks);
-}
-
-// One wave's slots of regression scratch and the waves of a workgroup: a slot per index in flight (LVs, then direct paths), 64 at the most, fewer where the LDS does not
-// hold them beside four waves' rc; fewer waves where four slices with one slot each do not fit.  false: one wave with one slot needs more than 160 KiB.
-static bool structural_geometry(const plspm_model* m, int* waves, int* nslots) {
-    const long cap = (long)(kMaxLds / sizeof(double)), slot = std::max<long>(1, structural_slot_doubles(m->kmax));
-    const long want = std::max<long>(1, std::min<long>(64, std::max<long>(m->L, (long)m->struct_dir_from.size())));
-    for (int w = STRUCTURAL_WAVES; w >= 1; w >>= 1) {
-        const long fit = (cap / w - structural_ws_doubles(m->L, m->kmax, 0)) / slot;
-        if (fit >= 1) { *waves = w; *nslots = (int)std::min(want, fit); return true; }
-    }
-    return false;
-}
-
-// the assessment records `assess` that launch_assess wrote -> out [nb x (S + 2)] (kernels_structural.h).  No moment matrix: one kernel for both layouts.
-static int launch_structural(plspm_model* m, long nb, const double* rows, long row_stride, const double* assess, double* out) {
+// the assessment records -> out [nb x (S + 2)] (kernels_structural.h).  No moment matrix: one kernel for both layouts.  The kernel is told its workgroup's waves
+// and a wave's regression slots.
+static int launch_structural(plspm_model* m, const DerivedPlan& pl, const ChainCall& c) {
     StructuralArgs a{};
-    a.R = plspm_row_width(m); a.A = assess_width(m);
+    a.R = plspm_row_width(m); a.A = stage_width(m, STAGE_ASSESS);
     a.md = make_desc(m);
     const int n_dir = (int)m->struct_dir_from.size(), n_spec = (int)m->struct_chain_off.size() - 1;
     const int* d = (const int*)m->structural_desc.p;
     a.sd = StructDesc{n_dir, n_spec, d, d + n_dir, d + 2 * n_dir, d + 2 * n_dir + n_spec + 1};
-    if (!structural_geometry(m, &a.waves, &a.nslots)) return fail(m, PLSPM_E_LIMIT, "structural assessment: rc and one regression slot of one replicate need more than 160 KiB of LDS");
-    a.rows = rows; a.row_stride = row_stride; a.assess = assess; a.out = out; a.nb = nb;
-    return launch_wave_per_problem(m, structural_kernel, a, nb, a.waves, structural_ws_doubles(m->L, m->kmax, a.nslots), &a.marks, 8, print_structural_clocks);
+    a.waves = pl.stage[STAGE_STRUCTURAL].waves; a.nslots = pl.nslots;
+    a.rows = c.rows; a.row_stride = c.row_stride; a.assess = c.out[STAGE_ASSESS]; a.out = c.out[STAGE_STRUCTURAL]; a.nb = c.nb;
+    return launch_stage(m, structural_kernel, a, pl.stage[STAGE_STRUCTURAL], 8, print_structural_clocks);
 }
 
-// The chain to `depth` on `nb` problems: stage s writes out[s] and reads out[s - 1]; `side` [nb x 3 L] takes the assessment's hand-over to PLSc (depth >= 2); the
-// structural branch (out[kStructural] not null) reads out[0] and runs behind the assessment, before the deeper stages.
-static int chain_launch(plspm_model* m, int depth, long nb, bool dense, const double* gram, const double* rows, long row_stride, double* const* out, double* side) {
-    const MomentLayout mom = moment_layout(m, dense, gram);
-    int rc;
-    if ((rc = launch_assess(m, nb, dense, mom, rows, row_stride, out[0], depth >= 2 ? side : nullptr))) return rc;
-    if (out[kStructural] && (rc = launch_structural(m, nb, rows, row_stride, out[0], out[kStructural]))) return rc;
-    if (depth >= 2 && (rc = launch_plsc(m, nb, dense, mom, rows, row_stride, out[0], side, out[1]))) return rc;
-    if (depth >= 3 && (rc = launch_modelfit(m, nb, dense, mom, rows, row_stride, out[1], out[2]))) return rc;
-    if (depth >= 4 && (rc = launch_geodesic(m, nb, dense, mom, rows, row_stride, out[1], out[2], out[3]))) return rc;
-    return 0;
+// the assessment records and the hand-over -> out [nb x (W + 2)] (kernels_plsc.h)
+static int launch_plsc(plspm_model* m, const DerivedPlan& pl, const ChainCall& c) {
+    PlscArgs a{};
+    a.mom = c.mom;
+    a.R = plspm_row_width(m); a.A = stage_width(m, STAGE_ASSESS);
+    a.md = make_desc(m);
+    a.factor = (const unsigned char*)m->plsc_mask.p;
+    a.rows = c.rows; a.row_stride = c.row_stride; a.assess = c.out[STAGE_ASSESS]; a.side = c.side; a.out = c.out[STAGE_PLSC]; a.nb = c.nb;
+    return launch_stage(m, c.dense ? plsc_kernel<true> : plsc_kernel<false>, a, pl.stage[STAGE_PLSC], 16, print_plsc_clocks);
+}
+
+// the PLSc records -> out [nb x 6] (kernels_modelfit.h)
+static int launch_modelfit(plspm_model* m, const DerivedPlan& pl, const ChainCall& c) {
+    ModelfitArgs a{};
+    a.mom = c.mom;
+    a.R = plspm_row_width(m);
+    a.md = make_desc(m);
+    a.factor = (const unsigned char*)m->plsc_mask.p;
+    a.rows = c.rows; a.row_stride = c.row_stride; a.plsc = c.out[STAGE_PLSC]; a.out = c.out[STAGE_MODELFIT]; a.nb = c.nb;
+    return launch_stage(m, c.dense ? modelfit_kernel<true> : modelfit_kernel<false>, a, pl.stage[STAGE_MODELFIT], 8, print_modelfit_clocks);
+}
+
+// the PLSc and the model-fit records -> out [nb x 4] (kernels_geodesic.h).  The kernel reads its workgroup's waves from the launch.
+static int launch_geodesic(plspm_model* m, const DerivedPlan& pl, const ChainCall& c) {
+    GeodesicArgs a{};
+    a.mom = c.mom;
+    a.R = plspm_row_width(m);
+    a.md = make_desc(m);
+    a.factor = (const unsigned char*)m->plsc_mask.p;
+    a.rows = c.rows; a.row_stride = c.row_stride; a.plsc = c.out[STAGE_PLSC]; a.modelfit = c.out[STAGE_MODELFIT]; a.out = c.out[STAGE_GEODESIC]; a.nb = c.nb;
+    return launch_stage(m, c.dense ? geodesic_kernel<true> : geodesic_kernel<false>, a, pl.stage[STAGE_GEODESIC], 16, print_geodesic_clocks);
+}
+
+static int (*const kLaunch[kDerivedStages])(plspm_model*, const DerivedPlan&, const ChainCall&) = {launch_assess, launch_structural, launch_plsc, launch_modelfit, launch_geodesic};
+
+// the running stages' launches, in the table's order
+static int chain_launch(plspm_model* m, const DerivedPlan& pl, const ChainCall& c) {
+    int rc = 0;
+    for (int s = 0; s < kDerivedStages && !rc; ++s)
+        if (pl.runs & stage_bit(s)) rc = kLaunch[s](m, pl, c);
+    return rc;
 }
 
 // ---- the batch driver's three calls (host_internal.h)
-int derived_begin(plspm_model* m, const BatchCall& call, int* depth) {
-    *depth = 0;
+int derived_begin(plspm_model* m, const BatchCall& call, int* runs) {
+    *runs = 0;
     const bool own = !call.rows_out;
-    if (!(own || call.chain_off >= 0) || !plain_metric(m) || call.kind != BatchCall::PLAIN || call.moments_out) return 0;
-    const bool branch = m->structural_on;
-    const int d = m->geodesic_on ? 4 : (m->modelfit_on ? 3 : (m->plsc_on ? 2 : ((m->assess_on || branch) ? 1 : 0)));
-    if (d >= 4 && geodesic_ws_doubles(m->P, m->L) * sizeof(double) > kMaxLds)      // (refused before anything of the call runs; launch_geodesic's allow_lds says the same)
-        return fail(m, PLSPM_E_LIMIT, "geodesic discrepancy: the two P x P triangles of one replicate need more than 160 KiB of LDS");
-    for (int s = 0; own && s < d; ++s)
-        if (int rc = ensure(m, m->*kStage[s].rows, (size_t)call.B * stage_stride(m, s) * sizeof(double))) return rc;
-    if (own && branch)
-        if (int rc = ensure(m, m->structural_rows, (size_t)call.B * stage_stride(m, kStructural) * sizeof(double))) return rc;
-    *depth = d | (branch ? kBranchStructural : 0);
+    const int on = derived_enabled(m);
+    if (!on || !(own || call.chain_off >= 0) || !plain_metric(m) || call.kind != BatchCall::PLAIN || call.moments_out) return 0;
+    const DerivedPlan pl = derived_plan(derived_shape(m), on, (long)call.B);
+    if (pl.refused >= 0)      // (before anything of the call runs)
+        return fail(m, PLSPM_E_LIMIT, std::string(kDerivedStage[pl.refused].title) + ": " + kDerivedStage[pl.refused].lds_need);
+    for (int s = 0; own && s < kDerivedStages; ++s)
+        if (pl.runs & stage_bit(s))
+            if (int rc = ensure(m, m->derived[s].rows, (size_t)call.B * pl.stage[s].stride * sizeof(double))) return rc;
+    *runs = pl.runs;
     return 0;
 }
 
-int derived_launch(plspm_model* m, int chain, long nb, int64_t pos, bool dense, const double* gram, const double* rows, long row_stride) {
-    const int depth = chain_depth(chain);
-    if (!depth) return 0;
-    if (depth >= 2)      // (the assessment's side output lasts for one pass)
-        if (int rc = ensure(m, m->plsc_side, (size_t)nb * 3 * m->L * sizeof(double))) return rc;
-    double* out[kStages] = {};
-    for (int s = 0; s < depth; ++s) out[s] = (double*)(m->*kStage[s].rows).p + pos * stage_stride(m, s);
-    if (chain_branch(chain)) out[kStructural] = (double*)m->structural_rows.p + pos * stage_stride(m, kStructural);
-    return chain_launch(m, depth, nb, dense, gram, rows, row_stride, out, (double*)m->plsc_side.p);
+int derived_launch(plspm_model* m, int runs, long nb, int64_t pos, bool dense, const double* gram, const double* rows, long row_stride) {
+    if (!runs) return 0;
+    const DerivedPlan pl = derived_plan(derived_shape(m), runs, nb);
+    if (int rc = ensure(m, m->plsc_side, pl.side_bytes)) return rc;      // (the assessment's hand-over lasts for one pass)
+    ChainCall c{nb, dense, moment_layout(m, dense, gram), rows, row_stride, {}, pl.side_bytes ? (double*)m->plsc_side.p : nullptr};
+    for (int s = 0; s < kDerivedStages; ++s)
+        if (pl.runs & stage_bit(s)) c.out[s] = (double*)m->derived[s].rows.p + pos * pl.stage[s].stride;
+    return chain_launch(m, pl, c);
 }
 
-void derived_commit(plspm_model* m, int chain, int64_t B) {
-    for (int s = 0; s < chain_depth(chain); ++s) m->*kStage[s].count = B;
-    if (chain_branch(chain)) m->structural_B = B;
+void derived_commit(plspm_model* m, int runs, int64_t B) {
+    for (int s = 0; s < kDerivedStages; ++s)
+        if (runs & stage_bit(s)) m->derived[s].B = B;
 }
 
 // ---- the factor mask of PLSc and model fit
@@ -203,209 +190,7 @@ static int plsc_take_mask(plspm_model* m, const uint8_t* factor, const std::stri
     return plsc_set_mask(m, f);
 }
 
-// The full-sample record of stage `depth` (plspm_assess_fit, plspm_plsc_fit, plspm_modelfit_fit, plspm_geodesic_fit), or of the structural branch behind depth 1
-// (plspm_structural_fit): the chain of a replicate on the moments of all uploaded rows and plspm_fit's solver problem, from depth 2 on with the handle's mask (the
-// default mask if none was ever set).  h: that stage's record [width + 2].
-static int chain_full_sample(plspm_model* m, int depth, std::vector<double>& h, const std::string& who, bool branch = false) {
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, who + ": plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, who + ": no data uploaded");
-    HIPCHK(m, hipSetDevice(m->device));
-    int rc;
-    if (depth >= 2 && m->plsc_factor.empty() && (rc = plsc_set_mask(m, plsc_default_mask(m)))) return rc;
-    // [record RS | the stages' records, width + 2 each | side 3 L | status, iterations (int)]
-    size_t doubles = (size_t)plspm_row_stride(m) + 3 * (size_t)m->L;
-    for (int s = 0; s < depth; ++s) doubles += (size_t)stage_stride(m, s);
-    if (branch) doubles += (size_t)stage_stride(m, kStructural);
-    if ((rc = ensure(m, m->derived_fit, doubles * sizeof(double) + 2 * sizeof(int)))) return rc;
-    double* const rec = (double*)m->derived_fit.p;
-    double* out[kStages] = {};
-    double* next = rec + plspm_row_stride(m);
-    for (int s = 0; s < depth; ++s) { out[s] = next; next += stage_stride(m, s); }
-    if (branch) { out[kStructural] = next; next += stage_stride(m, kStructural); }
-    const int last = branch ? kStructural : depth - 1;
-    if ((rc = solve_full_sample(m, rec, (int*)(next + 3 * m->L)))) return rc;      // (its moments: tile-packed, in m->gram)
-    if ((rc = chain_launch(m, depth, 1, false, (const double*)m->gram.p, rec, 0, out, next))) return rc;
-    HIPCHK(m, hipGetLastError());
-    h.resize((size_t)stage_stride(m, last));
-    HIPCHK(m, hipMemcpyAsync(h.data(), out[last], h.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(m, hipStreamSynchronize(m->stream));
-    return 0;
-}
-
-// ---- measurement-model assessment (DESIGN.md 5m): per-replicate records [alpha | rho_a | rho_c | ave | htmt | htmt2 | lv_cor | status | iterations]
-static SideRecords assess_records(const plspm_model* m) {
-    return {m->assess_rows, m->assess_B, assess_width(m), false,
-            ": no assessment records on this handle (plspm_assess_enable, then a plain bootstrap; an upload or a later call replaced them)",
-            ": B differs from the last assessed bootstrap on this handle", ": range exceeds the last assessed bootstrap's replicates",
-            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no assessment records, so there is no bca"};
-}
-
-extern "C" {
-
-int plspm_assess_enable(plspm_model_t* m, int32_t on) {
-    if (!m) return fail(m, PLSPM_E_ARG, "plspm_assess_enable: no handle");
-    if (on && !plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_assess_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    m->assess_on = on != 0;
-    return 0;
-}
-
-int32_t plspm_assess_width(const plspm_model_t* m) { return m ? assess_width(m) : 0; }
-
-int plspm_assess_fit(plspm_model_t* m, double* out, int32_t* status) {
-    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_assess_fit: bad arguments");
-    std::vector<double> h;
-    if (int rc = chain_full_sample(m, 1, h, "plspm_assess_fit")) return rc;
-    const int A = assess_width(m);
-    std::copy(h.begin(), h.begin() + A, out);
-    if (status) *status = (h[A] == h[A]) ? (int32_t)h[A] : -1;
-    return 0;
-}
-
-int plspm_assess_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    return m ? side_fetch(m, assess_records(m), first, count, out, status, "plspm_assess_fetch") : fail(m, PLSPM_E_ARG, "plspm_assess_fetch: bad arguments");
-}
-
-int plspm_assess_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    return m ? side_summary(m, assess_records(m), B, original, summary, n_used, "plspm_assess_summary") : fail(m, PLSPM_E_ARG, "plspm_assess_summary: bad arguments (1 <= B <= 2^30)");
-}
-
-int plspm_assess_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    return m ? side_intervals(m, assess_records(m), B, original, method, level, out, n_used, "plspm_assess_intervals") : fail(m, PLSPM_E_ARG, "plspm_assess_intervals: bad arguments (1 <= B <= 2^30)");
-}
-
-}  // extern "C"
-
-// ---- consistent PLS (DESIGN.md 5o): per-replicate records [weights | r2 | total | direct | loadings | lv_cor_c | status | iterations]
-static SideRecords plsc_records(const plspm_model* m) {
-    return {m->plsc_rows, m->plsc_B, plsc_width(m), false,
-            ": no PLSc records on this handle (plspm_plsc_enable, then a plain bootstrap; an upload or a later call replaced them)",
-            ": B differs from the last PLSc bootstrap on this handle", ": range exceeds the last PLSc bootstrap's replicates",
-            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no PLSc records, so there is no bca"};
-}
-
-extern "C" {
-
-int plspm_plsc_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) {
-    if (!m) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: no handle");
-    if (!on) { m->plsc_on = false; return 0; }
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_plsc_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (int rc = factor ? plsc_take_mask(m, factor, "plspm_plsc_enable") : plsc_set_mask(m, plsc_default_mask(m))) return rc;
-    m->plsc_on = true;
-    return 0;
-}
-
-int32_t plspm_plsc_width(const plspm_model_t* m) { return m ? plsc_width(m) : 0; }
-
-int plspm_plsc_fit(plspm_model_t* m, double* out, int32_t* status) {
-    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_plsc_fit: bad arguments");
-    std::vector<double> h;
-    if (int rc = chain_full_sample(m, 2, h, "plspm_plsc_fit")) return rc;
-    const int W = plsc_width(m);
-    std::copy(h.begin(), h.begin() + W, out);
-    if (status) *status = (h[W] == h[W]) ? (int32_t)h[W] : -1;
-    return 0;
-}
-
-int plspm_plsc_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    return m ? side_fetch(m, plsc_records(m), first, count, out, status, "plspm_plsc_fetch") : fail(m, PLSPM_E_ARG, "plspm_plsc_fetch: bad arguments");
-}
-
-int plspm_plsc_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    return m ? side_summary(m, plsc_records(m), B, original, summary, n_used, "plspm_plsc_summary") : fail(m, PLSPM_E_ARG, "plspm_plsc_summary: bad arguments (1 <= B <= 2^30)");
-}
-
-int plspm_plsc_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    return m ? side_intervals(m, plsc_records(m), B, original, method, level, out, n_used, "plspm_plsc_intervals") : fail(m, PLSPM_E_ARG, "plspm_plsc_intervals: bad arguments (1 <= B <= 2^30)");
-}
-
-}  // extern "C"
-
-// plspm_modelfit_enable, plspm_geodesic_enable: the stage's switch, and the handle's one factor mask (NULL keeps it)
-static int enable_keeping_mask(plspm_model* m, int32_t on, const uint8_t* factor, bool plspm_model::*flag, const std::string& who) {
-    if (!m) return fail(m, PLSPM_E_ARG, who + ": no handle");
-    if (!on) { m->*flag = false; return 0; }
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, who + ": plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (factor) { if (int rc = plsc_take_mask(m, factor, who)) return rc; }
-    else if (m->plsc_factor.empty()) { if (int rc = plsc_set_mask(m, plsc_default_mask(m))) return rc; }      // (NULL keeps the handle's mask)
-    m->*flag = true;
-    return 0;
-}
-
-// ---- model fit (DESIGN.md 5p): per-replicate records [srmr_sat | d_uls_sat | srmr_est | d_uls_est | status | iterations]
-static SideRecords modelfit_records(const plspm_model* m) {
-    return {m->modelfit_rows, m->modelfit_B, MODELFIT_WIDTH, true,
-            ": no model-fit records on this handle (plspm_modelfit_enable, then a plain bootstrap; an upload or a later call replaced them)",
-            ": B differs from the last model-fit bootstrap on this handle", ": range exceeds the last model-fit bootstrap's replicates",
-            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no model-fit records, so there is no bca"};
-}
-
-extern "C" {
-
-int plspm_modelfit_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) { return enable_keeping_mask(m, on, factor, &plspm_model::modelfit_on, "plspm_modelfit_enable"); }
-
-int32_t plspm_modelfit_width(const plspm_model_t* m) { return m ? MODELFIT_WIDTH : 0; }
-
-int plspm_modelfit_fit(plspm_model_t* m, double* out, int32_t* status) {
-    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_modelfit_fit: bad arguments");
-    std::vector<double> h;
-    if (int rc = chain_full_sample(m, 3, h, "plspm_modelfit_fit")) return rc;
-    std::copy(h.begin(), h.begin() + MODELFIT_WIDTH, out);
-    if (status) *status = (int32_t)h[MODELFIT_WIDTH];
-    return 0;
-}
-
-int plspm_modelfit_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    return m ? side_fetch(m, modelfit_records(m), first, count, out, status, "plspm_modelfit_fetch") : fail(m, PLSPM_E_ARG, "plspm_modelfit_fetch: bad arguments");
-}
-
-int plspm_modelfit_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    return m ? side_summary(m, modelfit_records(m), B, original, summary, n_used, "plspm_modelfit_summary") : fail(m, PLSPM_E_ARG, "plspm_modelfit_summary: bad arguments (1 <= B <= 2^30)");
-}
-
-int plspm_modelfit_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    return m ? side_intervals(m, modelfit_records(m), B, original, method, level, out, n_used, "plspm_modelfit_intervals") : fail(m, PLSPM_E_ARG, "plspm_modelfit_intervals: bad arguments (1 <= B <= 2^30)");
-}
-
-}  // extern "C"
-
-// ---- geodesic discrepancy (DESIGN.md 5q): per-replicate records [d_g_sat | d_g_est | status | iterations]
-static SideRecords geodesic_records(const plspm_model* m) {
-    return {m->geodesic_rows, m->geodesic_B, GEODESIC_WIDTH, true,
-            ": no geodesic records on this handle (plspm_geodesic_enable, then a plain bootstrap; an upload or a later call replaced them)",
-            ": B differs from the last geodesic bootstrap on this handle", ": range exceeds the last geodesic bootstrap's replicates",
-            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no geodesic records, so there is no bca"};
-}
-
-extern "C" {
-
-int plspm_geodesic_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) { return enable_keeping_mask(m, on, factor, &plspm_model::geodesic_on, "plspm_geodesic_enable"); }
-
-int32_t plspm_geodesic_width(const plspm_model_t* m) { return m ? GEODESIC_WIDTH : 0; }
-
-int plspm_geodesic_fit(plspm_model_t* m, double* out, int32_t* status) {
-    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_geodesic_fit: bad arguments");
-    std::vector<double> h;
-    if (int rc = chain_full_sample(m, 4, h, "plspm_geodesic_fit")) return rc;
-    std::copy(h.begin(), h.begin() + GEODESIC_WIDTH, out);
-    if (status) *status = (int32_t)h[GEODESIC_WIDTH];
-    return 0;
-}
-
-int plspm_geodesic_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    return m ? side_fetch(m, geodesic_records(m), first, count, out, status, "plspm_geodesic_fetch") : fail(m, PLSPM_E_ARG, "plspm_geodesic_fetch: bad arguments");
-}
-
-int plspm_geodesic_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    return m ? side_summary(m, geodesic_records(m), B, original, summary, n_used, "plspm_geodesic_summary") : fail(m, PLSPM_E_ARG, "plspm_geodesic_summary: bad arguments (1 <= B <= 2^30)");
-}
-
-int plspm_geodesic_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    return m ? side_intervals(m, geodesic_records(m), B, original, method, level, out, n_used, "plspm_geodesic_intervals") : fail(m, PLSPM_E_ARG, "plspm_geodesic_intervals: bad arguments (1 <= B <= 2^30)");
-}
-
-}  // extern "C"
-
-// ---- structural-model assessment (DESIGN.md 5r): per-replicate records [f2 | vif | specific | status | iterations]
+// ---- structural-model assessment: the lists
 constexpr long kStructuralMaxChains = 4096;
 
 // The direct paths (effect pairs with a path of their own, in pair order) and the chains (pair order, then lexicographic by node sequence) of the handle's path matrix,
@@ -469,37 +254,151 @@ static int structural_list(plspm_model* m, const std::string& who) {
     HIPCHK(m, hipMemcpy(m->structural_desc.p, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice));
     m->struct_dir_from = dir_from; m->struct_dir_to = dir_to; m->struct_chain_off = chain_off; m->struct_chain_nodes = nodes;
     m->structural_listed = true;
-    int waves, nslots;
-    if (!structural_geometry(m, &waves, &nslots)) {
+    if (derived_plan(derived_shape(m), stage_bit(STAGE_STRUCTURAL), 1).refused == STAGE_STRUCTURAL) {
         m->structural_listed = false;
-        return fail(m, PLSPM_E_LIMIT, who + ": rc and one regression slot of one replicate need more than 160 KiB of LDS");
+        return fail(m, PLSPM_E_LIMIT, who + ": " + kDerivedStage[STAGE_STRUCTURAL].lds_need);
     }
     return 0;
 }
 
-static SideRecords structural_records(const plspm_model* m) {
-    return {m->structural_rows, m->structural_B, structural_width(m), true,
-            ": no structural records on this handle (plspm_structural_enable, then a plain bootstrap; an upload or a later call replaced them)",
-            ": B differs from the last structural bootstrap on this handle", ": range exceeds the last structural bootstrap's replicates",
-            ": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no structural records, so there is no bca"};
+// ---- what the entry points of every stage share
+// The full-sample record of stage `target` (plspm_*_fit): the launches of a replicate, for the stages `target` takes, on the moments of all uploaded rows and
+// plspm_fit's solver problem; where PLSc runs, with the handle's mask (the default mask if none was ever set).  h: that stage's record [width + 2].
+static int chain_full_sample(plspm_model* m, int target, std::vector<double>& h, const std::string& who) {
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, who + kPlainOnly);
+    int rc;
+    if (target == STAGE_STRUCTURAL && (rc = structural_list(m, who))) return rc;
+    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, who + ": no data uploaded");
+    HIPCHK(m, hipSetDevice(m->device));
+    const DerivedFitLayout lay = derived_fit_layout(derived_shape(m), target);
+    if ((lay.plan.runs & stage_bit(STAGE_PLSC)) && m->plsc_factor.empty() && (rc = plsc_set_mask(m, plsc_default_mask(m)))) return rc;
+    if ((rc = ensure(m, m->derived_fit, lay.bytes))) return rc;
+    double* const rec = (double*)m->derived_fit.p;
+    ChainCall c{1, false, {}, rec, 0, {}, lay.plan.side_bytes ? rec + lay.o_side : nullptr};
+    for (int s = 0; s < kDerivedStages; ++s)
+        if (lay.o_stage[s] >= 0) c.out[s] = rec + lay.o_stage[s];
+    if ((rc = solve_full_sample(m, rec, (int*)(rec + lay.o_ints)))) return rc;      // (its moments: tile-packed, in m->gram)
+    c.mom = moment_layout(m, false, (const double*)m->gram.p);
+    if ((rc = chain_launch(m, lay.plan, c))) return rc;
+    HIPCHK(m, hipGetLastError());
+    h.resize((size_t)lay.plan.stage[target].stride);
+    HIPCHK(m, hipMemcpyAsync(h.data(), c.out[target], h.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return 0;
+}
+
+// a stage's records as the side-record functions take them (host_internal.h SideRecords), its four messages from the table's two words
+static SideRecords stage_records(const plspm_model* m, int s) {
+    static const std::vector<std::string> msg = [] {
+        std::vector<std::string> v;
+        for (const DerivedStageRow& r : kDerivedStage) {
+            const std::string noun = r.noun, last = r.last;
+            v.push_back(": no " + noun + " records on this handle (plspm_" + r.api + "_enable, then a plain bootstrap; an upload or a later call replaced them)");
+            v.push_back(": B differs from the last " + last + " bootstrap on this handle");
+            v.push_back(": range exceeds the last " + last + " bootstrap's replicates");
+            v.push_back(": method must be 0 (percentile), 1 (basic) or 2 (bc); the jackknife writes no " + noun + " records, so there is no bca");
+        }
+        return v;
+    }();
+    const plspm_model::DerivedRecords& d = m->derived[s];
+    return {d.rows, d.B, stage_width(m, s), kDerivedStage[s].plain_only, msg[4 * s].c_str(), msg[4 * s + 1].c_str(), msg[4 * s + 2].c_str(), msg[4 * s + 3].c_str()};
+}
+
+// plspm_*_enable: the handle check, the off switch and the plain-metric refusal they share; `prepare`: what the stage needs on the handle before it is switched on
+static int stage_enable(plspm_model* m, int s, int32_t on, const std::string& who, int (*prepare)(plspm_model*, const uint8_t*, const std::string&) = nullptr,
+                        const uint8_t* factor = nullptr) {
+    if (!m) return fail(m, PLSPM_E_ARG, who + ": no handle");
+    if (!on) { m->derived[s].on = false; return 0; }
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, who + kPlainOnly);
+    if (prepare) { if (int rc = prepare(m, factor, who)) return rc; }
+    m->derived[s].on = true;
+    return 0;
+}
+// plspm_plsc_enable: the handle's one factor mask is set whenever the stage is switched on (NULL: the default mask)
+static int mask_set(plspm_model* m, const uint8_t* factor, const std::string& who) { return factor ? plsc_take_mask(m, factor, who) : plsc_set_mask(m, plsc_default_mask(m)); }
+// plspm_modelfit_enable, plspm_geodesic_enable: NULL keeps the handle's mask
+static int mask_keep(plspm_model* m, const uint8_t* factor, const std::string& who) {
+    if (factor) return plsc_take_mask(m, factor, who);
+    return m->plsc_factor.empty() ? plsc_set_mask(m, plsc_default_mask(m)) : 0;
+}
+static int lists_built(plspm_model* m, const uint8_t*, const std::string& who) { return structural_list(m, who); }
+
+// (the status word of a record is an integer status as a double in every stage -- the solver's, or the stage's own --, never NaN; the guard keeps the cast defined
+//  whatever a kernel may come to write)
+static int stage_fit(plspm_model* m, int s, double* out, int32_t* status, const char* who) {
+    if (!m || !out) return fail(m, PLSPM_E_ARG, std::string(who) + ": bad arguments");
+    std::vector<double> h;
+    if (int rc = chain_full_sample(m, s, h, who)) return rc;
+    const size_t W = h.size() - 2;
+    std::copy(h.begin(), h.begin() + W, out);
+    if (status) *status = (h[W] == h[W]) ? (int32_t)h[W] : -1;
+    return 0;
+}
+static int stage_fetch(plspm_model* m, int s, int64_t first, int64_t count, double* out, int32_t* status, const char* who) {
+    return m ? side_fetch(m, stage_records(m, s), first, count, out, status, who) : fail(m, PLSPM_E_ARG, std::string(who) + ": bad arguments");
+}
+static int stage_summary(plspm_model* m, int s, int64_t B, const double* original, double* summary, int64_t* n_used, const char* who) {
+    return m ? side_summary(m, stage_records(m, s), B, original, summary, n_used, who) : fail(m, PLSPM_E_ARG, std::string(who) + ": bad arguments (1 <= B <= 2^30)");
+}
+static int stage_intervals(plspm_model* m, int s, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used, const char* who) {
+    return m ? side_intervals(m, stage_records(m, s), B, original, method, level, out, n_used, who) : fail(m, PLSPM_E_ARG, std::string(who) + ": bad arguments (1 <= B <= 2^30)");
 }
 
 extern "C" {
 
-int plspm_structural_enable(plspm_model_t* m, int32_t on) {
-    if (!m) return fail(m, PLSPM_E_ARG, "plspm_structural_enable: no handle");
-    if (!on) { m->structural_on = false; return 0; }
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_structural_enable: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (int rc = structural_list(m, "plspm_structural_enable")) return rc;
-    m->structural_on = true;
-    return 0;
+// ---- measurement-model assessment (DESIGN.md 5m): per-replicate records [alpha | rho_a | rho_c | ave | htmt | htmt2 | lv_cor | status | iterations]
+int plspm_assess_enable(plspm_model_t* m, int32_t on) { return stage_enable(m, STAGE_ASSESS, on, "plspm_assess_enable"); }
+int32_t plspm_assess_width(const plspm_model_t* m) { return stage_width(m, STAGE_ASSESS); }
+int plspm_assess_fit(plspm_model_t* m, double* out, int32_t* status) { return stage_fit(m, STAGE_ASSESS, out, status, "plspm_assess_fit"); }
+int plspm_assess_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) { return stage_fetch(m, STAGE_ASSESS, first, count, out, status, "plspm_assess_fetch"); }
+int plspm_assess_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) { return stage_summary(m, STAGE_ASSESS, B, original, summary, n_used, "plspm_assess_summary"); }
+int plspm_assess_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
+    return stage_intervals(m, STAGE_ASSESS, B, original, method, level, out, n_used, "plspm_assess_intervals");
 }
 
-int32_t plspm_structural_width(const plspm_model_t* m) { return m ? structural_width(m) : 0; }
+// ---- consistent PLS (DESIGN.md 5o): per-replicate records [weights | r2 | total | direct | loadings | lv_cor_c | status | iterations]
+int plspm_plsc_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) { return stage_enable(m, STAGE_PLSC, on, "plspm_plsc_enable", mask_set, factor); }
+int32_t plspm_plsc_width(const plspm_model_t* m) { return stage_width(m, STAGE_PLSC); }
+int plspm_plsc_fit(plspm_model_t* m, double* out, int32_t* status) { return stage_fit(m, STAGE_PLSC, out, status, "plspm_plsc_fit"); }
+int plspm_plsc_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) { return stage_fetch(m, STAGE_PLSC, first, count, out, status, "plspm_plsc_fetch"); }
+int plspm_plsc_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) { return stage_summary(m, STAGE_PLSC, B, original, summary, n_used, "plspm_plsc_summary"); }
+int plspm_plsc_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
+    return stage_intervals(m, STAGE_PLSC, B, original, method, level, out, n_used, "plspm_plsc_intervals");
+}
+
+// ---- model fit (DESIGN.md 5p): per-replicate records [srmr_sat | d_uls_sat | srmr_est | d_uls_est | status | iterations]
+int plspm_modelfit_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) { return stage_enable(m, STAGE_MODELFIT, on, "plspm_modelfit_enable", mask_keep, factor); }
+int32_t plspm_modelfit_width(const plspm_model_t* m) { return stage_width(m, STAGE_MODELFIT); }
+int plspm_modelfit_fit(plspm_model_t* m, double* out, int32_t* status) { return stage_fit(m, STAGE_MODELFIT, out, status, "plspm_modelfit_fit"); }
+int plspm_modelfit_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) { return stage_fetch(m, STAGE_MODELFIT, first, count, out, status, "plspm_modelfit_fetch"); }
+int plspm_modelfit_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) { return stage_summary(m, STAGE_MODELFIT, B, original, summary, n_used, "plspm_modelfit_summary"); }
+int plspm_modelfit_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
+    return stage_intervals(m, STAGE_MODELFIT, B, original, method, level, out, n_used, "plspm_modelfit_intervals");
+}
+
+// ---- geodesic discrepancy (DESIGN.md 5q): per-replicate records [d_g_sat | d_g_est | status | iterations]
+int plspm_geodesic_enable(plspm_model_t* m, int32_t on, const uint8_t* factor) { return stage_enable(m, STAGE_GEODESIC, on, "plspm_geodesic_enable", mask_keep, factor); }
+int32_t plspm_geodesic_width(const plspm_model_t* m) { return stage_width(m, STAGE_GEODESIC); }
+int plspm_geodesic_fit(plspm_model_t* m, double* out, int32_t* status) { return stage_fit(m, STAGE_GEODESIC, out, status, "plspm_geodesic_fit"); }
+int plspm_geodesic_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) { return stage_fetch(m, STAGE_GEODESIC, first, count, out, status, "plspm_geodesic_fetch"); }
+int plspm_geodesic_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) { return stage_summary(m, STAGE_GEODESIC, B, original, summary, n_used, "plspm_geodesic_summary"); }
+int plspm_geodesic_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
+    return stage_intervals(m, STAGE_GEODESIC, B, original, method, level, out, n_used, "plspm_geodesic_intervals");
+}
+
+// ---- structural-model assessment (DESIGN.md 5r): per-replicate records [f2 | vif | specific | status | iterations]
+int plspm_structural_enable(plspm_model_t* m, int32_t on) { return stage_enable(m, STAGE_STRUCTURAL, on, "plspm_structural_enable", lists_built); }
+int32_t plspm_structural_width(const plspm_model_t* m) { return stage_width(m, STAGE_STRUCTURAL); }
+int plspm_structural_fit(plspm_model_t* m, double* out, int32_t* status) { return stage_fit(m, STAGE_STRUCTURAL, out, status, "plspm_structural_fit"); }
+int plspm_structural_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) { return stage_fetch(m, STAGE_STRUCTURAL, first, count, out, status, "plspm_structural_fetch"); }
+int plspm_structural_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) { return stage_summary(m, STAGE_STRUCTURAL, B, original, summary, n_used, "plspm_structural_summary"); }
+int plspm_structural_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
+    return stage_intervals(m, STAGE_STRUCTURAL, B, original, method, level, out, n_used, "plspm_structural_intervals");
+}
 
 int plspm_structural_paths(plspm_model_t* m, int32_t* n_dir, int32_t* dir_from, int32_t* dir_to, int32_t* n_spec, int32_t* chain_off, int32_t* chain_nodes) {
     if (!m) return fail(m, PLSPM_E_ARG, "plspm_structural_paths: no handle");
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_structural_paths: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, std::string("plspm_structural_paths") + kPlainOnly);
     if (int rc = structural_list(m, "plspm_structural_paths")) return rc;
     if (n_dir) *n_dir = (int32_t)m->struct_dir_from.size();
     if (n_spec) *n_spec = (int32_t)m->struct_chain_off.size() - 1;
@@ -508,30 +407,6 @@ int plspm_structural_paths(plspm_model_t* m, int32_t* n_dir, int32_t* dir_from, 
     if (chain_off) std::copy(m->struct_chain_off.begin(), m->struct_chain_off.end(), chain_off);
     if (chain_nodes) std::copy(m->struct_chain_nodes.begin(), m->struct_chain_nodes.end(), chain_nodes);
     return 0;
-}
-
-int plspm_structural_fit(plspm_model_t* m, double* out, int32_t* status) {
-    if (!m || !out) return fail(m, PLSPM_E_ARG, "plspm_structural_fit: bad arguments");
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_structural_fit: plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
-    if (int rc = structural_list(m, "plspm_structural_fit")) return rc;
-    std::vector<double> h;
-    if (int rc = chain_full_sample(m, 1, h, "plspm_structural_fit", true)) return rc;
-    const int S = structural_width(m);
-    std::copy(h.begin(), h.begin() + S, out);
-    if (status) *status = (h[S] == h[S]) ? (int32_t)h[S] : -1;
-    return 0;
-}
-
-int plspm_structural_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status) {
-    return m ? side_fetch(m, structural_records(m), first, count, out, status, "plspm_structural_fetch") : fail(m, PLSPM_E_ARG, "plspm_structural_fetch: bad arguments");
-}
-
-int plspm_structural_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used) {
-    return m ? side_summary(m, structural_records(m), B, original, summary, n_used, "plspm_structural_summary") : fail(m, PLSPM_E_ARG, "plspm_structural_summary: bad arguments (1 <= B <= 2^30)");
-}
-
-int plspm_structural_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used) {
-    return m ? side_intervals(m, structural_records(m), B, original, method, level, out, n_used, "plspm_structural_intervals") : fail(m, PLSPM_E_ARG, "plspm_structural_intervals: bad arguments (1 <= B <= 2^30)");
 }
 
 }  // extern "C"

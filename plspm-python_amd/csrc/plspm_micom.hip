@@ -43,7 +43,7 @@ int launch_micom(plspm_model* m, long nperm, bool dense, const double* gram, con
     a.rows = rows; a.row_stride = plspm_row_stride(m);
     a.u = (const double*)m->micom_pool.p; a.r0 = a.u + 2L * m->P;
     a.out = out; a.np = nperm;
-    if (int rc = launch_wave_per_problem(m, dense ? micom_kernel<true> : micom_kernel<false>, a, nperm, MICOM_WAVES, micom_wave_doubles(kb))) return rc;
+    if (int rc = launch_wave_per_problem(m, dense ? micom_kernel<true> : micom_kernel<false>, a, MICOM_WAVES, (size_t)MICOM_WAVES * micom_wave_doubles(kb) * sizeof(double), (nperm + MICOM_WAVES - 1) / MICOM_WAVES)) return rc;
     m->last_micom_layout = dense ? 1 : 2;
     return 0;
 }

@@ -99,7 +99,10 @@ PLSPM_HD long chol_block_doubles(int k) { return 2L * k * k; }
 PLSPM_HD long workspace_small_doubles(int P, int L, int kmax, int n_chol) {
     return 7L * P + (long)P * L + 8L * L * L + 4L * L + (long)L * regression_scratch_doubles(kmax) + n_chol + 8 + 16;
 }
-PLSPM_HD int cov_ld(int P) { return (P + 1) | 1; }      // S carries the ones row/column P as well (column sums, n)
+// one wave's LDS slice of the assessment kernel (kernels_assess.h; its launch: derived_route.h): 1 / s, mu, v, lambda [P] | m, g, v'Rv, sign [L] | the three pair sums
+// of the current block [L] | one window of three columns [64]
+PLSPM_HD long assess_wave_doubles(int P, int L) { return 4L * P + 7L * L + 3 * 64; }
+PLSPM_HD int cov_ld(int P) { return (P + 1) | 1; }     // S carries the ones row/column P as well (column sums, n)
 PLSPM_HD long cov_doubles(int P) { return (long)(P + 1) * cov_ld(P); }
 
 PLSPM_HD void carve_small(Workspace& ws, double* base, int P, int L, int kmax, int n_chol) {

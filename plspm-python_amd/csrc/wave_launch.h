@@ -9,19 +9,19 @@ inline MomentLayout moment_layout(const plspm_model* m, bool dense, const double
     return {gram, dense ? cov_doubles(m->P) : packed_size(m->T), dense ? cov_ld(m->P) : m->T, m->P};
 }
 
-// `nproblems` waves of kernel `k` on `a`, `waves` per workgroup, `wave_doubles` of LDS each.  marks / nclocks / print: the phase clocks of problem 0 (`make marks`;
-// never in the release library) -- the field of `a` that takes their device buffer, how many there are, and what writes them to stderr; null / 0: none.
+// `grid` workgroups of kernel `k` on `a`, `waves` waves and `lds` bytes of dynamic LDS each (the derived records: as derived_route.h plans them).  marks / nclocks /
+// print: the phase clocks of problem 0 (`make marks`; never in the release library) -- the field of `a` that takes their device buffer, how many there are, and what
+// writes them to stderr; null / 0: none.
 template <class Args>
-int launch_wave_per_problem(plspm_model* m, void (*k)(Args), Args& a, long nproblems, int waves, long wave_doubles, long long** marks = nullptr, int nclocks = 0,
+int launch_wave_per_problem(plspm_model* m, void (*k)(Args), Args& a, int waves, size_t lds, long grid, long long** marks = nullptr, int nclocks = 0,
                             void (*print)(const long long*) = nullptr) {
-    const size_t lds = (size_t)waves * wave_doubles * sizeof(double);
     if (int rc = allow_lds(m, (const void*)k, lds)) return rc;
 #ifdef PLSPM_DEBUG_MARKS
     if (marks) HIPCHK(m, plspm_dmalloc((void**)marks, nclocks * sizeof(long long)));
 #endif
     {
         ProfScope ps(m, PLSPM_K_ASSESS);
-        hipLaunchKernelGGL(k, dim3((unsigned)((nproblems + waves - 1) / waves)), dim3(64 * waves), lds, m->stream, a);
+        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * waves), lds, m->stream, a);
     }
 #ifdef PLSPM_DEBUG_MARKS
     if (marks) {

@@ -21,6 +21,7 @@
 #include "../../plspm-python_amd/csrc/gram_route.h"
 #include "../../plspm-python_amd/csrc/batch_route.h"
 #include "../../plspm-python_amd/csrc/fit_route.h"
+#include "../../plspm-python_amd/csrc/derived_route.h"
 #include "../../plspm-python_amd/csrc/group_route.h"
 #include "../../plspm-python_amd/csrc/options.h"
 
@@ -703,6 +704,28 @@ void hostemu_fit_plan(const long* sh, const long* call, long* out) {
                       (long)p.stage_need, p.solver.s_in_lds, p.solver.small_in_lds, (long)p.solver.lds, b.s_in_lds, b.small_in_lds, (long)b.lds, FIT_INT_ITERS, FIT_INT_STATUS, FIT_INT_SIGN};
     for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) out[i] = v[i];
 }
+
+// The plan of the derived records (csrc/derived_route.h derived_plan).  sh: P, L, kmax, R, n_dir, n_spec; enabled: the switches, bit s = stage s in launch order
+// (assessment, structural, PLSc, model fit, geodesic); nb problems.  out: runs, nslots, side_bytes, refused, then per stage stride, waves, wave_doubles, lds, grid
+// (zeros for a stage that does not run).  target >= 0: behind them derived_fit_layout of that stage -- runs, o_stage per stage, o_side, o_ints, bytes.
+void hostemu_derived_plan(const long* sh, long enabled, long nb, long target, long* out) {
+    const DerivedShape s{(int)sh[0], (int)sh[1], (int)sh[2], (int)sh[3], (int)sh[4], (int)sh[5]};
+    const DerivedPlan p = derived_plan(s, (int)enabled, nb);
+    long* v = out;
+    *v++ = p.runs; *v++ = p.nslots; *v++ = (long)p.side_bytes; *v++ = p.refused;
+    for (const DerivedLaunch& k : p.stage) { *v++ = k.stride; *v++ = k.waves; *v++ = k.wave_doubles; *v++ = (long)k.lds; *v++ = k.grid; }
+    if (target < 0) return;
+    const DerivedFitLayout f = derived_fit_layout(s, (int)target);
+    *v++ = f.plan.runs;
+    for (long o : f.o_stage) *v++ = o;
+    *v++ = f.o_side; *v++ = f.o_ints; *v++ = (long)f.bytes;
+}
+// a row of the stage table: what it reads (bits), waves, min_waves, plain_only; word 0 .. 4: api, noun, last, title, lds_need ("" for none)
+void hostemu_derived_stage(int s, long* out) {
+    const DerivedStageRow& r = kDerivedStage[s];
+    out[0] = r.reads; out[1] = r.waves; out[2] = r.min_waves; out[3] = r.plain_only;
+}
+const char* hostemu_derived_word(int s, int which) { const DerivedStageRow& r = kDerivedStage[s]; const char* w[] = {r.api, r.noun, r.last, r.title, r.lds_need}; return w[which] ? w[which] : ""; }
 
 // The option table (csrc/options.h) over a bare Tune of default options.  set: `name` = `value` on a Tune that holds `start` in that option (-1 << 31: its default) and
 // defaults elsewhere; out: option_set's result (0 ok, 1 out of range, 2 experiments only, 3 unknown name), the effect bits it reported (1 planes, 2 statistics), how many
