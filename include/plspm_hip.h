@@ -475,6 +475,41 @@ int plspm_jackknife_fetch(plspm_model_t* m, int64_t first, int64_t count, double
 int plspm_jackknife_stats(plspm_model_t* m, int64_t G, double* mean, double* std_error, double* accel, int64_t* n_used);
 
 /*
+ * ---- FIMIX-PLS (latent-class segmentation of the inner model) --------------------------------------------------------------------
+ * A finite mixture of inner-model regressions on the latent variable scores the last plspm_fit left on the handle (Y [N x L]).  With E the
+ * LVs that have predecessors (n_endo), pred(j) the predecessors of j and n_dir the number of direct paths, segment k of a problem of K segments models
+ *     y_ij = sum_{p in pred(j)} beta_kjp y_ip + e,   e ~ N(0, psi_kj)                       (no intercept; recursive model: Jacobian 1)
+ * and one problem is (K, an initial hard assignment of the rows to the K segments).  Iteration t = 1, 2, ...:
+ *   M-step on P^(t-1) (P^0: one-hot of the assignment): n_k = sum_i P_ik, rho_k = n_k / N, m_k[a,b] = sum_i P_ik y_ia y_ib; beta_kj solves
+ *     m_k[pred,pred] beta = m_k[pred,j] by the library's regression (pivot rule, minimum-norm answer for collinear predecessors);
+ *     psi_kj = (m_k[j,j] - beta_kj . m_k[pred,j]) / n_k.  The problem ends with PLSPM_SINGULAR at that t when an n_k < 1, a psi_kj <= 1e-10 m_k[j,j] / n_k
+ *     or a regression without an answer: its record is NaN.
+ *   E-step: a_ik = ln rho_k + sum_j [-1/2 ln(2 pi psi_kj) - r_ikj^2 / (2 psi_kj)], lse_i the log-sum-exp over k (row maximum subtracted),
+ *     lnL = sum_i lse_i, P_ik = exp(a_ik - lse_i), H = -sum_ik P_ik ln P_ik (0 ln 0 = 0).  PLSPM_NONFINITE (NaN record) when lnL is not finite.
+ *   Stop: PLSPM_OK when t >= 2 and |lnL^t - lnL^(t-1)| <= tol; PLSPM_NOT_CONVERGED at t = max_iter with the complete record of that t (tol = 0 runs
+ *     exactly max_iter iterations).
+ * Record, plspm_fimix_width() = 2 + kmax (1 + n_dir + n_endo) doubles:  lnL | H | rho[kmax] | beta[kmax][n_dir] | psi[kmax][n_endo]  -- beta in the
+ * direct-path order of plspm_structural_paths (from-major), psi in LV order, segments in the order the EM left them, NaN in the slots k >= K.
+ * Every sum runs in one fixed order: a call repeated on the same inputs gives the same bits.  Plain metric handles only (no non-metric scales, no
+ * missing values, not part of a two-stage pair): PLSPM_E_ARG otherwise.
+ *
+ * plspm_fimix_device: enqueues nprob problems, one workgroup each; k_of [nprob] host, 1..16; kmax >= every K (and <= 16); init [nprob*N] host, the segment
+ *   of every row (below its problem's K, else PLSPM_E_ARG), or NULL: row i of problem s goes to segment floor(u K) of the Philox draw keyed by
+ *   (seed, start_offset + s, i) (plspm_fimix_starts).  max_iter >= 1, tol >= 0.  PLSPM_E_STATE when the handle holds no scores of a fit on the rows now
+ *   resident (plspm_fit with `scores`; an upload voids them); PLSPM_E_LIMIT when one problem's state exceeds a workgroup's 160 KiB of LDS.
+ *   *d_out [nprob * (width + 2)] (values | status | iterations) / *d_status / *d_iters [nprob]: device pointers owned by the handle, valid until the
+ *   next plspm_fimix_device or upload (any may be NULL).
+ * plspm_fimix_fetch: host copy of problems [first, first + count) of the last call: out [count*width], status, iters [count] (any may be NULL).
+ * plspm_fimix_posteriors: the posteriors P [N x K] of one stored problem's parameters (row-major), out [N*K] host.
+ * PLSPM_E_STATE from the last two without a call on the handle (none yet; an upload voids it).
+ */
+int plspm_fimix_device(plspm_model_t* m, int64_t nprob, const int32_t* k_of, int32_t kmax, uint64_t seed, int64_t start_offset, const uint8_t* init, int32_t max_iter,
+                       double tol, void** d_out, void** d_status, void** d_iters);
+int32_t plspm_fimix_width(const plspm_model_t* m, int32_t kmax);
+int plspm_fimix_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status, int32_t* iters);
+int plspm_fimix_posteriors(plspm_model_t* m, int64_t problem, double* out);
+
+/*
  * ---- Bootstrap confidence intervals ---------------------------------------------------------------------------------------------
  * Two-sided intervals at a chosen level on bootstrap records in HBM, every handle kind; d_rows / B / stride as plspm_bootstrap_summary (NULL: the
  * handle's last records; else a device buffer in the record layout, e.g. the gathered records of all GPUs).  Per result column c over the m

@@ -53,6 +53,10 @@ int plspm_stratified_draws(uint64_t seed, int64_t rep, int64_t N, const uint8_t*
  * PLSPM_E_ARG unless 2 <= k <= 256 and N >= k. */
 int plspm_cv_folds(uint64_t seed, int64_t rep, int64_t N, int32_t k, uint8_t* fold);
 
+/* The initial segments the on-device draw of plspm_fimix_device gives the rows in start `start` (host-side mirror, for tests): segment [N] bytes below K.
+ * PLSPM_E_ARG unless 1 <= K <= 16. */
+int plspm_fimix_starts(uint64_t seed, int64_t start, int64_t N, int32_t K, uint8_t* segment);
+
 /* Test seam: what the last plspm_cv_device call (reps, k: that call's) left on the handle -- fold [reps*N] the fold id of every row, order [reps*N]
  * the rows of every repetition in fold order (ascending inside a fold), offsets [reps*(k+1)]: fold f of repetition r is order[r*N + offsets[r*(k+1) + f]
  * .. r*N + offsets[r*(k+1) + f + 1]).  Any output may be NULL. */

@@ -169,6 +169,13 @@ struct plspm_model {
     int64_t cv_reps = 0; int cv_k = 0;       // ... the last plspm_cv_device call whose folds, moments and records are on the handle (0: none)
     Buf jack_rows, jack_status, jack_iters, jack_io;      // plspm_jackknife_device: its records, status and iteration counts (buffers of their own: the bootstrap's survive the call), the statistics' out block
     int64_t jack_G = 0;                      // ... the last plspm_jackknife_device call whose records are on the handle (0: none)
+    // FIMIX-PLS (plspm_fimix.hip): the fit's scores describe the rows that are resident now (plspm_fit with scores sets it, an upload clears it); the last
+    // plspm_fimix_device call's records [nprob x (width + 2)], status and iteration counts in buffers of their own, its descriptor tables, segment counts and explicit starts
+    bool scores_valid = false;
+    Buf fimix_rows, fimix_status, fimix_iters, fimix_desc, fimix_k, fimix_init, fimix_post;
+    int64_t fimix_nprob = 0;                 // ... problems of that call (0: none)
+    int fimix_kmax = 0;                      // ... and its kmax
+    std::vector<int> fimix_k_of;             // ... and every problem's K
     // The records derived from a plain bootstrap's replicates (plspm_derived.hip; the stages, what each reads and its record: derived_route.h kDerivedStage): per stage
     // its switch (plspm_<stage>_enable), the replicates' records [B x (width + 2)] in a buffer of their own, indexed by the replicate's position in the whole call, and
     // the last plain bootstrap whose records of the stage are on the handle (0: none).  A stage's records are written whenever those of a stage that reads them are.
@@ -282,6 +289,7 @@ inline void void_resident(plspm_model* m, bool replaced) {
     if (m->stage2) { m->stage2->codes_valid = false; m->stage2->ind8_valid = false; }
     void_records(m, REC_ALL);
     m->micom_pool_valid = false;
+    m->scores_valid = false; m->fimix_nprob = 0;      // (plspm_fimix.hip: the scores and the mixture records describe the old rows)
 }
 
 // The batch driver (plspm_bootstrap.hip): enqueue the call's problems on the handle's stream.  No host synchronisation for metric models.

@@ -56,3 +56,14 @@ __host__ __device__ __forceinline__ u32x4 strat_quad(uint64_t seed, uint64_t s, 
 __host__ __device__ __forceinline__ u32x4 cv_quad(uint64_t seed, uint64_t rep, uint32_t q) {
     return philox4x32_10(q, 3u, (uint32_t)rep, (uint32_t)(rep >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
 }
+
+// Initial segment of row i (0 <= i < N) in start `start` of FIMIX-PLS: word (i & 3) of Philox(counter = (i >> 2, 4, start), key = seed), mapped to
+// [0, K) by the high-word multiply, floor(u K) for u = word / 2^32.  Counter word 1 is 4: a stream of its own -- kernels_fimix.h, plspm_fimix_starts.
+__host__ __device__ __forceinline__ u32x4 fimix_quad(uint64_t seed, uint64_t start, uint32_t q) {
+    return philox4x32_10(q, 4u, (uint32_t)start, (uint32_t)(start >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+__host__ __device__ __forceinline__ int fimix_start_segment(uint64_t seed, uint64_t start, uint32_t i, uint32_t K) {
+    const u32x4 u = fimix_quad(seed, start, i >> 2);
+    const uint32_t j = i & 3u, word = j == 0 ? u.v[0] : j == 1 ? u.v[1] : j == 2 ? u.v[2] : u.v[3];      // (no indexed register array on the device)
+    return (int)mulhi32(word, K);
+}

@@ -334,6 +334,7 @@ int plspm_fit(plspm_model_t* m, const plspm_fit_result_t* out) {
     if ((rc = fit_reserve(m, pl, &so)) || (rc = dense_moments(m)) || (rc = fit_solve(m, so))) return rc;
     if (pl.call.want_scores && (rc = fit_scores(m, pl))) return rc;
     HIPCHK(m, hipGetLastError());
+    if (pl.call.want_scores) m->scores_valid = true;      // (plspm_fimix_device reads them where they are)
     if ((rc = fit_download(m, pl, out->scores))) return rc;
     // plspm_bootstrap_prepare ran before this fit: its column statistics are on the host now, so the digit planes are cut (enqueue only)
     // while the caller unpacks the fit -- the first bootstrap call finds them ready.  (A failure here is reported by that call, which retries.)

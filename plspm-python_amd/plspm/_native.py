@@ -32,6 +32,7 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_stratified_bootstrap_device", "plspm_stratified_pair_counts", "plspm_stratified_draws",
            "plspm_cv_folds", "plspm_cv_device", "plspm_cv_fold_ids", "plspm_cv_moments", "plspm_cv_targets", "plspm_cv_predict",
            "plspm_jackknife_device", "plspm_jackknife_fetch", "plspm_jackknife_stats", "plspm_bootstrap_intervals",
+           "plspm_fimix_device", "plspm_fimix_width", "plspm_fimix_fetch", "plspm_fimix_posteriors", "plspm_fimix_starts",
            "plspm_assess_enable", "plspm_assess_width", "plspm_assess_fit", "plspm_assess_fetch", "plspm_assess_summary", "plspm_assess_intervals",
            "plspm_plsc_enable", "plspm_plsc_width", "plspm_plsc_fit", "plspm_plsc_fetch", "plspm_plsc_summary", "plspm_plsc_intervals",
            "plspm_modelfit_enable", "plspm_modelfit_width", "plspm_modelfit_fit", "plspm_modelfit_fetch", "plspm_modelfit_summary", "plspm_modelfit_intervals",
@@ -130,6 +131,12 @@ def load():
     lib.plspm_jackknife_fetch.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.plspm_jackknife_stats.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(i64)]
     lib.plspm_bootstrap_intervals.argtypes = [vp, vp, i64, i32, vp, vp, i32, dbl, vp, ctypes.POINTER(i64)]
+    lib.plspm_fimix_starts.argtypes = [u64, i64, i64, i32, vp]
+    lib.plspm_fimix_device.argtypes = [vp, i64, vp, i32, u64, i64, vp, i32, dbl, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.plspm_fimix_width.restype = i32
+    lib.plspm_fimix_width.argtypes = [vp, i32]
+    lib.plspm_fimix_fetch.argtypes = [vp, i64, i64, vp, vp, vp]
+    lib.plspm_fimix_posteriors.argtypes = [vp, i64, vp]
     # the six families of side records (assessment, PLSc, model fit, geodesic discrepancy, structural assessment, MICOM): one set of signatures; only MICOM has no
     # full-sample record
     lib.plspm_structural_paths.argtypes = [vp, ctypes.POINTER(i32), vp, vp, ctypes.POINTER(i32), vp, vp]
@@ -245,6 +252,15 @@ def cv_folds(seed, rep, n, k):
     if rc:
         raise NativeBackendError("plspm_cv_folds failed (%d)" % rc)
     return fold
+
+
+def fimix_starts(seed, start, n, k):
+    """Host mirror of the on-device initial assignment of FIMIX-PLS: [n] uint8, the segment (below ``k``) of every row in start ``start``."""
+    segment = np.empty(n, dtype=np.uint8)
+    rc = load().plspm_fimix_starts(seed, start, n, k, _ptr(segment))
+    if rc:
+        raise NativeBackendError("plspm_fimix_starts failed (%d)" % rc)
+    return segment
 
 
 def i8_tile_plan(count_tiles, pair_tiles, cus=256, mix=True):
@@ -557,6 +573,44 @@ class NativeModel:
         used = ctypes.c_int64(0)
         self._check(self._lib.plspm_jackknife_stats(self._h, G, _ptr(mean), _ptr(se), _ptr(accel), ctypes.byref(used)), "plspm_jackknife_stats")
         return mean, se, accel, used.value
+
+    def fimix(self, k_of, kmax=None, seed=0, start_offset=0, init=None, max_iter=5000, tol=1e-10):
+        """Enqueue FIMIX-PLS problems on the scores the last ``fit`` left on the device (plspm_fimix_device): problem s has ``k_of[s]`` segments and starts
+        from ``init[s]`` ([nprob, N] uint8 segments) or, with ``init`` None, from the Philox draw keyed by (seed, start_offset + s).  Returns the device
+        pointers (records, status, iters)."""
+        k_of = np.ascontiguousarray(k_of, dtype=np.int32).ravel()
+        kmax = int(k_of.max()) if kmax is None else int(kmax)
+        if init is not None:
+            init = np.ascontiguousarray(init, dtype=np.uint8)
+            if init.shape != (len(k_of), self.N):
+                raise ValueError("init must have shape (nprob, N)")
+        d_out, d_st, d_it = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.plspm_fimix_device(self._h, len(k_of), _ptr(k_of), kmax, seed, start_offset, _ptr(init), int(max_iter), float(tol), ctypes.byref(d_out),
+                                                 ctypes.byref(d_st), ctypes.byref(d_it)), "plspm_fimix_device")
+        self.last_fimix = (len(k_of), kmax, k_of.copy())
+        return d_out.value, d_st.value, d_it.value
+
+    def fimix_width(self, kmax):
+        return int(self._lib.plspm_fimix_width(self._h, int(kmax)))
+
+    def fimix_fetch(self, first=0, count=None):
+        """Host copy of problems [first, first + count) of the last ``fimix`` call: (records [count, width], status, iters)."""
+        nprob, kmax, _ = getattr(self, "last_fimix", (0, 1, None))
+        if count is None:
+            count = nprob - first if nprob else 1      # (no call yet: the library says so)
+        rows = np.empty((max(count, 0), self.fimix_width(kmax)))
+        status = np.empty(max(count, 0), dtype=np.int32)
+        iters = np.empty(max(count, 0), dtype=np.int32)
+        self._check(self._lib.plspm_fimix_fetch(self._h, first, count, _ptr(rows), _ptr(status), _ptr(iters)), "plspm_fimix_fetch")
+        return rows, status, iters
+
+    def fimix_posteriors(self, problem):
+        """The posteriors [N, K] of the stored parameters of one problem of the last ``fimix`` call (plspm_fimix_posteriors)."""
+        nprob, _, k_of = getattr(self, "last_fimix", (0, 1, None))
+        K = int(k_of[problem]) if k_of is not None and 0 <= problem < nprob else 1
+        out = np.empty((self.N, K))
+        self._check(self._lib.plspm_fimix_posteriors(self._h, int(problem), _ptr(out)), "plspm_fimix_posteriors")
+        return out
 
     # ---- side records: the assessment, PLSc and model-fit records of a plain bootstrap and the MICOM records of a permutation call.  One C signature per
     # operation (plspm_<family>_enable / _width / _fit / _fetch / _summary / _intervals), so one implementation each; the public methods below name the family.
