@@ -724,6 +724,37 @@ int plspm_structural_fetch(plspm_model_t* m, int64_t first, int64_t count, doubl
 int plspm_structural_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
 int plspm_structural_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
 
+/* Moderation analysis by the two-stage approach (this project's definitions, csrc/moderation_core.h): does the effect of a predictor LV a on a
+ * target LV j depend on a moderator LV b?  A term is (a, b, j), three different LVs with the paths a -> j and b -> j in the model.  Stage 1 is the model as it
+ * stands.  Per data set (the full sample, or one replicate with its row multiplicities) the stage-1 scores y_l are those of the record's weights by the
+ * assessment's conventions (v normalised per block, the sign rule; mean 0, variance 1), the product z_t = y_a y_b is neither centred nor rescaled, and every
+ * target that has terms is regressed on its predecessors (LV order) and then its terms (term order) on the correlation matrix of those scores and products, by
+ * the library's own regression.  The products of a replicate need a pass over the rows: four kernels behind the metric solver of every pass.
+ * Record, width W = n_dir + 4 T + L:  direct2 [n_dir] (the order of plspm_structural_paths) | interaction [T] | f2 [T] (dropping the term alone) |
+ * slope_low [T] | slope_high [T] (direct2[a -> j] -/+ interaction: the simple slope one SD below / above the moderator's mean) | r2 [L]; status and iterations
+ * behind it as doubles (pitch W + 2).  A target without terms keeps the bootstrap record's direct and r2 entries bit for bit.  A replicate whose bootstrap status
+ * is not PLSPM_OK keeps that status and has NaN in all W values; otherwise PLSPM_SINGULAR where a regression reports failure and PLSPM_NONFINITE where a value
+ * is not finite (a product without variance, an R squared of 1); the values stand.  Plain metric handles only: PLSPM_E_ARG otherwise.
+ *
+ * plspm_moderation_enable: n_terms > 0: the terms (LV indices; at most 8, no two with the same pair and target) -- every later plspm_bootstrap /
+ *   plspm_bootstrap_device call on this handle also writes the moderation records of its replicates into a buffer of their own, indexed like the bootstrap's
+ *   records; the bootstrap's records, status and iteration counts and every derived record are bit for bit what they are without it.  n_terms = 0: off (the
+ *   default): no launch, no allocation.  PLSPM_E_ARG for a term outside the definitions (the message names it); PLSPM_E_LIMIT for more than 65,535 uploaded rows
+ *   (the row multiplicities are one LDS histogram of 16-bit counters; also raised at the start of a call, before anything of it runs), for more than 128 row
+ *   sums per replicate, and for a model whose workspaces exceed a workgroup's 160 KiB of LDS.  Permutation, stratified, cross-validation, jackknife and group
+ *   calls write none.
+ * plspm_moderation_width: W (0 before the first plspm_moderation_enable with terms).
+ * plspm_moderation_fit: the full-sample record, out [W]: the same kernels on one problem with every multiplicity 1; *status (may be NULL): the record's status.
+ * plspm_moderation_fetch / _summary / _intervals: as plspm_structural_fetch / _summary / _intervals, on the moderation records.
+ * PLSPM_E_STATE from the last three without moderation records on the handle (whatever voids the assessment records voids these; a jackknife leaves them alone).
+ */
+int plspm_moderation_enable(plspm_model_t* m, int32_t n_terms, const int32_t* predictor, const int32_t* moderator, const int32_t* target);
+int32_t plspm_moderation_width(const plspm_model_t* m);
+int plspm_moderation_fit(plspm_model_t* m, double* out, int32_t* status);
+int plspm_moderation_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
+int plspm_moderation_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
+int plspm_moderation_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
+
 /*
  * ---- MICOM: permutation test of measurement invariance --------------------------------------------------------------------------
  * Measurement invariance of composite models (Henseler, Ringle and Sarstedt 2016), steps 2 and 3, for every permutation of plspm_permutation_device: one more
@@ -888,8 +919,10 @@ int plspm_op_outer_weights_nonmetric(int32_t device_id, int32_t mode, const doub
                                      double correction, double* w, double* Y);
 
 /* Kernel timing with HIP events on the handle's own stream (for the roofline figures in bench.py).
- * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM, PLSc and model-fit kernels). */
-enum { PLSPM_K_RESAMPLE = 0, PLSPM_K_GRAM = 1, PLSPM_K_SOLVER = 2, PLSPM_K_SCORES = 3, PLSPM_K_PACK = 4, PLSPM_K_REDUCE = 5, PLSPM_K_ASSESS = 6, PLSPM_K_COUNT = 7 };
+ * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM, PLSc and model-fit kernels),
+ * 7 .. 10 the moderation kernels: counts, prepare, row pass, finish. */
+enum { PLSPM_K_RESAMPLE = 0, PLSPM_K_GRAM = 1, PLSPM_K_SOLVER = 2, PLSPM_K_SCORES = 3, PLSPM_K_PACK = 4, PLSPM_K_REDUCE = 5, PLSPM_K_ASSESS = 6, PLSPM_K_MOD_COUNTS = 7, PLSPM_K_MOD_PREPARE = 8, PLSPM_K_MOD_ROWS = 9,
+       PLSPM_K_MOD_FINISH = 10, PLSPM_K_COUNT = 11 };
 /* on: 0 off, 1 every kernel, 2 + id only kernel `id` (an event pair costs dispatch latency on both sides: bracketing one kernel of a
  * step perturbs the step less than bracketing all of them). */
 int plspm_profile_enable(plspm_model_t* m, int32_t on);

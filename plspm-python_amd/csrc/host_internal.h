@@ -177,6 +177,16 @@ int derived_launch(plspm_model* m, int runs, long nb, int64_t pos, bool dense, c
 // The owner of the record buffers, behind the last chunk: B records of every stage that ran are valid.
 void derived_commit(plspm_model* m, int runs, int64_t B);
 
+// ---- plspm_moderation.hip: the moderation records of a plain metric bootstrap's replicates, beside the derived chain's three calls and by the same rule.
+// Once per call: *runs = 1 when the handle's switch is on and the call's owner takes the records (derived_begin's rule), else 0; the record buffer is reserved for
+// call.B replicates by a call of its own.  A shape the plan refuses is refused here, before anything of the call runs (PLSPM_E_LIMIT).
+int moderation_begin(plspm_model* m, const BatchCall& call, int* runs);
+// Once per pass, behind derived_launch: `nb` problems whose records start at position `pos` of the record buffer and whose draws are those of replicates rep0 ..
+// of `seed` (the two differ under rep_offset), or the explicit rows at d_idx [nb][N]; gram / rows as derived_launch takes them.
+int moderation_launch(plspm_model* m, int runs, long nb, int64_t pos, int64_t rep0, uint64_t seed, const int32_t* d_idx, bool dense, const double* gram, const double* rows,
+                      long row_stride);
+void moderation_commit(plspm_model* m, int runs, int64_t B);
+
 // ---- plspm_bootstrap.hip: side records -- a buffer of records [count x (width + 2)] (values | status | iterations) beside the bootstrap records, valid while
 // `count` is non-zero: the records of every stage of plspm_derived.hip, the MICOM records of a permutation call.  One description, and the entry points all share.
 // plain_only: the entry points refuse any other handle kind behind their argument check (MICOM; the assessment answers "no records" there).  none / differs /

@@ -11,6 +11,7 @@
 #include "../../include/plspm_hip_test.h"
 #include "gram_route.h"
 #include "derived_route.h"
+#include "moderation_core.h"
 #include "group_route.h"
 #include "options.h"
 
@@ -189,6 +190,14 @@ struct plspm_model {
     bool structural_listed = false;          // ... the lists below describe this handle's path matrix
     std::vector<int> struct_dir_from, struct_dir_to, struct_chain_off, struct_chain_nodes;      // [n_dir] x 2, [n_spec + 1], [chain_off[n_spec]]
     Buf structural_desc;                     // ... dir_from | dir_to | chain_off | chain_eff on the device (structural_core.h StructDesc)
+    // moderation analysis (plspm_moderation.hip): the switch and the terms' lists (moderation_core.h) from plspm_moderation_enable; the replicates' records
+    // [mod_B x (width + 2)] in a buffer of their own, indexed by the replicate's position in the whole call; a pass's counts, tables, correlations and partial sums
+    bool mod_on = false;
+    plspm::ModLayout mod_lay{};
+    int mod_e_total = 0;
+    std::vector<int> mod_terms;              // ... predictor | moderator | target, [3 T]
+    Buf mod_desc, mod_rows, mod_cnt, mod_table, mod_rc, mod_partial, mod_fit;
+    int64_t mod_B = 0;                       // ... the last plain bootstrap whose moderation records are on the handle (0: none)
     // MICOM records of a permutation call's splits (kernels_micom.h; plspm_micom_*): records [micom_B x (3 L + 2)] in a buffer of their own, indexed by the
     // permutation's position in the call; the pooled inputs (u, the diagonal blocks of R_0; plspm_micom.hip micom_prepare) once per upload
     bool micom_on = false;                   // plspm_micom_enable
@@ -269,6 +278,7 @@ inline void void_records(plspm_model* m, unsigned which) {
     // records go when a stage it reads goes, and a row reads rows before it).  PLSc reads the assessment, so REC_ASSESS takes every derived record with it and
     // REC_PLSC those from PLSc on; every caller names the two together.
     static_assert(plspm::kDerivedStage[plspm::STAGE_PLSC].reads & plspm::stage_bit(plspm::STAGE_ASSESS), "REC_ASSESS voids the PLSc records and what follows them");
+    if (which & REC_ASSESS) m->mod_B = 0;      // (the moderation records go exactly when the derived records do)
     int gone = (which & REC_ASSESS ? plspm::stage_bit(plspm::STAGE_ASSESS) : 0) | (which & REC_PLSC ? plspm::stage_bit(plspm::STAGE_PLSC) : 0);
     for (int s = 0; s < plspm::kDerivedStages; ++s)
         if (gone & (plspm::stage_bit(s) | plspm::kDerivedStage[s].reads)) { gone |= plspm::stage_bit(s); m->derived[s].B = 0; }

@@ -18,7 +18,8 @@ ABI_VERSION = 4
 
 STATUS_OK, STATUS_NOT_CONVERGED, STATUS_SINGULAR, STATUS_NONFINITE = 0, 1, 2, 3
 STATUS_INADMISSIBLE = 4      # PLSc, model-fit and geodesic records only (plspm_plsc_*, plspm_modelfit_*, plspm_geodesic_*)
-KERNELS = {"resample": 0, "gram": 1, "solver": 2, "scores": 3, "pack": 4, "reduce": 5, "assess": 6}
+KERNELS = {"resample": 0, "gram": 1, "solver": 2, "scores": 3, "pack": 4, "reduce": 5, "assess": 6, "moderation_counts": 7, "moderation_prepare": 8, "moderation_rows": 9,
+           "moderation_finish": 10}
 EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm_model_create", "plspm_model_destroy", "plspm_model_set_nonmetric", "plspm_model_set_categorical", "plspm_model_set_missing", "plspm_model_attach_second_stage", "plspm_model_set_incomplete_rows",
            "plspm_upload", "plspm_effect_pairs", "plspm_row_width", "plspm_row_stride", "plspm_fit", "plspm_bootstrap", "plspm_bootstrap_device", "plspm_bootstrap_summary",
            "plspm_sync", "plspm_stream", "plspm_bootstrap_indices", "plspm_profile_enable", "plspm_profile_read", "plspm_profile_reset",
@@ -39,6 +40,7 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_geodesic_enable", "plspm_geodesic_width", "plspm_geodesic_fit", "plspm_geodesic_fetch", "plspm_geodesic_summary", "plspm_geodesic_intervals",
            "plspm_structural_enable", "plspm_structural_width", "plspm_structural_paths", "plspm_structural_fit", "plspm_structural_fetch", "plspm_structural_summary",
            "plspm_structural_intervals",
+           "plspm_moderation_enable", "plspm_moderation_width", "plspm_moderation_fit", "plspm_moderation_fetch", "plspm_moderation_summary", "plspm_moderation_intervals",
            "plspm_micom_enable", "plspm_micom_width", "plspm_micom_fetch", "plspm_micom_summary", "plspm_micom_intervals", "plspm_micom_counts"]
 CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
 CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
@@ -140,8 +142,8 @@ def load():
     # the six families of side records (assessment, PLSc, model fit, geodesic discrepancy, structural assessment, MICOM): one set of signatures; only MICOM has no
     # full-sample record
     lib.plspm_structural_paths.argtypes = [vp, ctypes.POINTER(i32), vp, vp, ctypes.POINTER(i32), vp, vp]
-    for family in ("assess", "plsc", "modelfit", "geodesic", "structural", "micom"):
-        getattr(lib, "plspm_%s_enable" % family).argtypes = [vp, i32, vp] if family in ("plsc", "modelfit", "geodesic") else [vp, i32]
+    for family in ("assess", "plsc", "modelfit", "geodesic", "structural", "micom", "moderation"):
+        getattr(lib, "plspm_%s_enable" % family).argtypes = [vp, i32, vp] if family in ("plsc", "modelfit", "geodesic") else [vp, i32, vp, vp, vp] if family == "moderation" else [vp, i32]
         getattr(lib, "plspm_%s_width" % family).restype = i32
         getattr(lib, "plspm_%s_width" % family).argtypes = [vp]
         if family != "micom":
@@ -669,6 +671,34 @@ class NativeModel:
     def assess_intervals(self, B, original, method="percentile", level=0.95):
         """``intervals`` on the assessment records (plspm_assess_intervals; no bca): ([A, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
         return self._side_table("assess", "intervals", B, original, method, level)
+
+    def moderation_enable(self, terms):
+        """Moderation analysis (plspm_moderation_enable): ``terms`` a list of (predictor, moderator, target) LV indices -- every later ``bootstrap`` /
+        ``bootstrap_device`` call also writes the record direct2 [n_dir] | interaction | f2 | slope_low | slope_high [T each] | r2 [L] of every replicate; no other
+        record changes.  An empty list (or None) switches it off."""
+        terms = np.ascontiguousarray(np.asarray(terms if terms is not None else [], dtype=np.int32).reshape(-1, 3).T)
+        self._side_call("moderation", "enable", terms.shape[1], _ptr(terms[0]) if terms.shape[1] else None, _ptr(terms[1]) if terms.shape[1] else None,
+                        _ptr(terms[2]) if terms.shape[1] else None)
+
+    @property
+    def moderation_width(self):
+        return self._side_width("moderation")
+
+    def moderation_fit(self):
+        """The full-sample moderation record (plspm_moderation_fit): ([W] values, the record's status)."""
+        return self._side_fit("moderation")
+
+    def moderation_fetch(self, first=0, count=None):
+        """Host copy of the moderation records [first, first + count) of the last moderated bootstrap: (records [count, W], status [count])."""
+        return self._side_fetch("moderation", first, self.last_B - first if count is None else count)
+
+    def moderation_summary(self, B, original):
+        """``summary`` on the moderation records (plspm_moderation_summary): ([W, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
+        return self._side_table("moderation", "summary", B, original)
+
+    def moderation_intervals(self, B, original, method="percentile", level=0.95):
+        """``intervals`` on the moderation records (plspm_moderation_intervals; no bca): ([W, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
+        return self._side_table("moderation", "intervals", B, original, method, level)
 
     def structural_enable(self, on=True):
         """Structural-model assessment (plspm_structural_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the record f2 [n_dir] |

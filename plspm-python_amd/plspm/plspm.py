@@ -7,7 +7,8 @@ over once the caller NAMES GPUs (``devices=[...]`` or the ``PLSPM_DEVICES`` allo
 Without named GPUs everything runs on ``device_id``.  Keyword extensions: ``seed`` (reproducible bootstrap), ``device_id``, ``devices``,
 ``quality`` (with ``bootstrap=True``: the measurement-model assessment of every replicate, ``quality()``), ``consistent`` / ``factors`` (with ``bootstrap=True``:
 consistent PLS of the full sample and of every replicate, ``plsc()``; ``factors``: the LVs that are common factors, None = every Mode-A block of two items or more),
-``structural`` (with ``bootstrap=True``: f2, inner VIF and the specific indirect effects of every replicate, ``structural()``), ``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
+``structural`` (with ``bootstrap=True``: f2, inner VIF and the specific indirect effects of every replicate, ``structural()``),
+``interactions`` (with ``bootstrap=True``: (predictor, moderator, target) names -- the two-stage moderation analysis of every replicate, ``moderation()``), ``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
 reference's own fp64 accumulation on the data at hand; "strict": always seven planes = correctly rounded sums, ~20 % slower).
 """
 import time
@@ -69,7 +70,7 @@ class Plspm:
     def __init__(self, data: pd.DataFrame, config: c.Config, scheme: Scheme = Scheme.CENTROID, iterations: int = 100,
                  tolerance: float = 0.000001, bootstrap: bool = False, bootstrap_iterations: int = 100, processes: int = 2,
                  seed: int = None, device_id: int = 0, devices=None, precision: str = "auto", quality: bool = False,
-                 consistent: bool = False, factors=None, structural: bool = False):
+                 consistent: bool = False, factors=None, structural: bool = False, interactions=None):
         iterations, bootstrap_iterations = _normalise_arguments(scheme, iterations, tolerance, bootstrap_iterations, processes)
         t_start = time.perf_counter()
         estimator = Estimator(config)
@@ -116,6 +117,18 @@ class Plspm:
                     raise NotImplementedError("the structural assessment covers metric data without missing cells and without higher-order constructs: this model has " + why)
                 pst._check_chain_count(boot_on.compiled.path)
                 boot_on.native.structural_enable(True)
+            moderation_terms = None
+            if interactions:
+                # the moderation kernels run behind the solver of every replicate batch on this handle (plspm.moderation)
+                from plspm import moderation as pmo
+                from plspm import quality as pq
+                why = pq._unsupported(config, observations)
+                if why is not None:
+                    raise NotImplementedError("the moderation analysis covers metric data without missing cells and without higher-order constructs: this model has " + why)
+                if n_obs > pmo.MAX_ROWS:
+                    raise NotImplementedError("the moderation analysis covers at most %d rows: this data set has %d" % (pmo.MAX_ROWS, n_obs))
+                moderation_terms = pmo._term_names(config, interactions)
+                boot_on.native.moderation_enable(moderation_terms)
             pending = launch_bootstrap(boot_on, bootstrap_iterations, processes, seed, devices=devices)
         self._result = fit
         # The report frames only re-label / post-process the device outputs already on the host (fit.raw); they are built on first
@@ -156,6 +169,11 @@ class Plspm:
             if self._bootstrap.ranks() != 1:
                 raise NotImplementedError("the structural assessment runs on one GPU: this bootstrap was sharded over %d" % self._bootstrap.ranks())
             self._structural = pst.Structural.of_bootstrap(fit.native, fit.compiled, bootstrap_iterations)
+        self._moderation = None
+        if bootstrap and interactions:
+            if self._bootstrap.ranks() != 1:
+                raise NotImplementedError("the moderation analysis runs on one GPU: this bootstrap was sharded over %d" % self._bootstrap.ranks())
+            self._moderation = pmo.Moderation.of_bootstrap(fit.native, fit.compiled, bootstrap_iterations, moderation_terms)
         # fit_s: filter + upload + device fit; bootstrap_s: what the bootstrap adds (the wait for the replicates + the device summaries);
         # bootstrap_latency_s: enqueue of the replicates -> summaries on the host
         self._timings = {"fit_s": t_fit - t_start, "bootstrap_s": time.perf_counter() - t_fit,
@@ -227,6 +245,12 @@ class Plspm:
         if self._plsc is None:
             raise Exception("To get consistent PLS estimates, set the parameters bootstrap and consistent to True when calling Plspm")
         return self._plsc
+
+    def moderation(self):
+        """The :class:`plspm.moderation.Moderation` analysis of the bootstrap; raises unless bootstrap=True and interactions=[...] were requested."""
+        if self._moderation is None:
+            raise Exception("To analyse moderation, set the parameter bootstrap to True and list the interactions when calling Plspm")
+        return self._moderation
 
     def structural(self):
         """The :class:`plspm.structural.Structural` assessment of the bootstrap; raises unless bootstrap=True and structural=True were requested."""
