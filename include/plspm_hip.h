@@ -755,6 +755,35 @@ int plspm_moderation_fetch(plspm_model_t* m, int64_t first, int64_t count, doubl
 int plspm_moderation_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
 int plspm_moderation_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
 
+/* Confirmatory tetrad analysis (CTA-PLS; this project's definitions, csrc/tetrad_core.h): is a block reflective at all?  Under a one-factor
+ * reflective model every tetrad tau(a, b, c, d) = x_ab x_cd - x_ac x_bd of four items of the block vanishes, x the items' correlations (matrix 0, the
+ * assessment's r_pq) or covariances c_pq = M_pq / n - mu_p mu_q (matrix 1) of the data set: two rounded products and one subtraction, no fma.  A block is
+ * testable with at least four items, numbered 1 .. k in device order.  Set 0 (basis), k (k - 3) / 2 per block: for i = 4 .. k tau(1,3,i,2), tau(1,2,i,3), then
+ * for 4 <= i < j <= k, i-major, tau(1,2,i,j) -- a non-redundant set of the model-implied vanishing tetrads.  Set 1 (all), 2 C(k, 4) per block: per quadruple
+ * a < b < c < d in lexicographic order tau(a,b,c,d), tau(a,c,d,b) (the third is minus their sum).
+ * Record, width n_tet: the tetrads by block and then as above; status and iterations behind it as doubles (pitch n_tet + 2).  A replicate whose bootstrap status
+ * is not PLSPM_OK keeps that status and has NaN in all values; otherwise PLSPM_NONFINITE where a tetrad is not finite (a column that is constant in the
+ * resample, under the correlations); the values stand.  Plain metric handles only: PLSPM_E_ARG otherwise.
+ *
+ * plspm_tetrad_enable: on != 0: mask [L] names the tested blocks (NULL: every testable block) -- every later plspm_bootstrap / plspm_bootstrap_device call on
+ *   this handle also writes the tetrad records of its replicates into a buffer of their own, indexed like the bootstrap's records; every other record is bit for
+ *   bit what it is without it.  on = 0: off (the default): no launch, no allocation.  PLSPM_E_ARG for a mask entry on a block of fewer than four items (the message
+ *   names the LV), for no testable block and for a set or matrix outside 0 / 1; PLSPM_E_LIMIT for more than 4,096 tetrads (the message has the count) and for lists
+ *   whose staged correlations exceed a workgroup's 160 KiB of LDS.  Permutation, stratified, cross-validation, jackknife and group calls write none.
+ * plspm_tetrad_width: n_tet (0 before the first plspm_tetrad_enable that switched it on).
+ * plspm_tetrad_list: *n_tet and per tetrad its block (LV index) and its items a, b, c, d as device-order MV indices; any pointer may be NULL.
+ * plspm_tetrad_fit: the full-sample record, out [n_tet]: the same kernel on the moments of all uploaded rows; *status (may be NULL): the record's status.
+ * plspm_tetrad_fetch / _summary / _intervals: as plspm_structural_fetch / _summary / _intervals, on the tetrad records (methods 0 .. 2, any level in (0, 1)).
+ * PLSPM_E_STATE from the last three without tetrad records on the handle (whatever voids the assessment records voids these; a jackknife leaves them alone).
+ */
+int plspm_tetrad_enable(plspm_model_t* m, int32_t on, const uint8_t* mask, int32_t set, int32_t matrix);
+int32_t plspm_tetrad_width(const plspm_model_t* m);
+int plspm_tetrad_list(plspm_model_t* m, int32_t* n_tet, int32_t* block, int32_t* a, int32_t* b, int32_t* c, int32_t* d);
+int plspm_tetrad_fit(plspm_model_t* m, double* out, int32_t* status);
+int plspm_tetrad_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
+int plspm_tetrad_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
+int plspm_tetrad_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
+
 /*
  * ---- MICOM: permutation test of measurement invariance --------------------------------------------------------------------------
  * Measurement invariance of composite models (Henseler, Ringle and Sarstedt 2016), steps 2 and 3, for every permutation of plspm_permutation_device: one more
@@ -919,7 +948,7 @@ int plspm_op_outer_weights_nonmetric(int32_t device_id, int32_t mode, const doub
                                      double correction, double* w, double* Y);
 
 /* Kernel timing with HIP events on the handle's own stream (for the roofline figures in bench.py).
- * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM, PLSc and model-fit kernels),
+ * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM, PLSc, model-fit and tetrad kernels),
  * 7 .. 10 the moderation kernels: counts, prepare, row pass, finish. */
 enum { PLSPM_K_RESAMPLE = 0, PLSPM_K_GRAM = 1, PLSPM_K_SOLVER = 2, PLSPM_K_SCORES = 3, PLSPM_K_PACK = 4, PLSPM_K_REDUCE = 5, PLSPM_K_ASSESS = 6, PLSPM_K_MOD_COUNTS = 7, PLSPM_K_MOD_PREPARE = 8, PLSPM_K_MOD_ROWS = 9,
        PLSPM_K_MOD_FINISH = 10, PLSPM_K_COUNT = 11 };

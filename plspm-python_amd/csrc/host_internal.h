@@ -187,6 +187,14 @@ int moderation_launch(plspm_model* m, int runs, long nb, int64_t pos, int64_t re
                       long row_stride);
 void moderation_commit(plspm_model* m, int runs, int64_t B);
 
+// ---- plspm_tetrad.hip: the tetrad records of a plain metric bootstrap's replicates, beside the moderation's three calls and by the same rule.
+// Once per call: *runs = 1 when the handle's switch is on and the call's owner takes the records (derived_begin's rule), else 0; the record buffer is reserved for
+// call.B replicates by a call of its own.  Lists whose one wave the LDS does not hold are refused here, before anything of the call runs (PLSPM_E_LIMIT).
+int tetrad_begin(plspm_model* m, const BatchCall& call, int* runs);
+// Once per pass, behind moderation_launch: `nb` problems whose records start at position `pos` of the record buffer; gram / rows as derived_launch takes them.
+int tetrad_launch(plspm_model* m, int runs, long nb, int64_t pos, bool dense, const double* gram, const double* rows, long row_stride);
+void tetrad_commit(plspm_model* m, int runs, int64_t B);
+
 // ---- plspm_bootstrap.hip: side records -- a buffer of records [count x (width + 2)] (values | status | iterations) beside the bootstrap records, valid while
 // `count` is non-zero: the records of every stage of plspm_derived.hip, the MICOM records of a permutation call.  One description, and the entry points all share.
 // plain_only: the entry points refuse any other handle kind behind their argument check (MICOM; the assessment answers "no records" there).  none / differs /

@@ -198,6 +198,15 @@ struct plspm_model {
     std::vector<int> mod_terms;              // ... predictor | moderator | target, [3 T]
     Buf mod_desc, mod_rows, mod_cnt, mod_table, mod_rc, mod_partial, mod_fit;
     int64_t mod_B = 0;                       // ... the last plain bootstrap whose moderation records are on the handle (0: none)
+    // confirmatory tetrad analysis (plspm_tetrad.hip): the switch, the set, the matrix, the tested blocks and the tetrads' lists (tetrad_core.h) from
+    // plspm_tetrad_enable; the replicates' records [tet_B x (tet_n + 2)] in a buffer of their own, indexed by the replicate's position in the whole call
+    bool tet_on = false;
+    int tet_set = 0, tet_matrix = 0;
+    std::vector<uint8_t> tet_mask;           // ... [L]: the blocks whose triangles are staged
+    std::vector<int> tet_block, tet_items;   // ... per tetrad its block [tet_n] and its items a, b, c, d as device-order MV indices [4 tet_n]
+    int tet_n = 0; long tet_tri = 0;         // ... tetrads; doubles of the staged triangles
+    Buf tet_desc, tet_rows, tet_fit;         // ... descriptors | triangle offsets on the device; the records; the full-sample problem and its record
+    int64_t tet_B = 0;                       // ... the last plain bootstrap whose tetrad records are on the handle (0: none)
     // MICOM records of a permutation call's splits (kernels_micom.h; plspm_micom_*): records [micom_B x (3 L + 2)] in a buffer of their own, indexed by the
     // permutation's position in the call; the pooled inputs (u, the diagonal blocks of R_0; plspm_micom.hip micom_prepare) once per upload
     bool micom_on = false;                   // plspm_micom_enable
@@ -278,7 +287,7 @@ inline void void_records(plspm_model* m, unsigned which) {
     // records go when a stage it reads goes, and a row reads rows before it).  PLSc reads the assessment, so REC_ASSESS takes every derived record with it and
     // REC_PLSC those from PLSc on; every caller names the two together.
     static_assert(plspm::kDerivedStage[plspm::STAGE_PLSC].reads & plspm::stage_bit(plspm::STAGE_ASSESS), "REC_ASSESS voids the PLSc records and what follows them");
-    if (which & REC_ASSESS) m->mod_B = 0;      // (the moderation records go exactly when the derived records do)
+    if (which & REC_ASSESS) m->mod_B = m->tet_B = 0;      // (the moderation and the tetrad records go exactly when the derived records do)
     int gone = (which & REC_ASSESS ? plspm::stage_bit(plspm::STAGE_ASSESS) : 0) | (which & REC_PLSC ? plspm::stage_bit(plspm::STAGE_PLSC) : 0);
     for (int s = 0; s < plspm::kDerivedStages; ++s)
         if (gone & (plspm::stage_bit(s) | plspm::kDerivedStage[s].reads)) { gone |= plspm::stage_bit(s); m->derived[s].B = 0; }

@@ -41,6 +41,7 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_structural_enable", "plspm_structural_width", "plspm_structural_paths", "plspm_structural_fit", "plspm_structural_fetch", "plspm_structural_summary",
            "plspm_structural_intervals",
            "plspm_moderation_enable", "plspm_moderation_width", "plspm_moderation_fit", "plspm_moderation_fetch", "plspm_moderation_summary", "plspm_moderation_intervals",
+           "plspm_tetrad_enable", "plspm_tetrad_width", "plspm_tetrad_list", "plspm_tetrad_fit", "plspm_tetrad_fetch", "plspm_tetrad_summary", "plspm_tetrad_intervals",
            "plspm_micom_enable", "plspm_micom_width", "plspm_micom_fetch", "plspm_micom_summary", "plspm_micom_intervals", "plspm_micom_counts"]
 CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
 CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
@@ -142,8 +143,10 @@ def load():
     # the six families of side records (assessment, PLSc, model fit, geodesic discrepancy, structural assessment, MICOM): one set of signatures; only MICOM has no
     # full-sample record
     lib.plspm_structural_paths.argtypes = [vp, ctypes.POINTER(i32), vp, vp, ctypes.POINTER(i32), vp, vp]
-    for family in ("assess", "plsc", "modelfit", "geodesic", "structural", "micom", "moderation"):
-        getattr(lib, "plspm_%s_enable" % family).argtypes = [vp, i32, vp] if family in ("plsc", "modelfit", "geodesic") else [vp, i32, vp, vp, vp] if family == "moderation" else [vp, i32]
+    lib.plspm_tetrad_list.argtypes = [vp, ctypes.POINTER(i32), vp, vp, vp, vp, vp]
+    for family in ("assess", "plsc", "modelfit", "geodesic", "structural", "micom", "moderation", "tetrad"):
+        getattr(lib, "plspm_%s_enable" % family).argtypes = ([vp, i32, vp] if family in ("plsc", "modelfit", "geodesic") else [vp, i32, vp, vp, vp] if family == "moderation"
+                                                             else [vp, i32, vp, i32, i32] if family == "tetrad" else [vp, i32])
         getattr(lib, "plspm_%s_width" % family).restype = i32
         getattr(lib, "plspm_%s_width" % family).argtypes = [vp]
         if family != "micom":
@@ -699,6 +702,46 @@ class NativeModel:
     def moderation_intervals(self, B, original, method="percentile", level=0.95):
         """``intervals`` on the moderation records (plspm_moderation_intervals; no bca): ([W, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
         return self._side_table("moderation", "intervals", B, original, method, level)
+
+    def tetrad_enable(self, on=True, mask=None, tetrads="basis", matrix="correlation"):
+        """Confirmatory tetrad analysis (plspm_tetrad_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the tetrads of the tested blocks of
+        every replicate; no other record changes.  mask: uint8 [L], the tested blocks (None: every block of at least four items); tetrads "basis" / "all" (or 0 / 1);
+        matrix "correlation" / "covariance" (or 0 / 1)."""
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != (self.L,):
+                raise ValueError("mask must have one entry per latent variable")
+        set_id = ("basis", "all").index(tetrads) if isinstance(tetrads, str) else int(tetrads)
+        matrix_id = ("correlation", "covariance").index(matrix) if isinstance(matrix, str) else int(matrix)
+        self._side_call("tetrad", "enable", int(bool(on)), _ptr(mask) if mask is not None else None, set_id, matrix_id)
+
+    @property
+    def tetrad_width(self):
+        return self._side_width("tetrad")
+
+    def tetrad_list(self):
+        """The tetrads in record order (plspm_tetrad_list): (block [n_tet] LV indices, a, b, c, d [n_tet] device-order MV indices)."""
+        n = ctypes.c_int32(0)
+        self._side_call("tetrad", "list", ctypes.byref(n), None, None, None, None, None)
+        out = [np.empty(n.value, dtype=np.int32) for _ in range(5)]
+        self._side_call("tetrad", "list", None, *[_ptr(v) for v in out])
+        return tuple(out)
+
+    def tetrad_fit(self):
+        """The full-sample tetrad record (plspm_tetrad_fit): ([n_tet] values, the record's status)."""
+        return self._side_fit("tetrad")
+
+    def tetrad_fetch(self, first=0, count=None):
+        """Host copy of the tetrad records [first, first + count) of the last bootstrap with tetrads: (records [count, n_tet], status [count])."""
+        return self._side_fetch("tetrad", first, self.last_B - first if count is None else count)
+
+    def tetrad_summary(self, B, original):
+        """``summary`` on the tetrad records (plspm_tetrad_summary): ([n_tet, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
+        return self._side_table("tetrad", "summary", B, original)
+
+    def tetrad_intervals(self, B, original, method="bc", level=0.95):
+        """``intervals`` on the tetrad records (plspm_tetrad_intervals; no bca): ([n_tet, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
+        return self._side_table("tetrad", "intervals", B, original, method, level)
 
     def structural_enable(self, on=True):
         """Structural-model assessment (plspm_structural_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the record f2 [n_dir] |

@@ -8,7 +8,9 @@ Without named GPUs everything runs on ``device_id``.  Keyword extensions: ``seed
 ``quality`` (with ``bootstrap=True``: the measurement-model assessment of every replicate, ``quality()``), ``consistent`` / ``factors`` (with ``bootstrap=True``:
 consistent PLS of the full sample and of every replicate, ``plsc()``; ``factors``: the LVs that are common factors, None = every Mode-A block of two items or more),
 ``structural`` (with ``bootstrap=True``: f2, inner VIF and the specific indirect effects of every replicate, ``structural()``),
-``interactions`` (with ``bootstrap=True``: (predictor, moderator, target) names -- the two-stage moderation analysis of every replicate, ``moderation()``), ``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
+``interactions`` (with ``bootstrap=True``: (predictor, moderator, target) names -- the two-stage moderation analysis of every replicate, ``moderation()``),
+``tetrads`` (with ``bootstrap=True``: the confirmatory tetrad analysis of every block of four items or more, ``tetrads()``;
+``plspm.tetrad.TetradAnalysis`` takes the blocks, the set, the matrix and alpha), ``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
 reference's own fp64 accumulation on the data at hand; "strict": always seven planes = correctly rounded sums, ~20 % slower).
 """
 import time
@@ -70,7 +72,7 @@ class Plspm:
     def __init__(self, data: pd.DataFrame, config: c.Config, scheme: Scheme = Scheme.CENTROID, iterations: int = 100,
                  tolerance: float = 0.000001, bootstrap: bool = False, bootstrap_iterations: int = 100, processes: int = 2,
                  seed: int = None, device_id: int = 0, devices=None, precision: str = "auto", quality: bool = False,
-                 consistent: bool = False, factors=None, structural: bool = False, interactions=None):
+                 consistent: bool = False, factors=None, structural: bool = False, interactions=None, tetrads=False):
         iterations, bootstrap_iterations = _normalise_arguments(scheme, iterations, tolerance, bootstrap_iterations, processes)
         t_start = time.perf_counter()
         estimator = Estimator(config)
@@ -129,6 +131,14 @@ class Plspm:
                     raise NotImplementedError("the moderation analysis covers at most %d rows: this data set has %d" % (pmo.MAX_ROWS, n_obs))
                 moderation_terms = pmo._term_names(config, interactions)
                 boot_on.native.moderation_enable(moderation_terms)
+            if tetrads:
+                # the tetrad kernel runs behind the solver of every replicate batch on this handle (plspm.tetrad), with TetradAnalysis's defaults
+                from plspm import quality as pq
+                from plspm import tetrad as ptet
+                why = pq._unsupported(config, observations)
+                if why is not None:
+                    raise NotImplementedError("the tetrad analysis covers metric data without missing cells and without higher-order constructs: this model has " + why)
+                boot_on.native.tetrad_enable(True, ptet._options(boot_on.compiled, None, "basis", "correlation", 0.05))
             pending = launch_bootstrap(boot_on, bootstrap_iterations, processes, seed, devices=devices)
         self._result = fit
         # The report frames only re-label / post-process the device outputs already on the host (fit.raw); they are built on first
@@ -174,6 +184,11 @@ class Plspm:
             if self._bootstrap.ranks() != 1:
                 raise NotImplementedError("the moderation analysis runs on one GPU: this bootstrap was sharded over %d" % self._bootstrap.ranks())
             self._moderation = pmo.Moderation.of_bootstrap(fit.native, fit.compiled, bootstrap_iterations, moderation_terms)
+        self._tetrads = None
+        if bootstrap and tetrads:
+            if self._bootstrap.ranks() != 1:
+                raise NotImplementedError("the tetrad analysis runs on one GPU: this bootstrap was sharded over %d" % self._bootstrap.ranks())
+            self._tetrads = ptet.TetradAnalysis.of_bootstrap(fit.native, fit.compiled, bootstrap_iterations)
         # fit_s: filter + upload + device fit; bootstrap_s: what the bootstrap adds (the wait for the replicates + the device summaries);
         # bootstrap_latency_s: enqueue of the replicates -> summaries on the host
         self._timings = {"fit_s": t_fit - t_start, "bootstrap_s": time.perf_counter() - t_fit,
@@ -251,6 +266,12 @@ class Plspm:
         if self._moderation is None:
             raise Exception("To analyse moderation, set the parameter bootstrap to True and list the interactions when calling Plspm")
         return self._moderation
+
+    def tetrads(self):
+        """The :class:`plspm.tetrad.TetradAnalysis` of the bootstrap; raises unless bootstrap=True and tetrads=True were requested."""
+        if self._tetrads is None:
+            raise Exception("To run the confirmatory tetrad analysis, set the parameters bootstrap and tetrads to True when calling Plspm")
+        return self._tetrads
 
     def structural(self):
         """The :class:`plspm.structural.Structural` assessment of the bootstrap; raises unless bootstrap=True and structural=True were requested."""
