@@ -205,6 +205,21 @@ int side_fetch(plspm_model* m, const SideRecords& s, int64_t first, int64_t coun
 int side_summary(plspm_model* m, const SideRecords& s, int64_t B, const double* original, double* summary, int64_t* n_used, const char* who);
 int side_intervals(plspm_model* m, const SideRecords& s, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used, const char* who);
 
+// ---- plspm_bootstrap.hip: the calls that bring their own count rows to the int8 Gram (permutation, stratified bootstrap, cross-validation, jackknife).  What their
+// entry points refuse alike, in two steps around the entry point's own argument checks (which read the uploaded N and come before the device is touched):
+int counts_call_scope(plspm_model* m, const char* who, int64_t min_rows = 2);       // data uploaded (PLSPM_E_STATE), a plain metric handle (PLSPM_E_ARG)
+int counts_route_scope(plspm_model* m, const char* who);       // the 16x16x64 layout (PLSPM_E_ARG), hipSetDevice, the int8 route open at seven planes (PLSPM_E_LIMIT)
+// the (key, row) pairs of the N rows of repetition `rep` of a key stream (philox.h permute_quad / cv_quad), in row order: what the host mirrors of rank_select.h order
+template <class Quad>
+inline std::vector<std::pair<uint32_t, uint32_t>> row_keys(Quad quad, uint64_t seed, int64_t rep, int64_t N) {
+    std::vector<std::pair<uint32_t, uint32_t>> key((size_t)N);
+    for (int64_t q = 0; q < (N + 3) / 4; ++q) {
+        const auto u = quad(seed, (uint64_t)rep, (uint32_t)q);
+        for (int j = 0; j < 4; ++j) if (4 * q + j < N) key[(size_t)(4 * q + j)] = {u.v[j], (uint32_t)(4 * q + j)};
+    }
+    return key;
+}
+
 // ---- plspm_permute.hip (two-group permutation test)
 // One call's splits: permutation rep_offset + p has problem 2p = group a (n1 rows), 2p + 1 = the other N - n1 rows; `d_member` [B][N] bytes 0/1
 // (explicit memberships, tests) or null (on-device splits from the Philox keys, kernels_permute.h).

@@ -5,48 +5,33 @@
 // Folds of repetition r (include/plspm_hip.h plspm_cv_device): row i carries the key cv_quad(seed, r, i >> 2).v[i & 3] (philox.h); the rows
 // ordered by (key, row), the one at position j belongs to fold (j * k) / N.  Folds 0 .. f - 1 together hold the c_f = ceil(f N / k) smallest
 // pairs, so k - 1 nested thresholds over the one key stream say it all:
-//   cv_threshold_kernel    one workgroup per (repetition, f = 1 .. k - 1): radix select (11 + 11 + 10 bits) of the c_f-th smallest key and the row
-//                          cut among its ties (the selection of kernels_permute.h perm_threshold_kernel on this stream);
+//   cv_threshold_kernel    one workgroup per (repetition, f = 1 .. k - 1): radix select (11 + 11 + 10 bits) of the c_f-th smallest key and the row cut among
+//                          its ties -- perm_threshold_kernel's select (kernels_permute.h) on this stream, kept in step with it; constants and scan: rank_select.h;
 //   cv_assign_kernel       fold(i) = #{f : (key_i, i) is not among the c_f smallest} -- a binary search over the nested thresholds;
 //   cv_order_kernel        per (repetition, fold): its rows in ascending order into the repetition's index, and the fold's offset;
-//   cv_counts_kernel       problem q = r k + f: count 1 on the rows with fold != f, as int8 in resample_i8_kernel's layout.
+//   cv_counts_kernel       problem q = r k + f: count 1 on the rows with fold != f, as 0/1 count rows (count_rows.h).
 // Behind the solver:
 //   cv_fold_moments_kernel     per problem the cross-products [x', 1][x', 1]' over its HELD-OUT rows (x' = the resident mean-shifted row);
 //   cv_train_moments_kernel    training = (sum of the repetition's folds) - fold, in place;
 //   cv_compose_kernel          the affine map of a problem's fit: x_hat = C [1; x_raw] for the target indicators;
 //   cv_apply_kernel            e = x - C [1; x] on the held-out rows and its sums per (problem, target).
 #pragma once
-#include "philox.h"
-#include "wave_ops.h"
+#include "rank_select.h"
+#include "count_rows.h"
 
-#define CV_NT 256                 // threads per workgroup of every kernel here but cv_compose_kernel (one wave)
-#define CV_BINS 2048              // radix digits of 11 bits
-#define CV_CACHE_ROWS 12288       // up to this many rows the keys stay in LDS (48 KB) after the first radix pass
+#define CV_NT 256                 // threads per workgroup of the kernels here that are not rank_select.h's or count_rows.h's (cv_compose_kernel: one wave)
+// (cv_threshold_kernel and cv_order_kernel call rank_select.h's block_scan, which is written for RANK_NT threads: they take RANK_NT, whatever CV_NT becomes)
 
 // rows of folds 0 .. f - 1 of a repetition of N rows in k folds
 __host__ __device__ __forceinline__ int cv_fold_start(int f, int N, int k) { return (int)(((long long)f * N + k - 1) / k); }
 
-// exclusive prefix sum over the 256 threads of a workgroup; *total = the sum of all.  Ends behind a barrier (lds4 is free again).
-__device__ __forceinline__ unsigned cv_block_scan(unsigned v, unsigned* lds4, unsigned* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned inc = wv::inclusive_scan(v);
-    if (lane == 63) lds4[w] = inc;
-    __syncthreads();
-    unsigned base = 0u, tot = 0u;
-#pragma unroll
-    for (int j = 0; j < CV_NT / 64; ++j) { const unsigned t = lds4[j]; base += (j < w) ? t : 0u; tot += t; }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 // thr[r * (k - 1) + f - 1] = (thr_key, row_cut) of boundary f = blockIdx.y + 1 of repetition rep0 + r (r = blockIdx.x): row i is in a fold below f iff
-// key < thr_key || (key == thr_key && i < row_cut).  Dynamic LDS: N keys when `cache` (N <= CV_CACHE_ROWS), else none.
-__global__ void __launch_bounds__(CV_NT) cv_threshold_kernel(int N, int k, uint64_t seed, int64_t rep0, int cache, uint2* __restrict__ thr) {
+// key < thr_key || (key == thr_key && i < row_cut).  Dynamic LDS: N keys when `cache` (N <= RANK_CACHE_ROWS), else none.
+__global__ void __launch_bounds__(RANK_NT) cv_threshold_kernel(int N, int k, uint64_t seed, int64_t rep0, int cache, uint2* __restrict__ thr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     unsigned* keys = reinterpret_cast<unsigned*>(smem_raw);
-    __shared__ unsigned hist[CV_BINS];
-    __shared__ unsigned scan4[CV_NT / 64];
+    __shared__ unsigned hist[RANK_BINS];
+    __shared__ unsigned scan4[RANK_NT / 64];
     __shared__ unsigned sh_bin, sh_k, sh_cut;
     const int tid = threadIdx.x;
     const uint64_t r = (uint64_t)(rep0 + (int64_t)blockIdx.x);
@@ -56,10 +41,10 @@ __global__ void __launch_bounds__(CV_NT) cv_threshold_kernel(int N, int k, uint6
     for (int pass = 0; pass < 3; ++pass) {
         const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
         const unsigned dmask = pass == 2 ? 0x3ffu : 0x7ffu;
-        for (int i = tid; i < CV_BINS; i += CV_NT) hist[i] = 0u;
+        for (int i = tid; i < RANK_BINS; i += RANK_NT) hist[i] = 0u;
         __syncthreads();
         if (pass == 0 || !cache) {
-            for (int q = tid; q < nq; q += CV_NT) {
+            for (int q = tid; q < nq; q += RANK_NT) {
                 const u32x4 u = cv_quad(seed, r, (uint32_t)q);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -72,7 +57,7 @@ __global__ void __launch_bounds__(CV_NT) cv_threshold_kernel(int N, int k, uint6
                 }
             }
         } else {
-            for (int i = tid; i < N; i += CV_NT) {
+            for (int i = tid; i < N; i += RANK_NT) {
                 const unsigned key = keys[i];
                 if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & dmask], 1u);
             }
@@ -83,7 +68,7 @@ __global__ void __launch_bounds__(CV_NT) cv_threshold_kernel(int N, int k, uint6
 #pragma unroll
         for (int b = 0; b < 8; ++b) own += hist[8 * tid + b];
         unsigned tot;
-        const unsigned before = cv_block_scan(own, scan4, &tot);
+        const unsigned before = block_scan(own, scan4, &tot);
         if (before < kk && kk <= before + own) {
             unsigned c = before;
             int b = 0;
@@ -98,7 +83,7 @@ __global__ void __launch_bounds__(CV_NT) cv_threshold_kernel(int N, int k, uint6
     if (kk < eq) {
         // ties straddle the boundary (uniform over the workgroup): the kk-th row of key == thr_key in row order is the last one below it
         unsigned need = kk;
-        for (int q0 = 0; q0 < nq; q0 += CV_NT) {
+        for (int q0 = 0; q0 < nq; q0 += RANK_NT) {
             const int q = q0 + tid;
             unsigned hit = 0u, c = 0u;                       // hit: bit j = row 4q + j has the threshold key
             if (q < nq) {
@@ -112,7 +97,7 @@ __global__ void __launch_bounds__(CV_NT) cv_threshold_kernel(int N, int k, uint6
                     if (4 * q + j < N && u.v[j] == prefix) { hit |= 1u << j; ++c; }
             }
             unsigned tot;
-            const unsigned before = cv_block_scan(c, scan4, &tot);
+            const unsigned before = block_scan(c, scan4, &tot);
             if (before < need && need <= before + c) {
                 unsigned seen = before;
                 for (int j = 0; j < 4; ++j)
@@ -145,58 +130,48 @@ __global__ void __launch_bounds__(CV_NT) cv_assign_kernel(int N, int k, uint64_t
         int lo = 0, hi = k - 1;                               // the memberships are nested: below boundary t => below boundary t + 1
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            const uint2 th = sthr[mid];
-            if (key < th.x || (key == th.x && i < th.y)) hi = mid; else lo = mid + 1;
+            if (below(sthr[mid], key, i)) hi = mid; else lo = mid + 1;
         }
         fold[(long)r * N + i] = (uint8_t)lo;
     }
 }
 
 // Workgroup (r = blockIdx.x, f = blockIdx.y): off[r][f] = #{i : fold < f} (and off[r][k] = N), idx[r][off ..] = the rows of fold f, ascending.
-__global__ void __launch_bounds__(CV_NT) cv_order_kernel(int N, int k, const uint8_t* __restrict__ fold, int* __restrict__ idx, int* __restrict__ off) {
-    __shared__ unsigned scan4[CV_NT / 64];
+__global__ void __launch_bounds__(RANK_NT) cv_order_kernel(int N, int k, const uint8_t* __restrict__ fold, int* __restrict__ idx, int* __restrict__ off) {
+    __shared__ unsigned scan4[RANK_NT / 64];
     const int r = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
     const uint8_t* fr = fold + (long)r * N;
     unsigned lower = 0u;
-    for (int i = tid; i < N; i += CV_NT) lower += fr[i] < f ? 1u : 0u;
+    for (int i = tid; i < N; i += RANK_NT) lower += fr[i] < f ? 1u : 0u;
     unsigned base;
-    (void)cv_block_scan(lower, scan4, &base);
+    (void)block_scan(lower, scan4, &base);
     if (tid == 0) { off[(long)r * (k + 1) + f] = (int)base; if (f == k - 1) off[(long)r * (k + 1) + k] = N; }
     int* out = idx + (long)r * N;
-    for (int i0 = 0; i0 < N; i0 += CV_NT) {
+    for (int i0 = 0; i0 < N; i0 += RANK_NT) {
         const int i = i0 + tid;
         const unsigned mine = (i < N && fr[i] == f) ? 1u : 0u;
         unsigned tot;
-        const unsigned before = cv_block_scan(mine, scan4, &tot);
+        const unsigned before = block_scan(mine, scan4, &tot);
         if (mine) out[base + before] = i;
         base += tot;
     }
 }
 
-// four 0/1 bits -> four bytes
-__device__ __forceinline__ unsigned cv_spread4(unsigned n) { return (n & 1u) | ((n & 2u) << 7) | ((n & 4u) << 14) | ((n & 8u) << 21); }
-
-// Counts of the chunk's problems prob0 + p, p < nprob: 1 on the rows outside the problem's fold.  Thread (p = 8 x + tid % 8, piece c = 32 y + tid / 8): rows
-// 16c .. 16c + 15 -- the layout of kernels_permute.h perm_counts_kernel (block (k-block, count tile) of 1 KB, piece g * 16 + problem % 16).  Pieces of rows >= N are zero.
-__global__ void __launch_bounds__(CV_NT) cv_counts_kernel(int N, int KB, int MT, int k, int64_t prob0, int nprob, const uint8_t* __restrict__ fold, uint4* __restrict__ Cd) {
-    const int tid = threadIdx.x;
-    const int p = (int)blockIdx.x * 8 + (tid & 7);
-    const int c = (int)blockIdx.y * (CV_NT / 8) + (tid >> 3);
-    if (p >= nprob || c >= KB * 4) return;
+// Counts of the chunk's problems prob0 + p, p < nprob: 1 on the rows outside the problem's fold.
+__global__ void __launch_bounds__(COUNT_NT) cv_counts_kernel(int N, int KB, int MT, int k, int64_t prob0, int nprob, const uint8_t* __restrict__ fold, uint4* __restrict__ Cd) {
+    int p, c;
+    if (!count_row_thread(nprob, KB, p, c)) return;
     const int64_t q = prob0 + p;
     const int64_t r = q / k;
     const unsigned f = (unsigned)(q - r * k);
-    const int i0 = 16 * c;
-    unsigned bits = 0u;                                       // bit t: row i0 + t is a training row
-    if (i0 < N) {
-        const uint8_t* fp = fold + r * (int64_t)N + i0;
-        const int nv = N - i0 >= 16 ? 16 : N - i0;
+    const int nv = count_row_rows(N, c);
+    unsigned bits = 0u;                                       // bit t: row 16c + t is a training row
+    if (nv) {
+        const uint8_t* fp = fold + r * (int64_t)N + 16 * c;
         for (int t = 0; t < nv; ++t)
             if (fp[t] != f) bits |= 1u << t;
     }
-    uint4 a;
-    a.x = cv_spread4(bits & 15u); a.y = cv_spread4((bits >> 4) & 15u); a.z = cv_spread4((bits >> 8) & 15u); a.w = cv_spread4(bits >> 12);
-    Cd[((long)(c >> 2) * MT + (p >> 4)) * 64 + (c & 3) * 16 + (p & 15)] = a;
+    count_row_store(Cd, MT, c, p, bits);
 }
 
 // packed upper triangle of a symmetric C1 x C1 matrix, row-major: (p, q), p <= q

@@ -1,35 +1,26 @@
 // kernels_jack.h -- Device kernels, part 8: the jackknife (delete-one / delete-a-group).  Included by plspm_jackknife.hip only (wave_ops.h in front).
-//   jack_counts_kernel   problem g: count 1 on the rows i with i % G != g, as int8 in resample_i8_kernel's layout.
+//   jack_counts_kernel   problem g: count 1 on the rows i with i % G != g, as 0/1 count rows (count_rows.h).
 //   jack_stats_kernel    per record column: mean, d_g = mean - theta_(g), se and acceleration over the OK problems, every sum in one fixed order.
 #pragma once
+#include "count_rows.h"
 
-constexpr int JACK_NT = 256;       // threads of a workgroup
+constexpr int JACK_NT = 256;       // threads of a jack_stats_kernel workgroup
 
-// four 0/1 bits -> four bytes
-__device__ __forceinline__ unsigned jack_spread4(unsigned n) { return (n & 1u) | ((n & 2u) << 7) | ((n & 4u) << 14) | ((n & 8u) << 21); }
-
-// Counts of the chunk's problems prob0 + p, p < nprob: 1 on the rows the problem keeps.  Thread (p = 8 x + tid % 8, piece c = 32 y + tid / 8): rows
-// 16c .. 16c + 15 -- the layout of kernels_permute.h perm_counts_kernel (block (k-block, count tile) of 1 KB, piece g * 16 + problem % 16), every
-// 65,536-row window alike.  Pieces of rows >= N are zero.
-__global__ void __launch_bounds__(JACK_NT) jack_counts_kernel(int N, int KB, int MT, int G, int64_t prob0, int nprob, uint4* __restrict__ Cd) {
-    const int tid = threadIdx.x;
-    const int p = (int)blockIdx.x * 8 + (tid & 7);
-    const int c = (int)blockIdx.y * (JACK_NT / 8) + (tid >> 3);
-    if (p >= nprob || c >= KB * 4) return;
+// Counts of the chunk's problems prob0 + p, p < nprob: 1 on the rows the problem keeps.
+__global__ void __launch_bounds__(COUNT_NT) jack_counts_kernel(int N, int KB, int MT, int G, int64_t prob0, int nprob, uint4* __restrict__ Cd) {
+    int p, c;
+    if (!count_row_thread(nprob, KB, p, c)) return;
     const int g = (int)(prob0 + p);
-    const int i0 = 16 * c;
-    unsigned bits = 0u;                                       // bit t: row i0 + t stays in
-    if (i0 < N) {
-        const int nv = N - i0 >= 16 ? 16 : N - i0;
-        int r = i0 % G;                                       // (i0 + t) % G, stepped
+    const int nv = count_row_rows(N, c);
+    unsigned bits = 0u;                                       // bit t: row 16c + t stays in
+    if (nv) {
+        int r = (16 * c) % G;                                 // (16c + t) % G, stepped
         for (int t = 0; t < nv; ++t) {
             if (r != g) bits |= 1u << t;
             if (++r == G) r = 0;
         }
     }
-    uint4 a;
-    a.x = jack_spread4(bits & 15u); a.y = jack_spread4((bits >> 4) & 15u); a.z = jack_spread4((bits >> 8) & 15u); a.w = jack_spread4(bits >> 12);
-    Cd[((long)(c >> 2) * MT + (p >> 4)) * 64 + (c & 3) * 16 + (p & 15)] = a;
+    count_row_store(Cd, MT, c, p, bits);
 }
 
 // block-wide sum in one fixed order: 64-lane butterfly (wave_ops.h), then the four wave results in wave order

@@ -4,39 +4,22 @@
 //
 // Split of permutation r (include/plspm_hip.h plspm_permutation_device): row i carries the key permute_quad(seed, r, i >> 2).v[i & 3]
 // (philox.h); group a = the n1 rows with the smallest (key, row) pairs.  Two passes:
-//   perm_threshold_kernel  one workgroup per permutation: radix select (11 + 11 + 10 bits) of the n1-th smallest key -> thr_key, and
-//                          the row cut among the rows whose key equals it (a scan in row order, only when such ties straddle the cut);
-//   perm_counts_kernel     member(i) = key < thr_key || (key == thr_key && i < row_cut), local to every 16-row piece: problem 2p gets
-//                          the members, problem 2p + 1 the complement, as int8 counts in exactly resample_i8_kernel's layout
-//                          (kernels_gram_i8.h: block (k-block, count tile) of 1 KB, piece g * 16 + replicate % 16).
+//   perm_threshold_kernel  one workgroup per permutation: radix select (11 + 11 + 10 bits) of the n1-th smallest key -> thr_key, and the row cut among
+//                          the rows whose key equals it (a scan in row order, only when such ties straddle the cut); constants and scan: rank_select.h;
+//   perm_counts_kernel     member(i) = below((thr_key, row_cut), key_i, i), local to every 16-row piece: problem 2p gets the members, problem
+//                          2p + 1 the complement, as 0/1 count rows (count_rows.h).
 #pragma once
-#include "philox.h"
-#include "wave_ops.h"
+#include "rank_select.h"
+#include "count_rows.h"
 
-#define PERM_NT 256                 // threads per workgroup of both membership kernels
-#define PERM_BINS 2048              // radix digits of 11 bits
-#define PERM_CACHE_ROWS 12288       // up to this many rows the keys stay in LDS (48 KB) after the first pass instead of being drawn again
+#define PERM_NT 256                 // threads per workgroup of perm_exceed_kernel
 
-// exclusive prefix sum over the 256 threads of a workgroup; *total = the sum of all.  Ends behind a barrier (lds4 is free again).
-__device__ __forceinline__ unsigned perm_block_scan(unsigned v, unsigned* lds4, unsigned* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned inc = wv::inclusive_scan(v);
-    if (lane == 63) lds4[w] = inc;
-    __syncthreads();
-    unsigned base = 0u, tot = 0u;
-#pragma unroll
-    for (int k = 0; k < PERM_NT / 64; ++k) { const unsigned t = lds4[k]; base += (k < w) ? t : 0u; tot += t; }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
-// thr[p] = (thr_key, row_cut) of permutation perm0 + p.  1 <= n1 <= N.  Dynamic LDS: N keys when `cache` (N <= PERM_CACHE_ROWS), else none.
-__global__ void __launch_bounds__(PERM_NT) perm_threshold_kernel(int N, int n1, uint64_t seed, int64_t perm0, int cache, uint2* __restrict__ thr) {
+// thr[p] = (thr_key, row_cut) of permutation perm0 + p.  1 <= n1 <= N.  Dynamic LDS: N keys when `cache` (N <= RANK_CACHE_ROWS), else none.
+__global__ void __launch_bounds__(RANK_NT) perm_threshold_kernel(int N, int n1, uint64_t seed, int64_t perm0, int cache, uint2* __restrict__ thr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     unsigned* keys = reinterpret_cast<unsigned*>(smem_raw);
-    __shared__ unsigned hist[PERM_BINS];
-    __shared__ unsigned scan4[PERM_NT / 64];
+    __shared__ unsigned hist[RANK_BINS];
+    __shared__ unsigned scan4[RANK_NT / 64];
     __shared__ unsigned sh_bin, sh_k, sh_cut;
     const int tid = threadIdx.x;
     const uint64_t r = (uint64_t)(perm0 + (int64_t)blockIdx.x);
@@ -45,10 +28,10 @@ __global__ void __launch_bounds__(PERM_NT) perm_threshold_kernel(int N, int n1, 
     for (int pass = 0; pass < 3; ++pass) {
         const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
         const unsigned dmask = pass == 2 ? 0x3ffu : 0x7ffu;
-        for (int i = tid; i < PERM_BINS; i += PERM_NT) hist[i] = 0u;
+        for (int i = tid; i < RANK_BINS; i += RANK_NT) hist[i] = 0u;
         __syncthreads();
         if (pass == 0 || !cache) {
-            for (int q = tid; q < nq; q += PERM_NT) {
+            for (int q = tid; q < nq; q += RANK_NT) {
                 const u32x4 u = permute_quad(seed, r, (uint32_t)q);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -61,7 +44,7 @@ __global__ void __launch_bounds__(PERM_NT) perm_threshold_kernel(int N, int n1, 
                 }
             }
         } else {
-            for (int i = tid; i < N; i += PERM_NT) {
+            for (int i = tid; i < N; i += RANK_NT) {
                 const unsigned key = keys[i];
                 if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & dmask], 1u);
             }
@@ -72,7 +55,7 @@ __global__ void __launch_bounds__(PERM_NT) perm_threshold_kernel(int N, int n1, 
 #pragma unroll
         for (int b = 0; b < 8; ++b) own += hist[8 * tid + b];
         unsigned tot;
-        const unsigned before = perm_block_scan(own, scan4, &tot);
+        const unsigned before = block_scan(own, scan4, &tot);
         if (before < k && k <= before + own) {
             unsigned c = before;
             int b = 0;
@@ -87,7 +70,7 @@ __global__ void __launch_bounds__(PERM_NT) perm_threshold_kernel(int N, int n1, 
     if (k < eq) {
         // ties straddle the cut (uniform over the workgroup): the k-th row of key == thr_key in row order is the last member
         unsigned need = k;
-        for (int q0 = 0; q0 < nq; q0 += PERM_NT) {
+        for (int q0 = 0; q0 < nq; q0 += RANK_NT) {
             const int q = q0 + tid;
             unsigned hit = 0u, c = 0u;                       // hit: bit j = row 4q + j has the threshold key
             if (q < nq) {
@@ -101,7 +84,7 @@ __global__ void __launch_bounds__(PERM_NT) perm_threshold_kernel(int N, int n1, 
                     if (4 * q + j < N && u.v[j] == prefix) { hit |= 1u << j; ++c; }
             }
             unsigned tot;
-            const unsigned before = perm_block_scan(c, scan4, &tot);
+            const unsigned before = block_scan(c, scan4, &tot);
             if (before < need && need <= before + c) {
                 unsigned seen = before;
                 for (int j = 0; j < 4; ++j)
@@ -116,23 +99,16 @@ __global__ void __launch_bounds__(PERM_NT) perm_threshold_kernel(int N, int n1, 
     if (tid == 0) thr[blockIdx.x] = make_uint2(prefix, cut);
 }
 
-// four 0/1 bits -> four bytes
-__device__ __forceinline__ unsigned perm_spread4(unsigned n) { return (n & 1u) | ((n & 2u) << 7) | ((n & 4u) << 14) | ((n & 8u) << 21); }
-
 // Counts of the chunk's problems 2p (group a) and 2p + 1 (group b) for its permutations p < nperm (ids perm0 + p); `member` (explicit
-// memberships, [nperm][N] bytes 0/1) replaces the thresholds when not null.  Thread (p = 8 x + tid % 8, piece c = 32 y + tid / 8): rows
-// 16c .. 16c + 15 -- the eight permutations of a thread group fill the 16 consecutive pieces of one fragment row (256 B per store wave).
-// Pieces of rows >= N are zero, as the resample kernels leave them.
-__global__ void __launch_bounds__(PERM_NT) perm_counts_kernel(int N, int KB, int MT, uint64_t seed, int64_t perm0, int nperm, const uint2* __restrict__ thr,
-                                                              const uint8_t* __restrict__ member, uint4* __restrict__ Cd) {
-    const int tid = threadIdx.x;
-    const int p = (int)blockIdx.x * 8 + (tid & 7);
-    const int c = (int)blockIdx.y * (PERM_NT / 8) + (tid >> 3);
-    if (p >= nperm || c >= KB * 4) return;
+// memberships, [nperm][N] bytes 0/1) replaces the thresholds when not null.  (2p even: both problems in the same count tile, two adjacent pieces.)
+__global__ void __launch_bounds__(COUNT_NT) perm_counts_kernel(int N, int KB, int MT, uint64_t seed, int64_t perm0, int nperm, const uint2* __restrict__ thr,
+                                                               const uint8_t* __restrict__ member, uint4* __restrict__ Cd) {
+    int p, c;
+    if (!count_row_thread(nperm, KB, p, c)) return;
     const int i0 = 16 * c;
-    unsigned bits = 0u, valid = 0u;                           // bit t: row i0 + t is in group a / exists
-    if (i0 < N) {
-        valid = (N - i0 >= 16) ? 0xffffu : ((1u << (N - i0)) - 1u);
+    const unsigned valid = count_row_valid(N, c);
+    unsigned bits = 0u;                                       // bit t: row i0 + t is in group a
+    if (valid) {
         if (member) {
             const uint8_t* mp = member + (long)p * N + i0;
             for (int t = 0; t < 16; ++t)
@@ -144,22 +120,14 @@ __global__ void __launch_bounds__(PERM_NT) perm_counts_kernel(int N, int KB, int
             for (int qq = 0; qq < 4; ++qq) {
                 const u32x4 u = permute_quad(seed, r, (uint32_t)(4 * c + qq));
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned i = (unsigned)(i0 + 4 * qq + j);
-                    if (u.v[j] < th.x || (u.v[j] == th.x && i < th.y)) bits |= 1u << (4 * qq + j);
-                }
+                for (int j = 0; j < 4; ++j)
+                    if (below(th, u.v[j], (unsigned)(i0 + 4 * qq + j))) bits |= 1u << (4 * qq + j);
             }
             bits &= valid;
         }
     }
-    const unsigned comp = ~bits & valid;
-    uint4 a, b;
-    a.x = perm_spread4(bits & 15u); a.y = perm_spread4((bits >> 4) & 15u); a.z = perm_spread4((bits >> 8) & 15u); a.w = perm_spread4(bits >> 12);
-    b.x = perm_spread4(comp & 15u); b.y = perm_spread4((comp >> 4) & 15u); b.z = perm_spread4((comp >> 8) & 15u); b.w = perm_spread4(comp >> 12);
-    const int prob = 2 * p, mt = prob >> 4, rr = prob & 15;   // (rr even: both problems in the same count tile)
-    uint4* dst = Cd + ((long)(c >> 2) * MT + mt) * 64 + (c & 3) * 16 + rr;
-    dst[0] = a;
-    dst[1] = b;
+    count_row_store(Cd, MT, c, 2 * p, bits);
+    count_row_store(Cd, MT, c, 2 * p + 1, ~bits & valid);
 }
 
 // Exceedance counts of B permutations whose records (pitch RS, status in column R) sit in pairs (2p: group a, 2p + 1: group b): per column j

@@ -30,38 +30,28 @@ __host__ __device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1
     u32x4 o; o.v[0] = c0; o.v[1] = c1; o.v[2] = c2; o.v[3] = c3;
     return o;
 }
-// Resample index i (0 <= i < N) of replicate `rep`: word (i & 3) of Philox(counter = (i >> 2, 0, rep), key = seed),
-// mapped to [0, N) by the 32x32 -> high-word multiply (bias <= N / 2^32).
-__host__ __device__ __forceinline__ u32x4 resample_quad(uint64_t seed, uint64_t rep, uint32_t q) {
-    return philox4x32_10(q, 0u, (uint32_t)rep, (uint32_t)(rep >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+// The streams: word (i & 3) of Philox(counter = (i >> 2, STREAM, lo32(rep), hi32(rep)), key = seed) belongs to element i of repetition `rep`.  Counter word 1
+// names the stream, so no two of them ever share a block:
+//   0  resample_quad  bootstrap: resample index i (0 <= i < N) of replicate `rep`, mapped to [0, N) by the 32x32 -> high-word multiply (bias <= N / 2^32)
+//   1  permute_quad   two-group permutation test: sort key of row i in permutation `rep`; group a = the n1 rows with the smallest (key, row) pairs
+//                     (rank_select.h, kernels_permute.h, plspm_permutation_members)
+//   2  strat_quad     stratified (within-group) bootstrap of the two-group test: draw j of problem `rep`; resample r makes problem 2r (group a, n_a draws from
+//                     its rows) and 2r + 1 (group b) -- kernels_strat.h, plspm_stratified_draws
+//   3  cv_quad        k-fold cross-validation: sort key of row i in repetition `rep`; the rows ordered by (key, row), the one at position j belongs to fold
+//                     (j * k) / N -- rank_select.h, kernels_cv.h, plspm_cv_folds
+//   4  fimix_quad     FIMIX-PLS: initial segment of row i in start `rep`, mapped to [0, K) by the high-word multiply, floor(u K) for u = word / 2^32 --
+//                     kernels_fimix.h, plspm_fimix_starts
+template <uint32_t STREAM>
+__host__ __device__ __forceinline__ u32x4 stream_quad(uint64_t seed, uint64_t rep, uint32_t q) {
+    return philox4x32_10(q, STREAM, (uint32_t)rep, (uint32_t)(rep >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
 }
+constexpr uint32_t STREAM_RESAMPLE = 0u, STREAM_PERMUTE = 1u, STREAM_STRAT = 2u, STREAM_CV = 3u, STREAM_FIMIX = 4u;
+__host__ __device__ __forceinline__ u32x4 resample_quad(uint64_t seed, uint64_t rep, uint32_t q) { return stream_quad<STREAM_RESAMPLE>(seed, rep, q); }
+__host__ __device__ __forceinline__ u32x4 permute_quad(uint64_t seed, uint64_t perm, uint32_t q) { return stream_quad<STREAM_PERMUTE>(seed, perm, q); }
+__host__ __device__ __forceinline__ u32x4 strat_quad(uint64_t seed, uint64_t s, uint32_t q) { return stream_quad<STREAM_STRAT>(seed, s, q); }
+__host__ __device__ __forceinline__ u32x4 cv_quad(uint64_t seed, uint64_t rep, uint32_t q) { return stream_quad<STREAM_CV>(seed, rep, q); }
+__host__ __device__ __forceinline__ u32x4 fimix_quad(uint64_t seed, uint64_t start, uint32_t q) { return stream_quad<STREAM_FIMIX>(seed, start, q); }
 __host__ __device__ __forceinline__ int32_t to_index(uint32_t u, uint32_t n) { return (int32_t)mulhi32(u, n); }
-// Sort key of row i (0 <= i < N) in permutation `perm` of the two-group test: word (i & 3) of Philox(counter = (i >> 2, 1, perm), key = seed).
-// Counter word 1 is 1 where the bootstrap's is 0, so the two streams never share a block.  Group a of the permutation = the n1 rows with the
-// smallest (key, row) pairs (kernels_permute.h, plspm_permutation_members).
-__host__ __device__ __forceinline__ u32x4 permute_quad(uint64_t seed, uint64_t perm, uint32_t q) {
-    return philox4x32_10(q, 1u, (uint32_t)perm, (uint32_t)(perm >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-// Draw word of problem `s` of the stratified (within-group) bootstrap of the two-group test: word (j & 3) of Philox(counter = (j >> 2, 2, s),
-// key = seed) for draw j.  Counter word 1 is 2 (bootstrap 0, permutation 1): the three streams never share a block.  Resample r makes problem
-// s = 2r (group a, n_a draws from its rows) and s = 2r + 1 (group b) -- kernels_strat.h, plspm_stratified_draws.
-__host__ __device__ __forceinline__ u32x4 strat_quad(uint64_t seed, uint64_t s, uint32_t q) {
-    return philox4x32_10(q, 2u, (uint32_t)s, (uint32_t)(s >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-// Sort key of row i (0 <= i < N) in repetition `rep` of the k-fold cross-validation: word (i & 3) of Philox(counter = (i >> 2, 3, rep), key = seed).
-// Counter word 1 is 3 (bootstrap 0, permutation 1, stratified draws 2): the four streams never share a block.  The rows ordered by (key, row): the
-// one at position j belongs to fold (j * k) / N -- kernels_cv.h, plspm_cv_folds.
-__host__ __device__ __forceinline__ u32x4 cv_quad(uint64_t seed, uint64_t rep, uint32_t q) {
-    return philox4x32_10(q, 3u, (uint32_t)rep, (uint32_t)(rep >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-// Initial segment of row i (0 <= i < N) in start `start` of FIMIX-PLS: word (i & 3) of Philox(counter = (i >> 2, 4, start), key = seed), mapped to
-// [0, K) by the high-word multiply, floor(u K) for u = word / 2^32.  Counter word 1 is 4: a stream of its own -- kernels_fimix.h, plspm_fimix_starts.
-__host__ __device__ __forceinline__ u32x4 fimix_quad(uint64_t seed, uint64_t start, uint32_t q) {
-    return philox4x32_10(q, 4u, (uint32_t)start, (uint32_t)(start >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-}
 __host__ __device__ __forceinline__ int fimix_start_segment(uint64_t seed, uint64_t start, uint32_t i, uint32_t K) {
     const u32x4 u = fimix_quad(seed, start, i >> 2);
     const uint32_t j = i & 3u, word = j == 0 ? u.v[0] : j == 1 ? u.v[1] : j == 2 ? u.v[2] : u.v[3];      // (no indexed register array on the device)

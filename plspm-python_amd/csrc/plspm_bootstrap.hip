@@ -614,6 +614,21 @@ int plspm_bootstrap_moments(plspm_model_t* m, int64_t B, uint64_t seed, int64_t 
 
 }  // extern "C"
 
+// ---- the calls that bring their own count rows (host_internal.h): what their entry points refuse alike, in two steps around their own argument checks
+int counts_call_scope(plspm_model* m, const char* who, int64_t min_rows) {
+    if (!m->d_Xa || m->N < min_rows) return fail(m, PLSPM_E_STATE, std::string(who) + ": no data uploaded");
+    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, std::string(who) + ": plain metric models only (no non-metric scales, no missing values, not part of a two-stage pair)");
+    return 0;
+}
+int counts_route_scope(plspm_model* m, const char* who) {
+    if (m->tune.i8_shape != 16) return fail(m, PLSPM_E_ARG, std::string(who) + ": needs the 16x16x64 layout of the int8 Gram (i8_shape 16)");
+    HIPCHK(m, hipSetDevice(m->device));
+    // the int8 route whatever "gram_path" / "i8_min_batch" say (the dense 0/1 counts are what it reads; they add up to less than N, and the statistics are differences
+    // of nearly equal estimates: seven digit planes at least), unless the route itself is closed at the seven planes such a call cuts
+    if (!gram_counts_route_open(m)) return fail(m, PLSPM_E_LIMIT, std::string(who) + ": the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
+    return 0;
+}
+
 // ---- side records (host_internal.h SideRecords): the state check, the fetch, the summary and the intervals that the entry points of plspm_derived.hip and plspm_micom_* share
 int side_state(plspm_model* m, const SideRecords& s, int64_t B, const char* who) {
     if (!s.count || !s.buf.p) return fail(m, PLSPM_E_STATE, std::string(who) + s.none);

@@ -10,8 +10,7 @@
 #include "kernels_cv.h"
 
 int launch_cv_counts(plspm_model* m, const CvSpec& cs, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
-    const dim3 grid((unsigned)((nb + 7) / 8), (unsigned)((KB * 4 + CV_NT / 8 - 1) / (CV_NT / 8)));
-    hipLaunchKernelGGL(cv_counts_kernel, grid, dim3(CV_NT), 0, m->stream, (int)m->N, KB, MT, cs.k, prob0, (int)nb, cs.d_fold, (uint4*)cd);
+    hipLaunchKernelGGL(cv_counts_kernel, count_rows_grid(nb, KB), dim3(COUNT_NT), 0, m->stream, (int)m->N, KB, MT, cs.k, prob0, (int)nb, cs.d_fold, (uint4*)cd);
     HIPCHK(m, hipGetLastError());
     return 0;
 }
@@ -25,13 +24,6 @@ static std::vector<int> cv_targets(const plspm_model* m) {
     return cols;
 }
 
-static int cv_scope(plspm_model* m, const char* who) {
-    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, std::string(who) + ": no data uploaded");
-    if (m->stage1 || m->stage2) return fail(m, PLSPM_E_ARG, std::string(who) + ": plain metric models only (this handle is part of a two-stage pair)");
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, std::string(who) + ": plain metric models only (no non-metric scales, no missing values)");
-    return 0;
-}
-
 // the last plspm_cv_device call's folds, moments and records are still on the handle, and they are (reps, k)'s
 static int cv_state(plspm_model* m, int64_t reps, int32_t k, const char* who) {
     if (!m->cv_reps || !m->rows_B || !m->rows.p) return fail(m, PLSPM_E_STATE, std::string(who) + ": no cross-validation on this handle (a later call replaced it)");
@@ -43,11 +35,7 @@ extern "C" {
 
 int plspm_cv_folds(uint64_t seed, int64_t rep, int64_t N, int32_t k, uint8_t* fold) {
     if (!fold || k < 2 || k > 256 || N < k || N > 0x7fffffffLL || rep < 0) return PLSPM_E_ARG;
-    std::vector<std::pair<uint32_t, uint32_t>> key((size_t)N);
-    for (int64_t q = 0; q < (N + 3) / 4; ++q) {
-        const u32x4 u = cv_quad(seed, (uint64_t)rep, (uint32_t)q);
-        for (int j = 0; j < 4; ++j) if (4 * q + j < N) key[(size_t)(4 * q + j)] = {u.v[j], (uint32_t)(4 * q + j)};
-    }
+    std::vector<std::pair<uint32_t, uint32_t>> key = row_keys(cv_quad, seed, rep, N);
     std::sort(key.begin(), key.end());
     for (int64_t j = 0; j < N; ++j) fold[key[(size_t)j].second] = (uint8_t)((j * k) / N);
     return 0;
@@ -64,8 +52,7 @@ int plspm_cv_device(plspm_model_t* m, int64_t reps, int32_t k, uint64_t seed, in
     if (!m || reps < 1 || k < 2 || k > 256 || reps * k > ((int64_t)1 << 29) || rep_offset < 0 || rep_offset > ((int64_t)1 << 61))
         return fail(m, PLSPM_E_ARG, "plspm_cv_device: bad arguments (1 <= reps, 2 <= k <= 256, reps * k <= 2^29, rep_offset >= 0)");
     int rc;
-    if ((rc = cv_scope(m, "plspm_cv_device"))) return rc;
-    if (m->tune.i8_shape != 16) return fail(m, PLSPM_E_ARG, "plspm_cv_device: needs the 16x16x64 layout of the int8 Gram (i8_shape 16)");
+    if ((rc = counts_call_scope(m, "plspm_cv_device"))) return rc;
     const int64_t N = m->N;
     if (!fold && (N < k || N - (N + k - 1) / k < 4)) return fail(m, PLSPM_E_ARG, "plspm_cv_device: every training set needs at least four rows (and every fold one)");
     if (fold) {
@@ -84,9 +71,7 @@ int plspm_cv_device(plspm_model_t* m, int64_t reps, int32_t k, uint64_t seed, in
             }
         }
     }
-    HIPCHK(m, hipSetDevice(m->device));
-    // the int8 route whatever "gram_path" / "i8_min_batch" say, seven planes at least (as plspm_permutation_device: the counts add up to n_train < N)
-    if (!gram_counts_route_open(m)) return fail(m, PLSPM_E_LIMIT, "plspm_cv_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
+    if ((rc = counts_route_scope(m, "plspm_cv_device"))) return rc;
     void_records(m, REC_CV);
     const int C1 = m->P + 1;
     const long MS = (long)C1 * (C1 + 1) / 2;
@@ -100,17 +85,17 @@ int plspm_cv_device(plspm_model_t* m, int64_t reps, int32_t k, uint64_t seed, in
     } else {
         if ((rc = ensure(m, m->cv_thr, (size_t)reps * (k - 1) * sizeof(uint2)))) return rc;
         // the keys in LDS after the first radix pass while they fit 48 KB; beyond that every pass draws them again
-        const bool cache = N <= CV_CACHE_ROWS;
+        const bool cache = N <= RANK_CACHE_ROWS;
         const size_t lds = cache ? (size_t)N * sizeof(unsigned) : 0;
         if ((rc = allow_lds(m, (const void*)cv_threshold_kernel, lds))) return rc;
         ProfScope ps(m, PLSPM_K_RESAMPLE);
-        hipLaunchKernelGGL(cv_threshold_kernel, dim3((unsigned)reps, (unsigned)(k - 1)), dim3(CV_NT), lds, m->stream, (int)N, k, seed, rep_offset, cache ? 1 : 0, (uint2*)m->cv_thr.p);
+        hipLaunchKernelGGL(cv_threshold_kernel, dim3((unsigned)reps, (unsigned)(k - 1)), dim3(RANK_NT), lds, m->stream, (int)N, k, seed, rep_offset, cache ? 1 : 0, (uint2*)m->cv_thr.p);
         hipLaunchKernelGGL(cv_assign_kernel, dim3((unsigned)reps, (unsigned)((N + 4 * CV_NT - 1) / (4 * CV_NT))), dim3(CV_NT), 0, m->stream, (int)N, k, seed, rep_offset,
                            (const uint2*)m->cv_thr.p, d_fold);
     }
     {
         ProfScope ps(m, PLSPM_K_RESAMPLE);
-        hipLaunchKernelGGL(cv_order_kernel, dim3((unsigned)reps, (unsigned)k), dim3(CV_NT), 0, m->stream, (int)N, k, (const uint8_t*)d_fold, (int*)m->cv_idx.p, (int*)m->cv_off.p);
+        hipLaunchKernelGGL(cv_order_kernel, dim3((unsigned)reps, (unsigned)k), dim3(RANK_NT), 0, m->stream, (int)N, k, (const uint8_t*)d_fold, (int*)m->cv_idx.p, (int*)m->cv_off.p);
     }
     HIPCHK(m, hipGetLastError());
     const CvSpec spec{reps, k, d_fold};
@@ -177,7 +162,7 @@ int plspm_cv_predict(plspm_model_t* m, int64_t reps, int32_t k, int32_t techniqu
     if (!m || technique < 0 || technique > 1 || !sse || !sae || !sst || !rows || (pred_sum == nullptr) != (pred_cnt == nullptr))
         return fail(m, PLSPM_E_ARG, "plspm_cv_predict: bad arguments (technique 0 / 1; sse, sae, sst, rows required; pred_sum and pred_cnt together)");
     int rc;
-    if ((rc = cv_scope(m, "plspm_cv_predict"))) return rc;
+    if ((rc = counts_call_scope(m, "plspm_cv_predict"))) return rc;
     if ((rc = cv_state(m, reps, k, "plspm_cv_predict"))) return rc;
     const std::vector<int> tcol = cv_targets(m);
     const int P = m->P, L = m->L, T = (int)tcol.size(), C1 = P + 1, N = (int)m->N;

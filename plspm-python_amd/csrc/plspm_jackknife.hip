@@ -8,8 +8,7 @@
 #include "kernels_jack.h"
 
 int launch_jack_counts(plspm_model* m, const JackSpec& js, int64_t nb, int64_t prob0, int MT, int KB, void* cd) {
-    const dim3 grid((unsigned)((nb + 7) / 8), (unsigned)((KB * 4 + JACK_NT / 8 - 1) / (JACK_NT / 8)));
-    hipLaunchKernelGGL(jack_counts_kernel, grid, dim3(JACK_NT), 0, m->stream, (int)m->N, KB, MT, (int)js.G, prob0, (int)nb, (uint4*)cd);
+    hipLaunchKernelGGL(jack_counts_kernel, count_rows_grid(nb, KB), dim3(COUNT_NT), 0, m->stream, (int)m->N, KB, MT, (int)js.G, prob0, (int)nb, (uint4*)cd);
     HIPCHK(m, hipGetLastError());
     return 0;
 }
@@ -25,19 +24,13 @@ extern "C" {
 
 int plspm_jackknife_device(plspm_model_t* m, int64_t G, void** d_out, void** d_status, void** d_iters) {
     if (!m) return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: no handle");
-    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_jackknife_device: no data uploaded");
-    if (m->stage1 || m->stage2) return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: plain metric models only (this handle is part of a two-stage pair)");
-    if (!plain_metric(m)) return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: plain metric models only (no non-metric scales, no missing values)");
+    int rc;
+    if ((rc = counts_call_scope(m, "plspm_jackknife_device"))) return rc;
     const int64_t N = m->N;
     if (G < 2 || G > N || N - (N + G - 1) / G < 4)
         return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: bad G (2 <= G <= N, and every problem keeps at least four rows)");
-    if (m->tune.i8_shape != 16) return fail(m, PLSPM_E_ARG, "plspm_jackknife_device: needs the 16x16x64 layout of the int8 Gram (i8_shape 16)");
-    HIPCHK(m, hipSetDevice(m->device));
-    // the int8 route whatever "gram_path" / "i8_min_batch" say, seven planes at least (as plspm_permutation_device: the counts add up to less than N, and
-    // the statistic is a difference of nearly equal estimates)
-    if (!gram_counts_route_open(m)) return fail(m, PLSPM_E_LIMIT, "plspm_jackknife_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
+    if ((rc = counts_route_scope(m, "plspm_jackknife_device"))) return rc;
     void_records(m, REC_JACK);
-    int rc;
     if ((rc = ensure(m, m->jack_rows, (size_t)G * plspm_row_stride(m) * sizeof(double)))) return rc;
     const JackSpec spec{G};
     BatchCall call;

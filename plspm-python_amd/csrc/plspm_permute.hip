@@ -20,15 +20,14 @@ int launch_perm_counts(plspm_model* m, const PermSpec& ps, int64_t nb, int64_t p
     if (!ps.d_member) {
         if ((rc = ensure(m, m->perm_thr, (size_t)np * sizeof(uint2)))) return rc;
         // the keys in LDS after the first radix pass while they fit 48 KB (three workgroups per CU); beyond that every pass draws them again
-        const bool cache = N <= PERM_CACHE_ROWS;
+        const bool cache = N <= RANK_CACHE_ROWS;
         const size_t lds = cache ? (size_t)N * sizeof(unsigned) : 0;
         if ((rc = allow_lds(m, (const void*)perm_threshold_kernel, lds))) return rc;
-        hipLaunchKernelGGL(perm_threshold_kernel, dim3((unsigned)np), dim3(PERM_NT), lds, m->stream, N, (int)ps.n1, ps.seed, ps.rep_offset + p0, cache ? 1 : 0,
+        hipLaunchKernelGGL(perm_threshold_kernel, dim3((unsigned)np), dim3(RANK_NT), lds, m->stream, N, (int)ps.n1, ps.seed, ps.rep_offset + p0, cache ? 1 : 0,
                            (uint2*)m->perm_thr.p);
         thr = (const uint2*)m->perm_thr.p;
     }
-    const dim3 grid((unsigned)((np + 7) / 8), (unsigned)((KB * 4 + PERM_NT / 8 - 1) / (PERM_NT / 8)));
-    hipLaunchKernelGGL(perm_counts_kernel, grid, dim3(PERM_NT), 0, m->stream, N, KB, MT, ps.seed, ps.rep_offset + p0, (int)np, thr,
+    hipLaunchKernelGGL(perm_counts_kernel, count_rows_grid(np, KB), dim3(COUNT_NT), 0, m->stream, N, KB, MT, ps.seed, ps.rep_offset + p0, (int)np, thr,
                        ps.d_member ? ps.d_member + p0 * (int64_t)N : (const uint8_t*)nullptr, (uint4*)cd);
     HIPCHK(m, hipGetLastError());
     return 0;
@@ -91,19 +90,14 @@ int plspm_stratified_bootstrap_device(plspm_model_t* m, int64_t B, uint64_t seed
                                       void** d_status, void** d_iters) {
     if (!m || B < 1 || B > ((int64_t)1 << 29) || rep_offset < 0 || rep_offset > ((int64_t)1 << 61) || !member)
         return fail(m, PLSPM_E_ARG, "plspm_stratified_bootstrap_device: bad arguments (1 <= B <= 2^29, rep_offset >= 0, member required)");
-    if (!m->d_Xa || m->N < 4) return fail(m, PLSPM_E_STATE, "plspm_stratified_bootstrap_device: no data uploaded");
-    if (!plain_metric(m))
-        return fail(m, PLSPM_E_ARG, "plspm_stratified_bootstrap_device: plain metric models only (no non-metric scales, no missing values, no two-stage pair)");
-    if (m->tune.i8_shape != 16) return fail(m, PLSPM_E_ARG, "plspm_stratified_bootstrap_device: needs the 16x16x64 layout of the int8 Gram (i8_shape 16)");
+    int rc;
+    if ((rc = counts_call_scope(m, "plspm_stratified_bootstrap_device", 4))) return rc;
     const int64_t N = m->N;
     std::vector<int32_t> grp((size_t)N);
     const int64_t n_a = strat_split(member, N, grp.data());
     if (n_a < 0) return fail(m, PLSPM_E_ARG, "plspm_stratified_bootstrap_device: memberships must be 0 or 1");
     if (n_a < 2 || N - n_a < 2) return fail(m, PLSPM_E_ARG, "plspm_stratified_bootstrap_device: each group needs at least two rows");
-    HIPCHK(m, hipSetDevice(m->device));
-    // the int8 route whatever "gram_path" / "i8_min_batch" say, seven planes at least (as plspm_permutation_device)
-    if (!gram_counts_route_open(m)) return fail(m, PLSPM_E_LIMIT, "plspm_stratified_bootstrap_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
-    int rc;
+    if ((rc = counts_route_scope(m, "plspm_stratified_bootstrap_device"))) return rc;
     const size_t row_bytes = (size_t)N * sizeof(int32_t);
     if (!m->strat_rows.p || m->strat_member.size() != (size_t)N || !std::equal(member, member + N, m->strat_member.begin())) {
         if ((rc = ensure(m, m->strat_rows, row_bytes))) return rc;
@@ -178,11 +172,7 @@ int plspm_stratified_pair_counts(plspm_model_t* m, int64_t B, const double* cent
 
 int plspm_permutation_members(uint64_t seed, int64_t perm, int64_t N, int64_t n1, uint8_t* member) {
     if (!member || N < 2 || N > 0x7fffffffLL || perm < 0 || n1 < 1 || n1 >= N) return PLSPM_E_ARG;
-    std::vector<std::pair<uint32_t, uint32_t>> key((size_t)N);
-    for (int64_t q = 0; q < (N + 3) / 4; ++q) {
-        const u32x4 u = permute_quad(seed, (uint64_t)perm, (uint32_t)q);
-        for (int j = 0; j < 4; ++j) if (4 * q + j < N) key[(size_t)(4 * q + j)] = {u.v[j], (uint32_t)(4 * q + j)};
-    }
+    std::vector<std::pair<uint32_t, uint32_t>> key = row_keys(permute_quad, seed, perm, N);
     std::nth_element(key.begin(), key.begin() + (n1 - 1), key.end());
     const std::pair<uint32_t, uint32_t> last = key[(size_t)(n1 - 1)];       // the n1-th smallest (key, row) pair
     for (int64_t i = 0; i < N; ++i) member[i] = 0;
@@ -193,17 +183,11 @@ int plspm_permutation_members(uint64_t seed, int64_t perm, int64_t N, int64_t n1
 int plspm_permutation_device(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offset, int64_t n1, const uint8_t* member, void** d_out, void** d_status,
                              void** d_iters) {
     if (!m || B < 1 || B > ((int64_t)1 << 29) || rep_offset < 0) return fail(m, PLSPM_E_ARG, "plspm_permutation_device: bad arguments (1 <= B <= 2^29, rep_offset >= 0)");
-    if (!m->d_Xa || m->N < 2) return fail(m, PLSPM_E_STATE, "plspm_permutation_device: no data uploaded");
-    if (n1 < 1 || n1 >= m->N) return fail(m, PLSPM_E_ARG, "plspm_permutation_device: the group size must satisfy 1 <= n1 < N");
-    if (!plain_metric(m))
-        return fail(m, PLSPM_E_ARG, "plspm_permutation_device: plain metric models only (no non-metric scales, no missing values, no two-stage pair)");
-    if (m->tune.i8_shape != 16) return fail(m, PLSPM_E_ARG, "plspm_permutation_device: needs the 16x16x64 layout of the int8 Gram (i8_shape 16)");
-    HIPCHK(m, hipSetDevice(m->device));
-    // the int8 route whatever "gram_path" / "i8_min_batch" say (the dense 0/1 counts are what it reads), unless the route itself is closed at the seven
-    // planes this call cuts
-    if (!gram_counts_route_open(m)) return fail(m, PLSPM_E_LIMIT, "plspm_permutation_device: the int8 Gram route is closed for this data set (N >= 2^24, or digit planes above their 24 GiB budget)");
-    const uint8_t* d_member = nullptr;
     int rc;
+    if ((rc = counts_call_scope(m, "plspm_permutation_device"))) return rc;
+    if (n1 < 1 || n1 >= m->N) return fail(m, PLSPM_E_ARG, "plspm_permutation_device: the group size must satisfy 1 <= n1 < N");
+    if ((rc = counts_route_scope(m, "plspm_permutation_device"))) return rc;
+    const uint8_t* d_member = nullptr;
     if (member) {
         // explicit memberships (tests): every row of bytes 0/1 with exactly n1 ones
         for (int64_t p = 0; p < B; ++p) {

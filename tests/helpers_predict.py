@@ -134,7 +134,7 @@ def mean_predictions(problems, n, key="pred"):
 # ------------------------------------------------------------------ launch geometry of the prediction kernels, restated (plspm_cv.hip, kernels_cv.h)
 CV_NT = 256                     # threads of a cv_apply_kernel workgroup
 CV_MAX_LDS = 160 * 1024         # LDS a workgroup may take
-CV_CACHE_ROWS = 12288           # up to this many rows cv_threshold_kernel keeps the keys in LDS
+RANK_CACHE_ROWS = 12288         # up to this many rows rank_select.h (cv_threshold_kernel, perm_threshold_kernel) keeps the keys in LDS
 
 
 def cv_apply_lds(P, T, nrg):

@@ -2,7 +2,9 @@
 
   B1  G = 257, 512, 600: thread t takes the problems t, t + 256, ... -- two and three trips of the `g += 256` loops, a second trip of one thread only
       (257), whole trips (512) and a ragged last one (600: leave-one-out);
-  B2  some problems fail and most do not: the statistics run over the OK records alone.
+  B2  some problems fail and most do not: the statistics run over the OK records alone;
+  B3  N = 37: the count rows (jack_counts_kernel on count_rows.h) with a tail piece and a ragged last group of problems, against a cross-validation
+      handed the same kept rows.
 
 The bars are those of tests/test_gpu_ci.py (mean, std.error rtol 1e-12; accel atol 1e-12), against the package's mirror and against math.fsum
 (tests/helpers_ci.py).  They still hold at n = 600: a fixed-order fp64 sum of n cubes is off by n eps of sum |d|^3 <= (sum d^2)^1.5 at most, so the
@@ -64,6 +66,28 @@ def test_more_problems_than_threads(G):
     first_trip = _jackknife_stats(rows[:JACK_NT])
     with np.errstate(invalid="ignore", divide="ignore"):
         assert np.nanmax(np.abs(first_trip[0] / stats[0] - 1)) > 1e-9 and np.nanmax(np.abs(first_trip[1] / stats[1] - 1)) > 1e-3
+
+
+@pytest.mark.parametrize("G", [37, 5])
+def test_count_rows_with_a_tail_piece(G):
+    """N = 37: two whole 16-row pieces and a tail of five rows (kernels_jack.h jack_counts_kernel on count_rows.h); G = 37 (leave-one-out: five groups of eight
+    problems, the last ragged) and G = 5 (29 or 30 rows kept).  The records are bit for bit those of a cross-validation handed the folds i % G -- the same kept
+    rows as explicit bytes --, and the first and the last problem are the oracle's fits."""
+    n = 37
+    X, blocks = orc.synth(n, C3, 2, seed=14)
+    model = orc.Model(blocks, C3, "AAA", "path", True)
+    nm = native_model(model, X)
+    assert n - -(-n // G) >= 4
+    nm.jackknife(G)
+    assert nm.get_option("last_gram_path") == 2
+    rows, status, iters = nm.jackknife_fetch(0, G)
+    nm.cv(1, G, fold=(np.arange(n) % G).astype(np.uint8)[None, :])
+    rows2, status2, iters2 = nm.fetch(0, G)
+    assert np.array_equal(status, status2) and np.array_equal(iters, iters2) and np.array_equal(rows, rows2, equal_nan=True)
+    for g in (0, G - 1):
+        mine, its = oracle_record(X, model, np.arange(n) % G != g)
+        assert status[g] == 0 and iters[g] == its, (g, status[g], iters[g], its)
+        assert_close(rows[g], mine, RTOL, ATOL, what="jackknife problem %d of %d" % (g, G))
 
 
 def test_some_problems_fail_and_the_rest_are_used():

@@ -79,6 +79,30 @@ def test_device_splits_with_key_ties_at_the_cut(n, cached):
     assert np.array_equal(rows, rows2, equal_nan=True) and np.array_equal(status, status2) and np.array_equal(iters, iters2)
 
 
+@pytest.mark.parametrize("n1", [1, 36])
+def test_device_splits_with_a_tail_piece_and_a_ragged_problem_group(n1):
+    """N = 37: two whole 16-row pieces and a tail of five rows, whose mask also bounds the complement's bits; B = 9: a second group of eight permutations
+    with one member; n1 = 1 and N - 1: the smallest and the largest rank, and a group of one row, whose fit fails alike in either call."""
+    from plspm import _native
+    n, B, seed = 37, 9, 41
+    C = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0]])
+    X, blocks = orc.synth(n, C, 2, seed=14)
+    model = orc.Model(blocks, C, "AAA", "path", True)
+    nm = native_model(model, X)
+    rows, status, iters = run_perm(nm, B, n1, seed)
+    member = np.stack([_native.permutation_members(seed, p, n, n1) for p in range(B)])
+    assert np.all(member.sum(axis=1) == n1)
+    rows2, status2, iters2 = run_perm(nm, B, n1, member=member)
+    print("n1 %d: status %s" % (n1, status.tolist()))
+    assert np.array_equal(status, status2) and np.array_equal(iters, iters2) and np.array_equal(rows, rows2, equal_nan=True)
+    big = 0 if n1 > 1 else 1                                             # the group of 36 rows: the oracle's fit (the tail mask is the same in both calls)
+    assert np.all(status[1 - big::2] != 0)                               # the group of one row: a failure, the same in both calls (above)
+    for p in (0, B - 1):
+        mine, its = oracle_record(X, model, member[p] if big == 0 else ~member[p])
+        assert status[2 * p + big] == 0 and iters[2 * p + big] == its, (p, status[2 * p + big], iters[2 * p + big], its)
+        assert_close(rows[2 * p + big], mine, RTOL, ATOL, what="permutation %d, the group of 36 rows" % p)
+
+
 # ------------------------------------------------------------------ parity with the oracle
 @pytest.mark.parametrize("modes", ["A", "B", "M"])
 @pytest.mark.parametrize("scheme", ["centroid", "factorial", "path"])

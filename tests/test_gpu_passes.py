@@ -149,6 +149,30 @@ def test_jackknife_in_three_passes():
         check_oracle(X, model, records, q, np.arange(N) % G != q)
 
 
+def test_the_calls_that_bring_counts_refuse_alike():
+    """plspm_bootstrap.hip counts_call_scope in front of all four: a handle without data is PLSPM_E_STATE (101), a non-metric one PLSPM_E_ARG (100) and says why."""
+    from plspm import _native
+    X, model, _ = handle()
+    boff = np.concatenate(([0], np.cumsum([len(b) for b in model.blocks]))).astype(np.int32)
+    modes = np.zeros(3, dtype=np.int32)
+    member = np.arange(N) < 700
+
+    def calls(nm):
+        return (("plspm_permutation_device", lambda: nm.permutation(4, 800, 1)),
+                ("plspm_stratified_bootstrap_device", lambda: nm.stratified_bootstrap(4, member[:nm.N], 1)),
+                ("plspm_cv_device", lambda: nm.cv(2, 5, 1)),
+                ("plspm_jackknife_device", lambda: nm.jackknife(10)))
+    empty = _native.NativeModel(boff, model.C.astype(np.uint8), modes, 2, True, 100, 1e-6, 0)
+    for who, call in calls(empty):
+        with pytest.raises(_native.NativeBackendError, match=r"%s failed \(101\)" % who):
+            call()
+    nonmetric = _native.NativeModel(boff, model.C.astype(np.uint8), modes, 2, True, 100, 1e-6, 0, nonmetric=True)
+    nonmetric.upload(X)
+    for who, call in calls(nonmetric):
+        with pytest.raises(_native.NativeBackendError, match=r"%s failed \(100\).*plain metric" % who):
+            call()
+
+
 def test_the_plan_is_what_runs():
     """csrc/batch_route.h through the emulation build (helpers_batch_route) against the handle's own report: the passes and the Gram route of this file's handle at
     B 600, uncapped and capped, on either Gram; and of a Scale.NUM handle of 300 rows."""

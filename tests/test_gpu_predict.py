@@ -108,6 +108,32 @@ def test_device_folds_equal_the_host_mirror(n, k, reps, offset):
         assert np.array_equal(x, y, equal_nan=True)
 
 
+@pytest.mark.parametrize("k", [2, 9])
+def test_device_folds_and_count_rows_with_a_tail_piece(k):
+    """N = 37: two whole 16-row pieces and a tail of five rows; reps * k = 6 and 27 problems: a ragged last group of eight.  The folds are the host mirror's, the
+    records those of the same folds handed in, and the first and the last problem the oracle's fits on their training rows."""
+    from plspm import _native
+    n, reps, seed = 37, 3, 19
+    C = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0]])
+    X, blocks = orc.synth(n, C, 2, seed=14)
+    model = orc.Model(blocks, C, "AAA", "path", True)
+    nm = native_model(model, X)
+    mirror = np.stack([_native.cv_folds(seed, r, n, k) for r in range(reps)])
+    assert all(n - np.bincount(mirror[r], minlength=k).max() >= 4 and np.bincount(mirror[r], minlength=k).min() >= 1 for r in range(reps))
+    nm.cv(reps, k, seed=seed)
+    assert np.array_equal(nm.cv_fold_ids(reps, k)[0], mirror)
+    a = nm.fetch(0, reps * k)
+    nm.cv(reps, k, fold=mirror)
+    b = nm.fetch(0, reps * k)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y, equal_nan=True)
+    rows, status, iters = a
+    for q in (0, reps * k - 1):
+        mine, its = oracle_record(X, model, mirror[q // k] != q % k)
+        assert status[q] == 0 and iters[q] == its, (q, status[q], iters[q], its)
+        assert_close(rows[q], mine, RTOL, ATOL, what="training fit of problem %d" % q)
+
+
 # ------------------------------------------------------------------ predictions and error sums
 @pytest.mark.parametrize("scheme,scaled,modes", [("path", False, "AAAAAA"), ("path", True, "AABAAA"), ("centroid", True, "AAAAAA"), ("centroid", False, "AABAAA")])
 def test_satisfaction_predictions_vs_helper(scheme, scaled, modes):

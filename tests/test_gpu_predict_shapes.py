@@ -23,7 +23,7 @@ import pytest
 import plspm_oracle as orc
 from helpers import assert_close
 from helpers_mga import oracle_record
-from helpers_predict import (CV_CACHE_ROWS, CV_MAX_LDS, _find_cv_tie, cv_apply_lds, cv_apply_row_groups, cv_folds, synth_sized,
+from helpers_predict import (RANK_CACHE_ROWS, CV_MAX_LDS, _find_cv_tie, cv_apply_lds, cv_apply_row_groups, cv_folds, synth_sized,
                              training_moments_longdouble, training_moments_two_pass)
 from test_gpu_predict import check_predictions, host_folds, native_model
 
@@ -243,10 +243,10 @@ def test_training_moments_against_extended_precision(sizes):
 # ------------------------------------------------------------------ A4: key ties at a fold boundary
 @pytest.mark.parametrize("n,search,cached", [(12288, 4000, True), (200000, 64, False)])
 def test_device_folds_with_key_ties_at_a_fold_boundary(n, search, cached):
-    """cv_threshold_kernel's branch kk < eq: two rows share the key of a fold boundary and the row index decides -- with the keys in LDS (N = CV_CACHE_ROWS) and
+    """cv_threshold_kernel's branch kk < eq: two rows share the key of a fold boundary and the row index decides -- with the keys in LDS (N = RANK_CACHE_ROWS) and
     drawn again in every pass."""
     from plspm import _native
-    assert (n <= CV_CACHE_ROWS) == cached
+    assert (n <= RANK_CACHE_ROWS) == cached
     seed = 5
     found = _find_cv_tie(seed, n, range(search))
     assert found is not None
