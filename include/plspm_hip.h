@@ -784,6 +784,40 @@ int plspm_tetrad_fetch(plspm_model_t* m, int64_t first, int64_t count, double* o
 int plspm_tetrad_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
 int plspm_tetrad_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
 
+/* Importance-performance map analysis (IPMA; this project's definitions after Ringle & Sarstedt 2016, csrc/ipma_core.h): for a target construct,
+ * which antecedent constructs and indicators matter most (their unstandardised total effects) and how well do they perform on a 0-100 scale?  With fixed bounds
+ * lo_p < hi_p per MV (range_p = hi_p - lo_p), the rescaled indicator x~_p = 100 (x_p - lo_p) / range_p, and per data set mu_p, s_p, r_pq as the assessment has
+ * them, the raw mean m_p = shift_p + mu_p, v = w s normalised per block to v' R v = 1 and the fit's sign sigma_l:  a_p = sigma_l v_p range_p / (100 s_p) is the
+ * coefficient of x~_p in the standardised score, A_l = sum_{p in l} a_p.
+ * Record, width W = 2 L + 2 n_eff + 2 P + n_t P:
+ *     perf [L] | sd [L] | total_u [n_eff] | direct_u [n_eff] | weight_r [P] | mvperf [P] | mvimp [n_t x P]
+ * weight_r_p = a_p / A_l (1 in sum per block), mvperf_p = 100 (m_p - lo_p) / range_p, perf_l = sum weight_r_p mvperf_p (the mean of Y_l = sum weight_r_p x~_p),
+ * sd_l = 1 / A_l (its standard deviation), total_u[e] = total[e] A_i / A_j and direct_u[e] likewise for the effect pair e = (i -> j) of plspm_effect_pairs,
+ * mvimp[t][p] = weight_r_p total_u(l -> target t) for the MV p of LV l (0 without an effect pair l -> t and for the target's own block).  MVs in device order,
+ * targets in ascending LV order; status and iterations behind the values as doubles (pitch W + 2).  A replicate whose bootstrap status is not PLSPM_OK keeps that
+ * status and has NaN in all values; otherwise PLSPM_NONFINITE where a value is not finite (a column that is constant in the resample), otherwise 4
+ * (inadmissible, as the PLSc records) where a rescaled weight is negative -- the values stand under both, and neither enters a summary or an interval.
+ * Plain metric handles only: PLSPM_E_ARG otherwise.
+ *
+ * plspm_ipma_enable: on != 0: targets [L] names the target LVs (NULL: every LV with a predecessor), lo / hi [P] the bounds in device order -- every later
+ *   plspm_bootstrap / plspm_bootstrap_device call on this handle also writes the IPMA records of its replicates into a buffer of their own, indexed like the
+ *   bootstrap's records; every other record is bit for bit what it is without it.  on = 0: off (the default): no launch, no allocation.  PLSPM_E_ARG for a bound
+ *   that is not finite or lo_p >= hi_p (the message names the MV), for a mask that names no LV or an LV without a predecessor; PLSPM_E_LIMIT where one replicate's
+ *   statistics exceed a workgroup's 160 KiB of LDS.  Permutation, stratified, cross-validation, jackknife and group calls write none.
+ * plspm_ipma_width: W (0 before the first plspm_ipma_enable that switched it on).
+ * plspm_ipma_targets: *n_t and the targets' LV indices, ascending; either pointer may be NULL.
+ * plspm_ipma_fit: the full-sample record, out [W]: the same kernel on the moments of all uploaded rows; *status (may be NULL): the record's status.
+ * plspm_ipma_fetch / _summary / _intervals: as plspm_tetrad_fetch / _summary / _intervals, on the IPMA records (methods 0 .. 2, any level in (0, 1)).
+ * PLSPM_E_STATE from the last three without IPMA records on the handle (whatever voids the assessment records voids these; a jackknife leaves them alone).
+ */
+int plspm_ipma_enable(plspm_model_t* m, int32_t on, const uint8_t* targets, const double* lo, const double* hi);
+int32_t plspm_ipma_width(const plspm_model_t* m);
+int plspm_ipma_targets(plspm_model_t* m, int32_t* n_t, int32_t* lv);
+int plspm_ipma_fit(plspm_model_t* m, double* out, int32_t* status);
+int plspm_ipma_fetch(plspm_model_t* m, int64_t first, int64_t count, double* out, int32_t* status);
+int plspm_ipma_summary(plspm_model_t* m, int64_t B, const double* original, double* summary, int64_t* n_used);
+int plspm_ipma_intervals(plspm_model_t* m, int64_t B, const double* original, int32_t method, double level, double* out, int64_t* n_used);
+
 /*
  * ---- MICOM: permutation test of measurement invariance --------------------------------------------------------------------------
  * Measurement invariance of composite models (Henseler, Ringle and Sarstedt 2016), steps 2 and 3, for every permutation of plspm_permutation_device: one more
@@ -948,7 +982,7 @@ int plspm_op_outer_weights_nonmetric(int32_t device_id, int32_t mode, const doub
                                      double correction, double* w, double* Y);
 
 /* Kernel timing with HIP events on the handle's own stream (for the roofline figures in bench.py).
- * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM, PLSc, model-fit and tetrad kernels),
+ * kernel ids: 0 resample/compact, 1 gram (MFMA), 2 solver, 3 scores, 4 upload/pack, 5 gram reduce (and the counts on records), 6 assessment (and the MICOM, PLSc, model-fit, tetrad and IPMA kernels),
  * 7 .. 10 the moderation kernels: counts, prepare, row pass, finish. */
 enum { PLSPM_K_RESAMPLE = 0, PLSPM_K_GRAM = 1, PLSPM_K_SOLVER = 2, PLSPM_K_SCORES = 3, PLSPM_K_PACK = 4, PLSPM_K_REDUCE = 5, PLSPM_K_ASSESS = 6, PLSPM_K_MOD_COUNTS = 7, PLSPM_K_MOD_PREPARE = 8, PLSPM_K_MOD_ROWS = 9,
        PLSPM_K_MOD_FINISH = 10, PLSPM_K_COUNT = 11 };

@@ -195,6 +195,13 @@ int tetrad_begin(plspm_model* m, const BatchCall& call, int* runs);
 int tetrad_launch(plspm_model* m, int runs, long nb, int64_t pos, bool dense, const double* gram, const double* rows, long row_stride);
 void tetrad_commit(plspm_model* m, int runs, int64_t B);
 
+// ---- plspm_ipma.hip: the importance-performance records of a plain metric bootstrap's replicates, beside the tetrad's three calls and by the same
+// rule: *runs = 1 when the handle's switch is on and the call's owner takes the records, else 0; a slice the LDS does not hold is refused in ipma_begin.
+int ipma_begin(plspm_model* m, const BatchCall& call, int* runs);
+// Once per pass, behind tetrad_launch: `nb` problems whose records start at position `pos` of the record buffer; gram / rows as derived_launch takes them.
+int ipma_launch(plspm_model* m, int runs, long nb, int64_t pos, bool dense, const double* gram, const double* rows, long row_stride);
+void ipma_commit(plspm_model* m, int runs, int64_t B);
+
 // ---- plspm_bootstrap.hip: side records -- a buffer of records [count x (width + 2)] (values | status | iterations) beside the bootstrap records, valid while
 // `count` is non-zero: the records of every stage of plspm_derived.hip, the MICOM records of a permutation call.  One description, and the entry points all share.
 // plain_only: the entry points refuse any other handle kind behind their argument check (MICOM; the assessment answers "no records" there).  none / differs /

@@ -207,6 +207,14 @@ struct plspm_model {
     int tet_n = 0; long tet_tri = 0;         // ... tetrads; doubles of the staged triangles
     Buf tet_desc, tet_rows, tet_fit;         // ... descriptors | triangle offsets on the device; the records; the full-sample problem and its record
     int64_t tet_B = 0;                       // ... the last plain bootstrap whose tetrad records are on the handle (0: none)
+    // importance-performance map analysis (plspm_ipma.hip): the switch and the targets (ascending LV indices) from plspm_ipma_enable; the
+    // lists on the device (ipma_core.h IpmaBuild: lvof | targets | eff_of) and the bounds it was given (lo | hi, [P] each, device order); the replicates' records [ipma_B x (W + 2)] in a buffer of
+    // their own, indexed by the replicate's position in the whole call
+    bool ipma_on = false;
+    int ipma_nt = 0;                         // ... targets (0: never enabled)
+    std::vector<int> ipma_targets;
+    Buf ipma_ints, ipma_bounds, ipma_rows, ipma_fit;      // ... the lists; the bounds; the records; the full-sample problem and its record
+    int64_t ipma_B = 0;                      // ... the last plain bootstrap whose IPMA records are on the handle (0: none)
     // MICOM records of a permutation call's splits (kernels_micom.h; plspm_micom_*): records [micom_B x (3 L + 2)] in a buffer of their own, indexed by the
     // permutation's position in the call; the pooled inputs (u, the diagonal blocks of R_0; plspm_micom.hip micom_prepare) once per upload
     bool micom_on = false;                   // plspm_micom_enable
@@ -287,7 +295,7 @@ inline void void_records(plspm_model* m, unsigned which) {
     // records go when a stage it reads goes, and a row reads rows before it).  PLSc reads the assessment, so REC_ASSESS takes every derived record with it and
     // REC_PLSC those from PLSc on; every caller names the two together.
     static_assert(plspm::kDerivedStage[plspm::STAGE_PLSC].reads & plspm::stage_bit(plspm::STAGE_ASSESS), "REC_ASSESS voids the PLSc records and what follows them");
-    if (which & REC_ASSESS) m->mod_B = m->tet_B = 0;      // (the moderation and the tetrad records go exactly when the derived records do)
+    if (which & REC_ASSESS) m->mod_B = m->tet_B = m->ipma_B = 0;      // (the moderation, the tetrad and the IPMA records go exactly when the derived records do)
     int gone = (which & REC_ASSESS ? plspm::stage_bit(plspm::STAGE_ASSESS) : 0) | (which & REC_PLSC ? plspm::stage_bit(plspm::STAGE_PLSC) : 0);
     for (int s = 0; s < plspm::kDerivedStages; ++s)
         if (gone & (plspm::stage_bit(s) | plspm::kDerivedStage[s].reads)) { gone |= plspm::stage_bit(s); m->derived[s].B = 0; }

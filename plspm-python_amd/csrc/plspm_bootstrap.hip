@@ -28,6 +28,7 @@ struct BatchRun {
     int chain; int64_t chain_base;                       // the derived records (plspm_derived.hip): the stages that run, position of the call's first record
     int mod;                                             // the moderation records (plspm_moderation.hip): non-zero when they are written, from the same position
     int tet;                                             // the tetrad records (plspm_tetrad.hip): likewise
+    int ipma;                                            // the importance-performance records (plspm_ipma.hip): likewise
     double* rows_out; plspm_model::Buf *status_buf, *iters_buf;
 };
 // ... and of one pass: problems [b0, b0 + nb), what the int8 Gram left, what batch_chunk made of it, where the solver writes
@@ -163,6 +164,7 @@ static int solve_metric(BatchRun& r, const BatchPass& ps) {
                                 r.R)))
         return rc;
     if ((rc = tetrad_launch(m, r.tet, ps.nb, r.chain_base + ps.b0, dense, gram, ps.so.row, r.R))) return rc;
+    if ((rc = ipma_launch(m, r.ipma, ps.nb, r.chain_base + ps.b0, dense, gram, ps.so.row, r.R))) return rc;
     // (a pass holds whole 256-problem tiles: the pairs stay together, and the pass that starts at problem b0 starts at permutation b0 / 2)
     if (r.plan.micom) return launch_micom(m, ps.nb / 2, dense, gram, ps.so.row, (double*)m->micom_rows.p + (ps.b0 / 2) * r.plan.micom_stride);
     return 0;
@@ -182,7 +184,7 @@ static int batch_solve(BatchRun& r, BatchPass& ps) {
 static void batch_commit(BatchRun& r) {
     plspm_model* m = r.m;
     if (r.rows_out == (double*)m->rows.p) m->rows_B = r.call.B;
-    if (!r.call.rows_out) { derived_commit(m, r.chain, r.call.B); moderation_commit(m, r.mod, r.call.B); tetrad_commit(m, r.tet, r.call.B); }
+    if (!r.call.rows_out) { derived_commit(m, r.chain, r.call.B); moderation_commit(m, r.mod, r.call.B); tetrad_commit(m, r.tet, r.call.B); ipma_commit(m, r.ipma, r.call.B); }
     if (r.plan.micom) m->micom_B = r.call.B / 2;
 }
 
@@ -202,7 +204,7 @@ int plspm_detail_bootstrap(plspm_model* m, BatchCall& call) {
     void_records(m, call);
     // The derived records of a plain bootstrap: a call of its own (rows_out null) sizes their buffers and starts at record 0; a sub-batch of plspm_bootstrap()
     // writes from its position in that call (call.chain_off; the buffers are plspm_bootstrap's).
-    if ((rc = derived_begin(m, call, &r.chain)) || (rc = moderation_begin(m, call, &r.mod)) || (rc = tetrad_begin(m, call, &r.tet))) return rc;
+    if ((rc = derived_begin(m, call, &r.chain)) || (rc = moderation_begin(m, call, &r.mod)) || (rc = tetrad_begin(m, call, &r.tet)) || (rc = ipma_begin(m, call, &r.ipma))) return rc;
     r.chain_base = call.rows_out ? call.chain_off : 0;
     if ((rc = batch_error_word(r))) return rc;
     for (int64_t b0 = 0; b0 < call.B; b0 += r.plan.chunk) {
@@ -269,15 +271,15 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     if ((rc = ensure(m, m->rows, (size_t)B * RS * sizeof(double)))) return rc;
     double* const rows = (double*)m->rows.p;
     // the derived records follow the sub-batches: one buffer per stage for the whole call, every part writes from its first replicate's position (call.chain_off)
-    int chain = 0, mod = 0, tet = 0;
-    if ((rc = derived_begin(m, call, &chain)) || (rc = moderation_begin(m, call, &mod)) || (rc = tetrad_begin(m, call, &tet))) return rc;
+    int chain = 0, mod = 0, tet = 0, ipma = 0;
+    if ((rc = derived_begin(m, call, &chain)) || (rc = moderation_begin(m, call, &mod)) || (rc = tetrad_begin(m, call, &tet)) || (rc = ipma_begin(m, call, &ipma))) return rc;
     int* h_err = (int*)m->h_flag + 10;                   // (+8: plspm_bootstrap_fetch, +9: run_gram_i8's look at the multiplicity flag of an explicit index list)
     h_err[0] = h_err[1] = 0;
     FetchSeg segs[kBootChunksMax];
     int64_t b0 = 0;
     for (int k = 0; k < nparts; ++k) {
         call.B = parts[k]; call.rep_offset = rep_offset + b0; call.d_idx = d_idx ? d_idx + b0 * m->N : nullptr;
-        call.rows_out = rows + b0 * RS; call.chain_off = (chain || mod || tet) ? b0 : -1;
+        call.rows_out = rows + b0 * RS; call.chain_off = (chain || mod || tet || ipma) ? b0 : -1;
         if ((rc = plspm_detail_bootstrap(m, call))) return rc;
         if (k == nparts - 1) {
             // ONE error word, read with the last sub-batch: copied behind the last kernel, in front of the event its download waits for
@@ -295,6 +297,7 @@ int plspm_bootstrap(plspm_model_t* m, int64_t B, uint64_t seed, int64_t rep_offs
     derived_commit(m, chain, B);
     moderation_commit(m, mod, B);
     tetrad_commit(m, tet, B);
+    ipma_commit(m, ipma, B);
     if (h_err[0] & 4) return fail(m, PLSPM_E_STATE, "plspm_bootstrap: the persistent Gram gave up waiting for a partial tile (device shared with a long-running kernel?); set_option i8_sched 0");
     if (h_err[0] & 1) return fail(m, PLSPM_E_ARG, "plspm_bootstrap: resample index outside [0, N)");
     if ((h_err[0] & 2) || h_err[1]) return fail(m, PLSPM_E_LIMIT, "plspm_bootstrap: a resample multiplicity exceeded 127 on the int8 Gram path (set_option gram_path 1)");

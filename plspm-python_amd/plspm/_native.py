@@ -42,6 +42,7 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_structural_intervals",
            "plspm_moderation_enable", "plspm_moderation_width", "plspm_moderation_fit", "plspm_moderation_fetch", "plspm_moderation_summary", "plspm_moderation_intervals",
            "plspm_tetrad_enable", "plspm_tetrad_width", "plspm_tetrad_list", "plspm_tetrad_fit", "plspm_tetrad_fetch", "plspm_tetrad_summary", "plspm_tetrad_intervals",
+           "plspm_ipma_enable", "plspm_ipma_width", "plspm_ipma_targets", "plspm_ipma_fit", "plspm_ipma_fetch", "plspm_ipma_summary", "plspm_ipma_intervals",
            "plspm_micom_enable", "plspm_micom_width", "plspm_micom_fetch", "plspm_micom_summary", "plspm_micom_intervals", "plspm_micom_counts"]
 CI_METHODS = ("percentile", "basic", "bc", "bca")      # method ids of plspm_bootstrap_intervals
 CI_LDS_VALUES = 16384                                  # values of a column its kernel keeps in LDS (csrc/kernels_intervals.h); longer columns take a global scratch slice
@@ -144,8 +145,9 @@ def load():
     # full-sample record
     lib.plspm_structural_paths.argtypes = [vp, ctypes.POINTER(i32), vp, vp, ctypes.POINTER(i32), vp, vp]
     lib.plspm_tetrad_list.argtypes = [vp, ctypes.POINTER(i32), vp, vp, vp, vp, vp]
-    for family in ("assess", "plsc", "modelfit", "geodesic", "structural", "micom", "moderation", "tetrad"):
-        getattr(lib, "plspm_%s_enable" % family).argtypes = ([vp, i32, vp] if family in ("plsc", "modelfit", "geodesic") else [vp, i32, vp, vp, vp] if family == "moderation"
+    lib.plspm_ipma_targets.argtypes = [vp, ctypes.POINTER(i32), vp]
+    for family in ("assess", "plsc", "modelfit", "geodesic", "structural", "micom", "moderation", "tetrad", "ipma"):
+        getattr(lib, "plspm_%s_enable" % family).argtypes = ([vp, i32, vp] if family in ("plsc", "modelfit", "geodesic") else [vp, i32, vp, vp, vp] if family in ("moderation", "ipma")
                                                              else [vp, i32, vp, i32, i32] if family == "tetrad" else [vp, i32])
         getattr(lib, "plspm_%s_width" % family).restype = i32
         getattr(lib, "plspm_%s_width" % family).argtypes = [vp]
@@ -742,6 +744,50 @@ class NativeModel:
     def tetrad_intervals(self, B, original, method="bc", level=0.95):
         """``intervals`` on the tetrad records (plspm_tetrad_intervals; no bca): ([n_tet, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
         return self._side_table("tetrad", "intervals", B, original, method, level)
+
+    def ipma_enable(self, on=True, targets=None, lo=None, hi=None):
+        """Importance-performance map analysis (plspm_ipma_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the record perf [L] | sd [L] |
+        total_u [n_eff] | direct_u [n_eff] | weight_r [P] | mvperf [P] | mvimp [n_t x P] of every replicate; no other record changes.  targets: uint8 [L], the
+        target LVs (None: every LV with a predecessor); lo / hi: float64 [P], the bounds of every MV in device order."""
+        if not on:
+            self._side_call("ipma", "enable", 0, None, None, None)
+            return
+        if targets is not None:
+            targets = np.ascontiguousarray(targets, dtype=np.uint8)
+            if targets.shape != (self.L,):
+                raise ValueError("targets must have one entry per latent variable")
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        if lo.shape != (self.P,) or hi.shape != (self.P,):
+            raise ValueError("lo and hi must have one entry per manifest variable")
+        self._side_call("ipma", "enable", 1, _ptr(targets) if targets is not None else None, _ptr(lo), _ptr(hi))
+
+    @property
+    def ipma_width(self):
+        return self._side_width("ipma")
+
+    def ipma_targets(self):
+        """The target LVs of the record's mvimp rows, ascending (plspm_ipma_targets)."""
+        n = ctypes.c_int32(0)
+        self._side_call("ipma", "targets", ctypes.byref(n), None)
+        out = np.empty(n.value, dtype=np.int32)
+        self._side_call("ipma", "targets", None, _ptr(out))
+        return out
+
+    def ipma_fit(self):
+        """The full-sample IPMA record (plspm_ipma_fit): ([W] values, the record's status)."""
+        return self._side_fit("ipma")
+
+    def ipma_fetch(self, first=0, count=None):
+        """Host copy of the IPMA records [first, first + count) of the last bootstrap with the map on: (records [count, W], status [count])."""
+        return self._side_fetch("ipma", first, self.last_B - first if count is None else count)
+
+    def ipma_summary(self, B, original):
+        """``summary`` on the IPMA records (plspm_ipma_summary): ([W, 6] original, mean, std.error, perc.025, perc.975, t stat.; OK replicates)."""
+        return self._side_table("ipma", "summary", B, original)
+
+    def ipma_intervals(self, B, original, method="bc", level=0.95):
+        """``intervals`` on the IPMA records (plspm_ipma_intervals; no bca): ([W, 6] lower, upper, z0, accel, level.lower, level.upper; OK replicates)."""
+        return self._side_table("ipma", "intervals", B, original, method, level)
 
     def structural_enable(self, on=True):
         """Structural-model assessment (plspm_structural_enable): every later ``bootstrap`` / ``bootstrap_device`` call also writes the record f2 [n_dir] |

@@ -10,7 +10,8 @@ consistent PLS of the full sample and of every replicate, ``plsc()``; ``factors`
 ``structural`` (with ``bootstrap=True``: f2, inner VIF and the specific indirect effects of every replicate, ``structural()``),
 ``interactions`` (with ``bootstrap=True``: (predictor, moderator, target) names -- the two-stage moderation analysis of every replicate, ``moderation()``),
 ``tetrads`` (with ``bootstrap=True``: the confirmatory tetrad analysis of every block of four items or more, ``tetrads()``;
-``plspm.tetrad.TetradAnalysis`` takes the blocks, the set, the matrix and alpha), ``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
+``plspm.tetrad.TetradAnalysis`` takes the blocks, the set, the matrix and alpha),
+``ipma`` (with ``bootstrap=True``: True or dict(targets=..., scale=...) -- the importance-performance map of every replicate, ``ipma()``; ``plspm.ipma.Ipma``), ``precision`` ("auto": the bootstrap's moment sums on the fewest exact-integer digit planes that stay inside the error bound of the
 reference's own fp64 accumulation on the data at hand; "strict": always seven planes = correctly rounded sums, ~20 % slower).
 """
 import time
@@ -72,7 +73,7 @@ class Plspm:
     def __init__(self, data: pd.DataFrame, config: c.Config, scheme: Scheme = Scheme.CENTROID, iterations: int = 100,
                  tolerance: float = 0.000001, bootstrap: bool = False, bootstrap_iterations: int = 100, processes: int = 2,
                  seed: int = None, device_id: int = 0, devices=None, precision: str = "auto", quality: bool = False,
-                 consistent: bool = False, factors=None, structural: bool = False, interactions=None, tetrads=False):
+                 consistent: bool = False, factors=None, structural: bool = False, interactions=None, tetrads=False, ipma=False):
         iterations, bootstrap_iterations = _normalise_arguments(scheme, iterations, tolerance, bootstrap_iterations, processes)
         t_start = time.perf_counter()
         estimator = Estimator(config)
@@ -139,6 +140,20 @@ class Plspm:
                 if why is not None:
                     raise NotImplementedError("the tetrad analysis covers metric data without missing cells and without higher-order constructs: this model has " + why)
                 boot_on.native.tetrad_enable(True, ptet._options(boot_on.compiled, None, "basis", "correlation", 0.05))
+            ipma_bounds = None
+            if ipma:
+                # the IPMA kernel runs behind the solver of every replicate batch on this handle (plspm.ipma)
+                from plspm import ipma as pipma
+                from plspm import quality as pq
+                why = pq._unsupported(config, observations)
+                if why is not None:
+                    raise NotImplementedError("the importance-performance map covers metric data without missing cells and without higher-order constructs: this model has " + why)
+                ipma_options = ipma if isinstance(ipma, dict) else {}
+                unknown = set(ipma_options) - {"targets", "scale"}
+                if unknown:
+                    raise ValueError("ipma takes True or a dict with the keys targets and scale: got %s" % ", ".join(sorted(map(str, unknown))))
+                ipma_mask, *ipma_bounds = pipma._options(boot_on.compiled, observations, ipma_options.get("targets"), ipma_options.get("scale"))
+                boot_on.native.ipma_enable(True, ipma_mask, *ipma_bounds)
             pending = launch_bootstrap(boot_on, bootstrap_iterations, processes, seed, devices=devices)
         self._result = fit
         # The report frames only re-label / post-process the device outputs already on the host (fit.raw); they are built on first
@@ -189,6 +204,11 @@ class Plspm:
             if self._bootstrap.ranks() != 1:
                 raise NotImplementedError("the tetrad analysis runs on one GPU: this bootstrap was sharded over %d" % self._bootstrap.ranks())
             self._tetrads = ptet.TetradAnalysis.of_bootstrap(fit.native, fit.compiled, bootstrap_iterations)
+        self._ipma = None
+        if bootstrap and ipma:
+            if self._bootstrap.ranks() != 1:
+                raise NotImplementedError("the importance-performance map runs on one GPU: this bootstrap was sharded over %d" % self._bootstrap.ranks())
+            self._ipma = pipma.Ipma.of_bootstrap(fit.native, fit.compiled, bootstrap_iterations, ipma_bounds[0], ipma_bounds[1], scores.get)
         # fit_s: filter + upload + device fit; bootstrap_s: what the bootstrap adds (the wait for the replicates + the device summaries);
         # bootstrap_latency_s: enqueue of the replicates -> summaries on the host
         self._timings = {"fit_s": t_fit - t_start, "bootstrap_s": time.perf_counter() - t_fit,
@@ -272,6 +292,12 @@ class Plspm:
         if self._tetrads is None:
             raise Exception("To run the confirmatory tetrad analysis, set the parameters bootstrap and tetrads to True when calling Plspm")
         return self._tetrads
+
+    def ipma(self):
+        """The :class:`plspm.ipma.Ipma` of the bootstrap; raises unless bootstrap=True and ipma=True (or a dict of its options) were requested."""
+        if self._ipma is None:
+            raise Exception("To draw the importance-performance map, set the parameter bootstrap to True and ipma to True (or its options) when calling Plspm")
+        return self._ipma
 
     def structural(self):
         """The :class:`plspm.structural.Structural` assessment of the bootstrap; raises unless bootstrap=True and structural=True were requested."""
