@@ -510,6 +510,43 @@ int plspm_fimix_fetch(plspm_model_t* m, int64_t first, int64_t count, double* ou
 int plspm_fimix_posteriors(plspm_model_t* m, int64_t problem, double* out);
 
 /*
+ * ---- REBUS-PLS (response-based unit segmentation) -------------------------------------------------------------------------------
+ * Classes of rows that differ in their outer AND inner model (Esposito Vinzi, Trinchera, Squillacciotti and Tenenhaus 2008).  This library's
+ * definitions; equality with R's rebus.pls is not claimed.  Inputs: the N uploaded rows, K classes (1..16), labels c^0 [N] below K.  Iteration t = 1, 2, ...:
+ *   local models   problem k = the model on the rows with c^(t-1) = k, estimated like a bootstrap replicate (same record layout; its own n_k, treatment and `scaled`
+ *                  scalar) on the int8 route with at least seven digit planes; mean_pk, sd_pk the population mean and sd of column p over the class's rows
+ *   residuals      of every row i under every class k: y_ilk the score plspm_fit's `scores` would give row i under class k's fit (plspm_cv_predict's rule: class
+ *                  means, the class's `scaled` scalar, the record's weights, the fit's sign); z_ipk = (x_ip - mean_pk) / sd_pk; e_ipk = z_ipk - lambda_pk y_i,lv(p),k
+ *                  (lambda: the record's loading); f_ijk = y_ijk - sum_{q in pred(j)} beta_kjq y_iqk for every LV j with predecessors;
+ *                  A_ik = sum_p e_ipk^2 / lambda_pk^2, B_ik = sum_j f_ijk^2 / R^2_jk
+ *   closeness      CM_ik = sqrt( A_ik / (sum_i A_ik / (N - 2)) * B_ik / (sum_i B_ik / (N - 2)) ), both sums over all N rows
+ *   assignment     c^t_i = argmin_k CM_ik (ties: the lowest k; a NaN never wins; a row whose every CM is NaN keeps its class); changed_t = #{i : c^t_i != c^(t-1)_i}
+ *   stop           PLSPM_OK when changed_t / N < stop_crit; PLSPM_NOT_CONVERGED at t = max_iter (max_iter = 0: no iteration, the final pass on c^0);
+ *                  PLSPM_SINGULAR at iteration t when a class has fewer than min_size rows, a local fit is not PLSPM_OK, an sd_pk is 0, or a lambda_pk^2 or an
+ *                  R^2_jk is not above 1e-10: the labels stay c^(t-1)
+ *   final pass     local models, residuals and closeness once more on c^t, without reassigning: the reported records and CM, and per class the within-class sums
+ *                  sum_{i in k} e_ipk^2 [P] and sum_{i in k} f_ijk^2 [n_endo].  The same checks; PLSPM_SINGULAR there as well.  Skipped after PLSPM_SINGULAR:
+ *                  labels and history stay, every other output is NaN (status and iteration counts of the local records: -1).
+ * Every floating-point sum runs in one fixed order: a repeated call gives the same bits.  Plain metric handles whose every block is Mode A and whose model has a
+ * path: PLSPM_E_ARG otherwise, as for K outside 1..16 or a start label that is not below K; PLSPM_E_STATE without data; PLSPM_E_LIMIT where the int8 route is
+ * closed or one class's parameters exceed a workgroup's 160 KiB of LDS.  The handle's bootstrap records survive the call bit for bit.
+ *
+ * plspm_rebus_device: runs the iteration (host-driven, one host wait per iteration: changed_t, the sizes and the validity flags; the labels stay on the device).
+ *   start [N] host.  *d_labels [N] int32 / *d_cm [N * K] (NULL after PLSPM_SINGULAR): device pointers owned by the handle, valid until the next plspm_rebus_*
+ *   call or upload (either may be NULL).  Returns 0 whatever the run's status.
+ * plspm_rebus_fetch: of the last run -- labels [N]; cm [N * K] row-major; records [K * plspm_row_width()], rec_status, rec_iters [K]; sizes [K] of the labels;
+ *   within_e [K * P] (device column order), within_f [K * n_endo] (LV order); run [3] = status, iterations, h = iterations whose counters are history (h =
+ *   iterations, or iterations - 1 where the iteration itself ended PLSPM_SINGULAR); hist_changed [h], hist_sizes [h * K].  Any may be NULL; the caller sizes the
+ *   last two by max_iter.  PLSPM_E_STATE without a run (none yet; an upload or plspm_rebus_residuals voids it).
+ * plspm_rebus_residuals: e and f of every row under the one-class model (K = 1, every row in class 0): out [N * (P + n_endo)] host, row-major, e in device column
+ *   order then f in LV order; NaN where that model is not valid.  Needs no prior run.
+ */
+int plspm_rebus_device(plspm_model_t* m, int32_t K, const int32_t* start, int32_t max_iter, double stop_crit, int64_t min_size, void** d_labels, void** d_cm);
+int plspm_rebus_fetch(plspm_model_t* m, int32_t* labels, double* cm, double* records, int32_t* rec_status, int32_t* rec_iters, int64_t* sizes, double* within_e, double* within_f,
+                      int32_t* run, int32_t* hist_changed, int32_t* hist_sizes);
+int plspm_rebus_residuals(plspm_model_t* m, double* out);
+
+/*
  * ---- Bootstrap confidence intervals ---------------------------------------------------------------------------------------------
  * Two-sided intervals at a chosen level on bootstrap records in HBM, every handle kind; d_rows / B / stride as plspm_bootstrap_summary (NULL: the
  * handle's last records; else a device buffer in the record layout, e.g. the gathered records of all GPUs).  Per result column c over the m

@@ -22,6 +22,9 @@ extern "C" {
  *                     Only ever lowers the automatic size; records, status and iteration counts must be bit-identical for every cut.
  *   "last_boot_passes"   read-only: the passes the last such batch was cut into (plspm_bootstrap() runs its sub-batches as batches of their own:
  *                     the last sub-batch's)
+ *   "rebus_classes"   0 (default: as many as fit) | 1 .. 16   caps the classes whose parameters one LDS load of the REBUS row pass holds
+ *                     (plspm_rebus_device), so that the pass over several loads runs at small shapes; every output must be bit-identical for every cap.
+ *   "last_rebus_loads"   read-only: the LDS loads per row tile of the last REBUS row pass (0: none yet)
  *   "last_micom_layout"  read-only: the moment layout the last MICOM launch read (plspm_micom_enable): 1 dense upper triangles, 2 tile-packed; 0: none yet
  *
  * Experiments build only (make -C plspm-python_amd/csrc experiments, loaded through PLSPM_HIP_LIB; the release library answers PLSPM_E_ARG):

@@ -253,6 +253,12 @@ struct JackSpec { int64_t G; };
 // run_gram_i8 on a jackknife call: the 0/1 counts of problems [prob0, prob0 + nb) of the call's groups `js` into `cd`, layout of resample_i8_kernel
 int launch_jack_counts(plspm_model* m, const JackSpec& js, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
 
+// ---- plspm_rebus.hip (REBUS-PLS: response-based unit segmentation)
+// One round's problems: problem k of K is the model on the rows whose label is k; `d_label` [N] ints below K, on the device.
+struct RebusSpec { int K; const int* d_label; };
+// run_gram_i8 on a REBUS call: the 0/1 counts of problems [prob0, prob0 + nb) of the round's classes `rs` into `cd`, layout of resample_i8_kernel
+int launch_rebus_counts(plspm_model* m, const RebusSpec& rs, int64_t nb, int64_t prob0, int MT, int KB, void* cd);
+
 // ---- plspm_micom.hip (MICOM: measurement invariance of composite models on a permutation call's splits)
 // the pooled inputs of the resident rows (u [P], the diagonal blocks of R_0) into m->micom_pool, once per upload; overwrites m->gram
 int micom_prepare(plspm_model* m);

@@ -36,6 +36,7 @@ struct PermSpec;      // two-group permutation: the splits (plspm_permute.hip)
 struct StratSpec;     // stratified bootstrap of the two-group test: the draws inside each group (plspm_permute.hip)
 struct CvSpec;        // cross-validation: the folds (plspm_cv.hip)
 struct JackSpec;      // jackknife: the number of groups (plspm_jackknife.hip)
+struct RebusSpec;     // REBUS-PLS: the rows' class labels (plspm_rebus.hip)
 
 // Kernel timing (plspm_profile_*): event pairs are recycled through `pool`, so a profiled launch costs two hipEventRecord only.
 struct ProfSlot { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev, pool; double total_ms = 0.0; int64_t launches = 0; };
@@ -175,6 +176,15 @@ struct plspm_model {
     bool scores_valid = false;
     Buf fimix_rows, fimix_status, fimix_iters, fimix_desc, fimix_k, fimix_init, fimix_post;
     int64_t fimix_nprob = 0;                 // ... problems of that call (0: none)
+    // REBUS-PLS (plspm_rebus.hip): the labels, the K local records with status and iteration counts in buffers of their own (the bootstrap's survive
+    // the call), the class moments' slices, the classes' parameters and validity flags, A | B [2][K][N], the tiles' partial sums, CM [N][K], the members-only sums
+    // (per tile, then [K][P + n_endo]), the per-iteration counters [max_iter + 1][1 + K] (changed | sizes: the history), the small tables, the one-class residuals
+    Buf rebus_label, rebus_rows, rebus_status, rebus_iters, rebus_mom, rebus_par, rebus_flags, rebus_ab, rebus_part, rebus_cm, rebus_within_part, rebus_within, rebus_ctr, rebus_tab, rebus_resid;
+    Pin rebus_pin;                           // ... what the driver reads back after a round: changed | sizes [K] | flags [K]
+    int rebus_K = 0;                         // ... classes of the last plspm_rebus_device call whose results are on the handle (0: none)
+    int rebus_status_run = 0, rebus_iters_run = 0, rebus_hist = 0;      // ... its run status, its iterations and the iterations whose counters are history
+    std::vector<int> rebus_sizes;            // ... the class sizes of its labels
+    int last_rebus_loads = 0;                // LDS loads per row tile of the last REBUS row pass (read-only option "last_rebus_loads")
     int fimix_kmax = 0;                      // ... and its kmax
     std::vector<int> fimix_k_of;             // ... and every problem's K
     // The records derived from a plain bootstrap's replicates (plspm_derived.hip; the stages, what each reads and its record: derived_route.h kDerivedStage): per stage
@@ -255,8 +265,8 @@ struct plspm_model {
 struct BatchCall {
     // where the problems' counts come from: PLAIN draws B resamples (Philox keys of `seed`, replicates rep_offset .., or the explicit rows at d_idx [B][N]);
     // the other kinds bring a spec (host_internal.h) their own count kernel reads, and leave seed / rep_offset / d_idx at zero
-    enum Kind { PLAIN, PERMUTATION, STRATIFIED, CROSS_VALIDATION, JACKKNIFE } kind = PLAIN;
-    union { const PermSpec* perm = nullptr; const StratSpec* strat; const CvSpec* cv; const JackSpec* jack; };
+    enum Kind { PLAIN, PERMUTATION, STRATIFIED, CROSS_VALIDATION, JACKKNIFE, REBUS } kind = PLAIN;
+    union { const PermSpec* perm = nullptr; const StratSpec* strat; const CvSpec* cv; const JackSpec* jack; const RebusSpec* rebus; };
     int64_t B = 0, rep_offset = 0;       // B problems
     uint64_t seed = 0;
     const int32_t* d_idx = nullptr;
@@ -275,8 +285,9 @@ struct BatchCall {
 // The kind brings its own counts: the int8 route whatever "gram_path" / "i8_min_batch" say (its caller asked gram_counts_route_open), seven digit planes at
 // least (their counts add up to less than N: plspm_gram_i8.hip prepare_zs), and no draws on the aux stream.
 inline bool brings_counts(const BatchCall& c) { return c.kind != BatchCall::PLAIN; }
-// The call leaves the handle's records alone (the jackknife: buffers of its own, so that the bootstrap whose BCa intervals ask for it keeps its records).
-inline bool keeps_records(const BatchCall& c) { return c.kind == BatchCall::JACKKNIFE; }
+// The call leaves the handle's records alone (the jackknife: buffers of its own, so that the bootstrap whose BCa intervals ask for it keeps its records; REBUS-PLS:
+// the local models of a round, in buffers of their own as well).
+inline bool keeps_records(const BatchCall& c) { return c.kind == BatchCall::JACKKNIFE || c.kind == BatchCall::REBUS; }
 // Problems 2p / 2p + 1 are the two sides of split p of the resident rows: what a MICOM record compares.
 inline bool pairs_problems(const BatchCall& c) { return c.kind == BatchCall::PERMUTATION; }
 // The handle kinds the two-group tests, the cross-validation, the jackknife, the assessment and MICOM cover.
@@ -317,6 +328,7 @@ inline void void_resident(plspm_model* m, bool replaced) {
     void_records(m, REC_ALL);
     m->micom_pool_valid = false;
     m->scores_valid = false; m->fimix_nprob = 0;      // (plspm_fimix.hip: the scores and the mixture records describe the old rows)
+    m->rebus_K = 0;                                   // (plspm_rebus.hip: so do the classes)
 }
 
 // The batch driver (plspm_bootstrap.hip): enqueue the call's problems on the handle's stream.  No host synchronisation for metric models.

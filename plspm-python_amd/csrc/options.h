@@ -62,6 +62,7 @@ struct Tune {
     int nm_vlong = 1;            // one-launch categorical batch, verification: 1 one long round for the stragglers behind the fourth short one
     int strat_rows = 0;
     int boot_pass = 0;           // test seam: cap on the replicates per pass (plspm_detail_bootstrap)
+    int rebus_classes = 0;       // test seam: cap on the classes per LDS load of rebus_residual_kernel (0: as many as fit; rebus_route.h)
 };
 
 // The values an option takes: an integer in [v0, v1]; one of v0 .. v3; 0 or an integer in [v0, v1]; a multiple of 256 up to 2^30.
@@ -140,8 +141,14 @@ static constexpr OptionRow kOptions[] = {
     {"boot_pass", &Tune::boot_pass, pass_cap()},
 };
 
+// The seams of one call kind each, settable like the options above and outside their table: kOptions is what tests/golden/option_table.json records row by row.
+static constexpr OptionRow kSeamOptions[] = {
+    {"rebus_classes", &Tune::rebus_classes, in_range(0, 16)},
+};
+
 inline const OptionRow* option_find(const char* name) {
     for (const OptionRow& o : kOptions) if (!strcmp(o.name, name)) return &o;
+    for (const OptionRow& o : kSeamOptions) if (!strcmp(o.name, name)) return &o;
     return nullptr;
 }
 inline bool option_takes(const OptionValues& s, int value) {

@@ -322,6 +322,7 @@ static int gram_i8_counts(plspm_model* m, const BatchCall& call, const GramI8Pla
             case BatchCall::STRATIFIED: rc = launch_strat_counts(m, *call.strat, nb, rep0, p.MT, m->zs_KB, cd.p); break;          // ... its stratified bootstrap: draws inside each group
             case BatchCall::CROSS_VALIDATION: rc = launch_cv_counts(m, *call.cv, nb, rep0, p.MT, m->zs_KB, cd.p); break;         // 0/1 counts of the training folds, plspm_cv.hip
             case BatchCall::JACKKNIFE: rc = launch_jack_counts(m, *call.jack, nb, rep0, p.MT, m->zs_KB, cd.p); break;            // 0/1 counts of the rows a problem keeps, plspm_jackknife.hip
+            case BatchCall::REBUS: rc = launch_rebus_counts(m, *call.rebus, nb, rep0, p.MT, m->zs_KB, cd.p); break;            // 0/1 counts of a class's rows, plspm_rebus.hip
             case BatchCall::PLAIN: rc = launch_resample(m, p, stream, d_idx, call.seed, rep0, cd.p, on_aux ? m->err2.p : m->err.p); break;
         }
     }

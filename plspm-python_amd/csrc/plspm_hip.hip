@@ -418,7 +418,7 @@ struct ReadOut { const char* name; int32_t (*get)(const plspm_model*); };
 static const ReadOut kReadOuts[] = {
     {"last_i8_slices", [](const plspm_model* m) -> int32_t { return m->zs_valid ? m->zs_S : 0; }},
     {"last_i8_ratio", [](const plspm_model* m) -> int32_t { return (m->zs_valid && m->zs_ratio < 9e18) ? (int32_t)(int64_t)m->zs_ratio : 0; }},      // floor of the smallest sum|z| / max|z| (automatic plane count)
-    LAST(i8_rt), LAST(i8_short), LAST(i8_mt), LAST(i8_nibbles), LAST(i8_dma), LAST(i8_priv), LAST(i8_persist), LAST(gram_path), LAST(solver), LAST(boot_passes), LAST(strat_rows), LAST(micom_layout),
+    LAST(i8_rt), LAST(i8_short), LAST(i8_mt), LAST(i8_nibbles), LAST(i8_dma), LAST(i8_priv), LAST(i8_persist), LAST(gram_path), LAST(solver), LAST(boot_passes), LAST(strat_rows), LAST(micom_layout), LAST(rebus_loads),
     LAST(nm_codes), LAST(nm_mfma), LAST(nm_direct16), LAST(nm_one), LAST(nm_exact), LAST(nm_wave), LAST(nm_wave16), LAST(nm_flagged), LAST(nm_replayed),
     {"boot_round_units", [](const plspm_model* m) -> int32_t { return (int32_t)plspm_detail_round_units_peek(m); }},      // (64 until the digit planes of this upload exist: a query builds nothing)
     {"build_experiments", [](const plspm_model*) -> int32_t { return kExperiments; }},

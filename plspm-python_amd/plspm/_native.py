@@ -34,6 +34,7 @@ EXPORTS = ["plspm_abi_version", "plspm_device_count", "plspm_last_error", "plspm
            "plspm_cv_folds", "plspm_cv_device", "plspm_cv_fold_ids", "plspm_cv_moments", "plspm_cv_targets", "plspm_cv_predict",
            "plspm_jackknife_device", "plspm_jackknife_fetch", "plspm_jackknife_stats", "plspm_bootstrap_intervals",
            "plspm_fimix_device", "plspm_fimix_width", "plspm_fimix_fetch", "plspm_fimix_posteriors", "plspm_fimix_starts",
+           "plspm_rebus_device", "plspm_rebus_fetch", "plspm_rebus_residuals",
            "plspm_assess_enable", "plspm_assess_width", "plspm_assess_fit", "plspm_assess_fetch", "plspm_assess_summary", "plspm_assess_intervals",
            "plspm_plsc_enable", "plspm_plsc_width", "plspm_plsc_fit", "plspm_plsc_fetch", "plspm_plsc_summary", "plspm_plsc_intervals",
            "plspm_modelfit_enable", "plspm_modelfit_width", "plspm_modelfit_fit", "plspm_modelfit_fetch", "plspm_modelfit_summary", "plspm_modelfit_intervals",
@@ -141,6 +142,9 @@ def load():
     lib.plspm_fimix_width.argtypes = [vp, i32]
     lib.plspm_fimix_fetch.argtypes = [vp, i64, i64, vp, vp, vp]
     lib.plspm_fimix_posteriors.argtypes = [vp, i64, vp]
+    lib.plspm_rebus_device.argtypes = [vp, i32, vp, i32, dbl, i64, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.plspm_rebus_fetch.argtypes = [vp] * 12
+    lib.plspm_rebus_residuals.argtypes = [vp, vp]
     # the six families of side records (assessment, PLSc, model fit, geodesic discrepancy, structural assessment, MICOM): one set of signatures; only MICOM has no
     # full-sample record
     lib.plspm_structural_paths.argtypes = [vp, ctypes.POINTER(i32), vp, vp, ctypes.POINTER(i32), vp, vp]
@@ -304,6 +308,7 @@ class NativeModel:
         self.P = int(self.block_offset[-1])
         path = np.ascontiguousarray(path, dtype=np.uint8)
         modes = np.ascontiguousarray(modes, dtype=np.int32)
+        self.n_endo = int((path.reshape(self.L, self.L).sum(axis=1) > 0).sum())      # LVs that have a predecessor
         self._h = lib.plspm_model_create(self.P, self.L, _ptr(self.block_offset), _ptr(path), _ptr(modes), int(scheme), int(bool(scaled)),
                                          int(max_iter), float(tol), int(device_id))
         if not self._h:
@@ -596,6 +601,36 @@ class NativeModel:
                                                  ctypes.byref(d_st), ctypes.byref(d_it)), "plspm_fimix_device")
         self.last_fimix = (len(k_of), kmax, k_of.copy())
         return d_out.value, d_st.value, d_it.value
+
+    def rebus(self, classes, start, max_iter=100, stop_crit=0.005, min_size=10):
+        """REBUS-PLS on the uploaded rows (plspm_rebus_device): ``start`` [N] labels below ``classes``.  Returns ``rebus_fetch()``."""
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        if start.shape != (self.N,):
+            raise ValueError("start = [N] labels")
+        self._check(self._lib.plspm_rebus_device(self._h, int(classes), _ptr(start), int(max_iter), float(stop_crit), int(min_size), None, None), "plspm_rebus_device")
+        self.last_rebus = (int(classes), int(max_iter))
+        return self.rebus_fetch()
+
+    def rebus_fetch(self):
+        """Host copy of the last ``rebus`` run (plspm_rebus_fetch): dict(status, iterations, labels [N], cm [N, K], records [K, R], rec_status, rec_iters [K],
+        sizes [K], within_e [K, P] (device column order), within_f [K, n_endo], changed [h], hist_sizes [h, K])."""
+        K, max_iter = getattr(self, "last_rebus", (0, 0))
+        n_endo = self.n_endo
+        out = dict(labels=np.empty(self.N, dtype=np.int32), cm=np.empty((self.N, max(K, 1))), records=np.empty((max(K, 1), self.row_width)), rec_status=np.empty(max(K, 1), dtype=np.int32),
+                   rec_iters=np.empty(max(K, 1), dtype=np.int32), sizes=np.empty(max(K, 1), dtype=np.int64), within_e=np.empty((max(K, 1), self.P)), within_f=np.empty((max(K, 1), n_endo)))
+        run = np.zeros(3, dtype=np.int32)
+        changed, hist = np.zeros(max(max_iter, 1), dtype=np.int32), np.zeros((max(max_iter, 1), max(K, 1)), dtype=np.int32)
+        self._check(self._lib.plspm_rebus_fetch(self._h, _ptr(out["labels"]), _ptr(out["cm"]), _ptr(out["records"]), _ptr(out["rec_status"]), _ptr(out["rec_iters"]), _ptr(out["sizes"]),
+                                                _ptr(out["within_e"]), _ptr(out["within_f"]), _ptr(run), _ptr(changed), _ptr(hist)), "plspm_rebus_fetch")
+        out.update(status=int(run[0]), iterations=int(run[1]), changed=changed[:run[2]].copy(), hist_sizes=hist[:run[2]].copy())
+        return out
+
+    def rebus_residuals(self):
+        """e [N, P] (device column order) and f [N, n_endo] of every row under the one-class model (plspm_rebus_residuals)."""
+        n_endo = self.n_endo
+        out = np.empty((self.N, self.P + n_endo))
+        self._check(self._lib.plspm_rebus_residuals(self._h, _ptr(out)), "plspm_rebus_residuals")
+        return out[:, :self.P].copy(), out[:, self.P:].copy()
 
     def fimix_width(self, kmax):
         return int(self._lib.plspm_fimix_width(self._h, int(kmax)))
